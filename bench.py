@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- forward+backward renders/sec of the HIP rasterizer on BASELINE.json's headline config.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3_synth_1M_1080p] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3_synth_1M_1080p] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline]]
 
 A "step" is one forward + backward pass of the rasterizer (GaussianRasterizer through the
 C ABI) for one 1920x1080 camera over 1 M synthetic Gaussians already resident in HBM, with a
@@ -11,6 +12,12 @@ cameras (default 2) of its own over the replicated Gaussians and adds up their p
 the 59-float/Gaussian sums are exchanged over RCCL, waited for, and consumed by one fused Adam step,
 all inside the timed step -- a synchronous data-parallel iteration, as the reference trains
 (weak scaling in cameras).  Prints ONE JSON line on rank 0.
+
+A plain run only sets up, warms up, times the K steps and prints the headline (value, ms_per_step).  --full adds what
+takes work of its own: the per-stage hipEvent pass, the pair counts, the roofline and lane-slot accounting, the PMC
+figures of profiles/, the CPU baseline with its parity check (--no-cpu-baseline drops it) and, N > 1, the cost of the
+exchange's parts.  --dump-outputs DIR writes what the last timed step computed (rank 0) as float32 .npy files; see
+dump_outputs().
 """
 from __future__ import annotations
 
@@ -69,13 +76,56 @@ def algorithmic_bytes(P, N, HW, K, M, n_marked=None):
     }
 
 
+DUMP_MAX_ROWS = 65536            # per-Gaussian outputs: a fixed sample of rows beyond this many Gaussians
+DUMP_MAX_PIXELS = 1 << 21         # the image: a fixed sample of pixels beyond this many (1920 x 1080 is written whole)
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, color, radii, grads):
+    """What a caller of the timed path receives from its last step, as float32 .npy files in out_dir:
+    color.npy [3, H, W] (or color_pixels.npy [3, n] + pixel_index.npy for images over DUMP_MAX_PIXELS), radii.npy [P] and
+    dL_d<param>.npy [P, ...] (or, beyond DUMP_MAX_ROWS Gaussians, the rows listed in gaussian_index.npy, the same rows in every
+    file).  The samples are drawn with a fixed seed from the sizes alone, so two builds given the same arguments write the
+    same elements; at most 64 MB in all."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    color = color.detach().float().cpu().numpy()
+    P = int(radii.shape[0])
+    files = {}
+    C_, H_, W_ = color.shape
+    if H_ * W_ > DUMP_MAX_PIXELS:
+        pix = np.sort(np.random.default_rng(DUMP_SEED).choice(H_ * W_, DUMP_MAX_PIXELS, replace=False))
+        files["color_pixels"] = color.reshape(C_, H_ * W_)[:, pix]
+        files["pixel_index"] = pix.astype(np.float64)
+    else:
+        files["color"] = color
+    rows = None
+    if P > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED + 1).choice(P, DUMP_MAX_ROWS, replace=False))
+        files["gaussian_index"] = rows.astype(np.float64)
+        rows_t = torch.as_tensor(rows, dtype=torch.int64, device=radii.device)
+    take = (lambda t: t) if rows is None else (lambda t: t.index_select(0, rows_t))
+    files["radii"] = take(radii.detach()).float().cpu().numpy()
+    for name, g in zip(("means3D", "opacities", "shs", "scales", "rotations"), grads):
+        files["dL_d" + name] = take(g.detach()).float().cpu().numpy()
+    total = sum(a.nbytes for a in files.values())
+    assert total <= 64 << 20, f"--dump-outputs would write {total} bytes"
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(files)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="cfg3_synth_1M_1080p")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-stage times, pair counts, roofline, lane counters, "
+                    "CPU baseline and parity, N > 1 exchange breakdown (each outside the timed steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's image, radii and gradients as float32 .npy files into DIR")
     ap.add_argument("--cameras-per-rank", type=int, default=0, help="N > 1: cameras every rank renders per step (default 2; 1 with --gpus 1)")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--opt", action="append", default=[], help="native tuning knob name=value (include/gsr.h gsr_set_option)")
@@ -167,29 +217,29 @@ def main():
         means2D = means2D_placeholder
         if arena is None:
             color, radii = GaussianRasterizer(raster_settings=settings[b])(means3D=means3D, means2D=means2D, shs=shs, opacities=opac, scales=scales, rotations=rots)
-            return color, torch.autograd.grad(color, params, grad_outputs=dL), None
+            return color, radii, torch.autograd.grad(color, params, grad_outputs=dL), None
         with gradient_arena(arena):        # around the forward call too: the arena's slices are zero-filled beside the forward pass
             color, radii = GaussianRasterizer(raster_settings=settings[b])(means3D=means3D, means2D=means2D, shs=shs, opacities=opac, scales=scales, rotations=rots)
             mask = composited_mask(color) if (ex_sparse and world > 1) else None
             grads = torch.autograd.grad(color, params, grad_outputs=dL)
-        return color, grads, mask
+        return color, radii, grads, mask
 
     def step():
         e = state["ex"]
         if world == 1:
             for b in range(B):
-                color, grads, _ = render_backward(b, None)
-            state["color"], state["grads"] = color, grads
+                color, radii, grads, _ = render_backward(b, None)
+            state["color"], state["radii"], state["grads"] = color, radii, grads
             return
         arena = e.arena()                                 # waits (on the stream) for the exchange that last used this arena
         union = None
         for b in range(B):
-            color, grads, mask = render_backward(b, arena if b == 0 else scratch_arena)
+            color, radii, grads, mask = render_backward(b, arena if b == 0 else scratch_arena)
             if b > 0:
                 arena.add_(scratch_arena)                 # this rank's cameras, summed
             if mask is not None:
                 union = mask if union is None else (union | mask)
-        state["color"], state["grads"] = color, grads
+        state["color"], state["radii"], state["grads"] = color, radii, grads
         if state["exchange"]:
             e.launch(visible=union)
             if e.mode == "sync":
@@ -245,12 +295,31 @@ def main():
     gc.enable()
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
+    bytes_sent = ex.bytes_last if ex is not None else 0
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state["color"], state["radii"], state["grads"])
+
+    metric = "forward+backward renders/sec @1080p, 1M Gaussians; HBM GB/s vs roofline"
+    parallelism = (f"dp{world} ({B} camera{'s' if B > 1 else ''} per GPU per step" +
+                   (", gradients summed over RCCL and consumed by a fused Adam step inside the step)" if world > 1 else ")"))
+    if not args.full:
+        if rank == 0:
+            print(json.dumps({
+                "metric": metric,
+                "value": round(value, 3), "unit": "renders/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                "dtype": "f32", "data": "synthetic", "allreduce_bytes_per_step": int(bytes_sent),
+                "config": {"workload": args.config, "gaussians": P, "width": W, "height": H, "sh_degree": D,
+                           "cameras_per_step": world * B, "parallelism": parallelism}}), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- N > 1: what the parts cost (outside the timed region): the same K steps without the exchange, without exchange and optimiser,
     # K exchanges alone, and the delayed-update variant ----
     exchange = None
     if ex is not None:
-        bytes_sent = ex.bytes_last
         state["exchange"] = False
         no_ex_ms = timed(args.steps) / args.steps * 1e3
         state["consume"] = False
@@ -461,7 +530,7 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": "forward+backward renders/sec @1080p, 1M Gaussians; HBM GB/s vs roofline",
+            "metric": metric,
             "value": round(value, 3), "unit": "renders/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
@@ -469,8 +538,7 @@ def main():
             "config": {"workload": args.config, "gaussians": P, "width": W, "height": H, "sh_degree": D,
                        "num_rendered_pairs": int(N), "pairs_under_reference_tile_rule": int(N_ref_rule),
                        "cameras_per_step": world * B,
-                       "parallelism": f"dp{world} ({B} camera{'s' if B > 1 else ''} per GPU per step" +
-                                      (", gradients summed over RCCL and consumed by a fused Adam step inside the step)" if world > 1 else ")")},
+                       "parallelism": parallelism},
             "roofline": roofline,
             "cpu_baseline": cpu,
         }

@@ -2,7 +2,7 @@
 """Timeline of the kernels of one bench step from a rocprofv3 --kernel-trace CSV: start offset, duration and queue of every
 dispatch of the last complete step (a step = from one preprocess_fwd_kernel to the next).
 
-    python scripts/kernel_timeline.py gpurun_out/kt/**/kt_kernel_trace.csv [--step -2]
+    python scripts/kernel_timeline.py results/kt/**/kt_kernel_trace.csv [--step -2]
 """
 import csv
 import glob
@@ -10,7 +10,7 @@ import sys
 
 
 def main():
-    pat = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/kt/**/*kernel_trace.csv"
+    pat = sys.argv[1] if len(sys.argv) > 1 else "results/kt/**/*kernel_trace.csv"
     which = int(sys.argv[sys.argv.index("--step") + 1]) if "--step" in sys.argv else -2
     f = sorted(glob.glob(pat, recursive=True))[0]
     rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))

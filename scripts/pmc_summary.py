@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Summarise rocprofv3 --pmc CSVs (scripts/pmc_passes.sh): per kernel, mean counter value per dispatch."""
 import csv, glob, sys, collections, json, os
-d = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/pmc"
+d = sys.argv[1] if len(sys.argv) > 1 else "results/pmc"
 tag = sys.argv[2] if len(sys.argv) > 2 else "run"
 res = collections.defaultdict(lambda: collections.defaultdict(list))
 for f in sorted(glob.glob(os.path.join(d, f"{tag}_pass*_counter_collection.csv"))):

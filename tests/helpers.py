@@ -1,4 +1,6 @@
 """Shared test helpers: scene -> oracle Scene conversion, tolerances."""
+import os
+
 import numpy as np
 
 from gaussian_transformer_amd import synth
@@ -8,6 +10,18 @@ from oracle import ref
 # largest reference magnitude of that tensor, with the same absolute floor).
 RGB_ATOL = 1e-4
 GRAD_RTOL = 1e-3
+
+
+def cpu_math_as_recorded() -> bool:
+    """True when this host's torch CPU kernels round sqrt, log, exp, sigmoid and bmm bit for bit as on the host the
+    CPU-side golden fixtures (densify.npz, scene_io.npz) were recorded on (tests/golden/cpu_math_probe.npz, recorded there).
+    torch runs these through MKL, whose code path -- and last-place rounding -- depends on the CPU's vendor and ISA."""
+    import torch
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cpu_math_probe.npz"))
+    x, y = torch.from_numpy(g["x"]), torch.from_numpy(g["y"])
+    got = {"sqrt": x.sqrt(), "log": x.log(), "exp": y.exp(), "sigmoid": y.sigmoid(),
+           "bmm": torch.bmm(torch.from_numpy(g["a"]), torch.from_numpy(g["b"]))}
+    return all(np.array_equal(v.numpy(), g[k]) for k, v in got.items())
 
 
 def oracle_scene(sc: synth.SyntheticScene, **over) -> ref.Scene:

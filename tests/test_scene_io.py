@@ -12,6 +12,7 @@ from gaussian_transformer_amd import io as gio
 from gaussian_transformer_amd import scene_io as sio
 from gaussian_transformer_amd.densify import DensityController, OptimizationParams
 from gaussian_transformer_amd.model import GaussianParams
+from tests.helpers import cpu_math_as_recorded
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -111,11 +112,20 @@ def _controller_from_fixture(gold, adam="torch"):
     return ctl
 
 
+def _same(a, b):
+    # bit for bit where torch's CPU kernels round as on the recording host (Adam's sqrt goes through MKL, whose code path
+    # depends on the CPU); elsewhere within the last-place tolerance tests/test_densify.py allows the GPU's Adam
+    if cpu_math_as_recorded():
+        np.testing.assert_array_equal(a, b)
+    else:
+        np.testing.assert_allclose(a, b, rtol=2e-6, atol=2e-7)
+
+
 def _check_capture(cap, gold):
     assert len(cap) == int(gold["ck_len"]) == len(sio.CAPTURE_FIELDS) == 12
     assert cap[0] == int(gold["ck_active_sh_degree"]) and cap[11] == float(gold["ck_spatial_lr_scale"])
     for idx, k in zip(range(1, 7), ("xyz", "f_dc", "f_rest", "scaling", "rotation", "opacity")):     # the tuple's own order
-        np.testing.assert_array_equal(cap[idx].detach().numpy(), gold[f"ck_{idx}_{k}"])
+        _same(cap[idx].detach().numpy(), gold[f"ck_{idx}_{k}"])
     np.testing.assert_array_equal(cap[7].numpy(), gold["ck_7_max_radii2D"])
     np.testing.assert_array_equal(cap[8].numpy(), gold["ck_8_xyz_gradient_accum"]); np.testing.assert_array_equal(cap[9].numpy(), gold["ck_9_denom"])
     sd = cap[10]
@@ -127,8 +137,8 @@ def _check_capture(cap, gold):
     for pid in range(6):
         st = sd["state"][pid]
         assert float(st["step"]) == float(gold[f"ck_opt_state{pid}_step"])
-        np.testing.assert_array_equal(st["exp_avg"].numpy(), gold[f"ck_opt_state{pid}_exp_avg"])
-        np.testing.assert_array_equal(st["exp_avg_sq"].numpy(), gold[f"ck_opt_state{pid}_exp_avg_sq"])
+        _same(st["exp_avg"].numpy(), gold[f"ck_opt_state{pid}_exp_avg"])
+        _same(st["exp_avg_sq"].numpy(), gold[f"ck_opt_state{pid}_exp_avg_sq"])
 
 
 def test_checkpoint_capture_restore_match_the_reference(gold, tmp_path):
@@ -149,7 +159,7 @@ def test_checkpoint_capture_restore_match_the_reference(gold, tmp_path):
     m = ctl2.model
     for k, attr in zip(("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation"),
                        ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation")):
-        np.testing.assert_array_equal(getattr(m, attr).detach().numpy(), gold[f"ck_after_{k}"])
+        _same(getattr(m, attr).detach().numpy(), gold[f"ck_after_{k}"])
     assert [g["lr"] for g in ctl2.optimizer.param_groups if g["name"] == "xyz"][0] == pytest.approx(float(gold["ck_after_lr_xyz"]), rel=1e-12)
 
 
