@@ -30,6 +30,9 @@ def direct_all_reduce(flat: torch.Tensor, group=None, scratch: Optional[torch.Te
     does not depend on which rank owns it, i.e. not on where the element sits in the buffer: a compacted (sparse) exchange
     gives bitwise the same sums as the dense one, and every rank holds identical bits.
     Point-to-point only (batch_isend_irecv), so it also runs on gloo.  In place; returns `flat`.
+    gloo's point-to-point ops on a device tensor are not ordered with its stream (sums of a compacted buffer still being filled were
+    seen): on gloo the host waits for the stream before each phase -- what is sent is complete, what is received overwrites nothing
+    still to be read -- and for the device after it.
     Not the default of bench.py: which of the two is faster on an 8-GPU node has not been measured (one GPU per box here)."""
     world = dist.get_world_size(group)
     if world == 1:
@@ -44,6 +47,15 @@ def direct_all_reduce(flat: torch.Tensor, group=None, scratch: Optional[torch.Te
         scratch = torch.empty(((world - 1) * per,), dtype=flat.dtype, device=flat.device)
     peers = [r for r in range(world) if r != rank]
     to_global = (lambda r: dist.get_global_rank(group, r)) if group is not None else (lambda r: r)
+    host_moved = flat.device.type == "cuda" and dist.get_backend(group) == "gloo"
+
+    def run(ops):
+        if host_moved:
+            torch.cuda.current_stream(flat.device).synchronize()
+        for w in (dist.batch_isend_irecv(ops) if ops else []):
+            w.wait()
+        if host_moved:
+            torch.cuda.synchronize(flat.device)
     # phase 1: my slice of everyone's buffer comes to me
     ops, bufs = [], {}
     for k, r in enumerate(peers):
@@ -53,8 +65,7 @@ def direct_all_reduce(flat: torch.Tensor, group=None, scratch: Optional[torch.Te
             ops.append(dist.P2POp(dist.irecv, buf, to_global(r), group))
         if hi(r) > lo(r):
             ops.append(dist.P2POp(dist.isend, flat[lo(r):hi(r)], to_global(r), group))
-    for w in (dist.batch_isend_irecv(ops) if ops else []):
-        w.wait()
+    run(ops)
     if mine.numel():
         if rank == 0:
             for r in peers:
@@ -71,8 +82,7 @@ def direct_all_reduce(flat: torch.Tensor, group=None, scratch: Optional[torch.Te
             ops.append(dist.P2POp(dist.irecv, flat[lo(r):hi(r)], to_global(r), group))
         if mine.numel():
             ops.append(dist.P2POp(dist.isend, mine, to_global(r), group))
-    for w in (dist.batch_isend_irecv(ops) if ops else []):
-        w.wait()
+    run(ops)
     return flat
 
 
@@ -121,8 +131,10 @@ class GradientExchange:
         self.sh_active = None                            # None = all M coefficient columns
         self.sparse_slack = sparse_slack                 # capacity of the compacted buffer = last union * [0] + [1] rows
         self._union_known = None                         # size of the last union the sparse exchange looked at (None: never)
-        self._count_host = None
-        self._comp = None
+        # per arena index, because the exchanges of several arenas can be in flight at once: the compacted buffer of its sparse
+        # exchange, and the word + event through which the union's size reaches the host (reused only once that arena is handed out again)
+        n = len(self.arenas)
+        self._comp, self._count_host, self._count_ev = [None] * n, [None] * n, [None] * n
         self.union_rows = 0
         self.sparse_overflows = 0
 
@@ -152,9 +164,12 @@ class GradientExchange:
         return out
 
     # ---- exchange ----
-    def _reduce(self, t: torch.Tensor, waits: list):
+    def _reduce(self, t: torch.Tensor, waits: list, shared_scratch: bool = True):
         self.bytes_last += t.numel() * t.element_size()
         if self.algo == "direct":
+            if not shared_scratch:                      # off the stream the launches use (overflow at wait time): a scratch of its own
+                direct_all_reduce(t, self.group)
+                return
             per = (t.numel() + self.world - 1) // self.world
             if self.scratch is None or self.scratch.numel() < (self.world - 1) * per or self.scratch.dtype != t.dtype:
                 self.scratch = torch.empty(((self.world - 1) * per,), dtype=t.dtype, device=t.device)
@@ -176,7 +191,7 @@ class GradientExchange:
             ctx = torch.cuda.stream(self.comm_stream) if side else _NullCtx()
             with ctx:
                 if visible is not None:
-                    self._launch_sparse(flat, visible, waits)
+                    self._launch_sparse(idx, flat, visible, waits)
                 elif self.sh_active is not None and self.sh_active < self.M:
                     self._launch_active_sh(flat, waits)
                 else:
@@ -210,11 +225,12 @@ class GradientExchange:
             return self.P
         return min(self.P, int(self._union_known * self.sparse_slack[0]) + int(self.sparse_slack[1]))
 
-    def _launch_sparse(self, flat, visible, waits):
+    def _launch_sparse(self, i, flat, visible, waits):
         """Exchange only the rows of the union of the ranks' masks, WITHOUT a host synchronisation on the compute stream: the rows are
         compacted into a buffer of fixed capacity (what the union needed recently, + 25 %) through a prefix sum of the mask; the union's
         size goes to the host asynchronously and is looked at when the exchange is waited for -- a union that did not fit (the camera
-        moved a lot) is exchanged densely then, from the gradients that are still untouched in the arena."""
+        moved a lot) is exchanged densely then, from the gradients that are still untouched in the arena.  `i`: the arena's index, whose
+        compacted buffer and count word this exchange uses (those of other arenas may belong to exchanges still in flight)."""
         vis = visible.to(torch.uint8, copy=True).contiguous()          # a copy: the reduction below must not overwrite the caller's mask
         self.bytes_last += vis.numel()
         dist.all_reduce(vis, op=dist.ReduceOp.MAX, group=self.group)      # union of the ranks' visibility masks
@@ -222,20 +238,22 @@ class GradientExchange:
         cap = self._sparse_capacity()
         count_dev = pos[-1:] + 1
         if self.device.type == "cuda":
-            if self._count_host is None:
-                self._count_host = torch.zeros((1,), dtype=torch.int64).pin_memory()
-            self._count_host.copy_(count_dev, non_blocking=True)
-            count_ev = torch.cuda.Event(); count_ev.record(torch.cuda.current_stream(self.device))
+            if self._count_host[i] is None:
+                self._count_host[i] = torch.zeros((1,), dtype=torch.int64).pin_memory()
+                self._count_ev[i] = torch.cuda.Event()
+            count_host, count_ev = self._count_host[i], self._count_ev[i]
+            count_host.copy_(count_dev, non_blocking=True)
+            count_ev.record(torch.cuda.current_stream(self.device))
         else:
-            self._count_host, count_ev = count_dev.clone(), None
+            count_host, count_ev = count_dev.clone(), None
         inside = (vis != 0) & (pos < cap)
         idx = torch.where(inside, pos, torch.full_like(pos, cap))         # everything else lands in the dump row `cap`
         v = self.views(flat)
         widths = [v[n].reshape(self.P, -1).shape[1] for n in self.names]
         W = sum(widths)
-        if self._comp is None or self._comp.shape[0] < cap + 1 or self._comp.shape[1] != W:
-            self._comp = torch.empty((cap + 1, W), dtype=flat.dtype, device=flat.device)
-        comp = self._comp[:cap + 1]
+        if self._comp[i] is None or self._comp[i].shape[0] < cap + 1 or self._comp[i].shape[1] != W:
+            self._comp[i] = torch.empty((cap + 1, W), dtype=flat.dtype, device=flat.device)
+        comp = self._comp[i][:cap + 1]
         off = 0
         for n, w in zip(self.names, widths):                              # gathered per parameter straight into the compacted buffer
             comp[:, off:off + w].index_copy_(0, idx, v[n].reshape(self.P, w))
@@ -245,17 +263,17 @@ class GradientExchange:
         for piece in self._pieces_of(payload.reshape(-1)):
             self._reduce(piece, waits)
 
-        def finish():
+        def finish():                                                     # reads only this launch's own objects
             if count_ev is not None:
                 count_ev.synchronize()                                    # recorded before the exchange was even launched: long done
-            n_union = int(self._count_host.item())
+            n_union = int(count_host.item())
             self._union_known = n_union
             self.union_rows = n_union
             if n_union > cap:                                             # did not fit: the arena still holds this rank's own gradients
                 self.sparse_overflows += 1
                 late: list = []
                 for piece in self._pieces(flat):
-                    self._reduce(piece, late)                             # same algorithm (and summation order) as the dense exchange
+                    self._reduce(piece, late, shared_scratch=False)       # same algorithm (and summation order) as the dense exchange
                 for w in late:
                     w.wait()
                 return
