@@ -5,6 +5,7 @@
 // initialise the Gaussian scales from the SfM cloud: scales = log(sqrt(clamp_min(dist2, 1e-7)))).
 // Semantics restated from that call site: for point i, the mean of the three smallest squared Euclidean
 // distances to the OTHER points (index != i; coincident points count with distance 0).  Exact, not approximate.
+// Clouds of fewer than four points: the mean over the one or two other points, 0 for a single point.
 //
 // gfx950 shape: points are ordered along a 30-bit Morton curve (rocPRIM radix sort), cut into boxes of 1024
 // consecutive points with their bounding boxes; one lane per point first looks at its 2x3 curve neighbours,
@@ -168,7 +169,10 @@ __global__ __launch_bounds__(256) void knn_query_kernel(int N, int nbox, const f
             keep3(dx * dx + dy * dy + dz * dz, best);
         }
     }
-    out[i] = (best[0] + best[1] + best[2]) / 3.f;
+    // fewer than four points: best[] beyond the N - 1 neighbours that exist still holds its FLT_MAX start value; the mean is taken
+    // over those that exist, and a single point gets 0 (include/gsr_knn.h) -- finite, so that log(sqrt(clamp_min(., 1e-7))) is
+    const int nn = min(N - 1, 3);
+    out[i] = nn == 3 ? (best[0] + best[1] + best[2]) / 3.f : nn == 2 ? (best[0] + best[1]) / 2.f : nn == 1 ? best[0] : 0.f;
 }
 
 hipError_t knn_workspace_bytes(int N, size_t *bytes) {

@@ -22,8 +22,13 @@ namespace gsr {
 #define SSIM_K 11
 #define SSIM_T 16
 #define SSIM_HALO (SSIM_T + 2 * SSIM_R)   // 26
-#define SSIM_C1 0.0001f                   // 0.01^2
-#define SSIM_C2 0.0009f                   // 0.03^2
+#define SSIM_C1 (0.01 * 0.01)
+#define SSIM_C2 (0.03 * 0.03)
+// The moments and everything derived from them are carried in float64.  In float32 the variance s11 - m1*m1 of a flat or smooth
+// patch of level c is the difference of two numbers of size c^2 and comes out with an absolute error of ~2^-24 c^2, which stands
+// against C2 = 9e-4 alone: 1e-4 relative on SSIM and, through the three derivative maps of size 1/C2 that cancel in the backward
+// pass, on the gradient (tests/test_gpu_loss_edges.py: flat backgrounds, one bright pixel).  The images, the derivative maps and
+// the gradient stay float32 in memory: the kernels remain bound by the same HBM traffic.
 
 struct SsimWeights { float g[SSIM_K]; };
 
@@ -46,7 +51,7 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int C, int H, int W, c
                                                           float *__restrict__ dmaps /*[3][C][H][W]*/,
                                                           float *__restrict__ partial /*[blocks][2]*/) {
     __shared__ float sx[SSIM_HALO][SSIM_HALO + 1], sy[SSIM_HALO][SSIM_HALO + 1];
-    __shared__ float hz[5][SSIM_HALO][SSIM_T + 1];
+    __shared__ double hz[5][SSIM_HALO][SSIM_T + 1];
     __shared__ float red[2][4];
     const int tid = threadIdx.x, lx = tid & 15, ly = tid >> 4;
     const int c = blockIdx.z, x0 = blockIdx.x * SSIM_T, y0 = blockIdx.y * SSIM_T;
@@ -61,19 +66,19 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int C, int H, int W, c
     __syncthreads();
     for (int i = tid; i < SSIM_HALO * SSIM_T; i += 256) {            // horizontal pass on 26 rows x 16 columns
         const int r = i >> 4, q = i & 15;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
 #pragma unroll
         for (int k = 0; k < SSIM_K; k++) {
-            const float xv = sx[r][q + k], yv = sy[r][q + k], w = wts.g[k];
-            a0 += w * xv; a1 += w * yv; a2 += w * xv * xv; a3 += w * yv * yv; a4 += w * xv * yv;
+            const double xv = sx[r][q + k], yv = sy[r][q + k], w = wts.g[k];
+            a0 += w * xv; a1 += w * yv; a2 += w * (xv * xv); a3 += w * (yv * yv); a4 += w * (xv * yv);
         }
         hz[0][r][q] = a0; hz[1][r][q] = a1; hz[2][r][q] = a2; hz[3][r][q] = a3; hz[4][r][q] = a4;
     }
     __syncthreads();
-    float m1 = 0.f, m2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;
+    double m1 = 0.0, m2 = 0.0, s11 = 0.0, s22 = 0.0, s12 = 0.0;
 #pragma unroll
     for (int k = 0; k < SSIM_K; k++) {
-        const float w = wts.g[k];
+        const double w = wts.g[k];
         m1 += w * hz[0][ly + k][lx]; m2 += w * hz[1][ly + k][lx]; s11 += w * hz[2][ly + k][lx];
         s22 += w * hz[3][ly + k][lx]; s12 += w * hz[4][ly + k][lx];
     }
@@ -81,15 +86,15 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int C, int H, int W, c
     const bool in = x < W && y < H;
     float l1 = 0.f, ss = 0.f;
     if (in) {
-        const float a1 = 2.f * m1 * m2 + SSIM_C1, sig12 = s12 - m1 * m2, a2 = 2.f * sig12 + SSIM_C2;
-        const float b1 = m1 * m1 + m2 * m2 + SSIM_C1, b2 = (s11 - m1 * m1) + (s22 - m2 * m2) + SSIM_C2;
-        const float invD = 1.f / (b1 * b2);
-        const float f = a1 * a2 * invD;
+        const double a1 = 2.0 * m1 * m2 + SSIM_C1, sig12 = s12 - m1 * m2, a2 = 2.0 * sig12 + SSIM_C2;
+        const double b1 = m1 * m1 + m2 * m2 + SSIM_C1, b2 = (s11 - m1 * m1) + (s22 - m2 * m2) + SSIM_C2;
+        const double invD = 1.0 / (b1 * b2);
+        const double f = a1 * a2 * invD;
         const size_t p = base + (size_t)y * W + x, CHW = (size_t)C * plane;
-        dmaps[p] = (2.f * m2 * (a2 - a1) - f * 2.f * m1 * (b2 - b1)) * invD;   // d f / d mu1 (total)
-        dmaps[CHW + p] = -f / b2;                                               // d f / d E[x^2]
-        dmaps[2 * CHW + p] = 2.f * a1 * invD;                                   // d f / d E[xy]
-        ss = f;
+        dmaps[p] = (float)((2.0 * m2 * (a2 - a1) - f * 2.0 * m1 * (b2 - b1)) * invD);   // d f / d mu1 (total)
+        dmaps[CHW + p] = (float)(-f / b2);                                               // d f / d E[x^2]
+        dmaps[2 * CHW + p] = (float)(2.0 * a1 * invD);                                   // d f / d E[xy]
+        ss = (float)f;
         l1 = fabsf(sx[ly + SSIM_R][lx + SSIM_R] - sy[ly + SSIM_R][lx + SSIM_R]);
     }
     // block sums (fixed order: deterministic)
@@ -130,7 +135,7 @@ __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int C, int H, int W, c
                                                           const float *__restrict__ grad_loss /*[1] or null*/,
                                                           float *__restrict__ grad_img) {
     __shared__ float sm[3][SSIM_HALO][SSIM_HALO + 1];
-    __shared__ float hz[3][SSIM_HALO][SSIM_T + 1];
+    __shared__ double hz[3][SSIM_HALO][SSIM_T + 1];
     const int tid = threadIdx.x, lx = tid & 15, ly = tid >> 4;
     const int c = blockIdx.z, x0 = blockIdx.x * SSIM_T, y0 = blockIdx.y * SSIM_T;
     const size_t plane = (size_t)H * W, base = (size_t)c * plane, CHW = (size_t)C * plane;
@@ -146,19 +151,19 @@ __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int C, int H, int W, c
     __syncthreads();
     for (int i = tid; i < SSIM_HALO * SSIM_T; i += 256) {
         const int r = i >> 4, q = i & 15;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
 #pragma unroll
         for (int k = 0; k < SSIM_K; k++) {
-            const float w = wts.g[k];
+            const double w = wts.g[k];
             a0 += w * sm[0][r][q + k]; a1 += w * sm[1][r][q + k]; a2 += w * sm[2][r][q + k];
         }
         hz[0][r][q] = a0; hz[1][r][q] = a1; hz[2][r][q] = a2;
     }
     __syncthreads();
-    float gA = 0.f, gB = 0.f, gC = 0.f;
+    double gA = 0.0, gB = 0.0, gC = 0.0;
 #pragma unroll
     for (int k = 0; k < SSIM_K; k++) {
-        const float w = wts.g[k];
+        const double w = wts.g[k];
         gA += w * hz[0][ly + k][lx]; gB += w * hz[1][ly + k][lx]; gC += w * hz[2][ly + k][lx];
     }
     const int x = x0 + lx, y = y0 + ly;
@@ -168,7 +173,7 @@ __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int C, int H, int W, c
         const float d = xv - yv;
         const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);           // torch.abs backward: sign(0) = 0
         const float up = grad_loss ? grad_loss[0] : 1.f;
-        grad_img[p] = up * inv_n * ((1.f - lambda) * sgn - lambda * (gA + 2.f * xv * gB + yv * gC));
+        grad_img[p] = (float)((double)up * inv_n * ((1.0 - lambda) * sgn - (double)lambda * (gA + 2.0 * xv * gB + (double)yv * gC)));
     }
 }
 

@@ -6,7 +6,9 @@
  * (.gitmodules:1-3, an empty directory in the snapshot), called once at scene/gaussian_model.py:134:
  *     dist2 = torch.clamp_min(distCUDA2(points), 0.0000001)
  * mean_dist2[i] = mean of the three smallest squared distances from point i to the other points
- * (exact; coincident points count with distance 0; fewer than 4 points give +inf).
+ * (exact; coincident points count with distance 0).  With fewer than 4 points there are fewer than three others: the
+ * result is then the mean over the N - 1 that exist, and 0 for N = 1.  A deliberate departure from summing the "no
+ * neighbour yet" sentinels, which gives +inf: the call site takes log(sqrt(clamp_min(., 1e-7))) and needs a finite number.
  * Same conventions as gsr.h: device pointers, float32, caller-owned buffers, enqueued on `stream`, 0 = ok.
  */
 #ifndef GSR_KNN_H

@@ -32,9 +32,10 @@ def _corr(a, w):
     return out
 
 
-def l1_ssim_loss(img, gt, lam=0.2, with_grad=True):
+def l1_ssim_loss(img, gt, lam=0.2, with_grad=True, w=None):
+    """w: another 11x11 window than window() (float64 array), e.g. the one torch builds -- see tests/test_aux_references.py"""
     x = np.asarray(img, dtype=np.float64); y = np.asarray(gt, dtype=np.float64)
-    w = window()
+    w = window() if w is None else np.asarray(w, dtype=np.float64)
     m1, m2 = _corr(x, w), _corr(y, w)
     s11, s22, s12 = _corr(x * x, w), _corr(y * y, w), _corr(x * y, w)
     a1 = 2 * m1 * m2 + C1; a2 = 2 * (s12 - m1 * m2) + C2
