@@ -73,6 +73,15 @@ SIGNATURES = {
     "gsr_get_stage_times": (_i32, [C.POINTER(C.c_char_p), C.POINTER(_f)]),
 }
 
+# include/gsr_chamfer.h (a table of its own: SIGNATURES is exactly gsr.h + gsr_loss.h + gsr_knn.h + gsr_optim.h)
+CHAMFER_SIGNATURES = {
+    "gsr_chamfer_workspace": (_i32, [_i32, _i32, _i32, C.POINTER(_sz)]),                 # B N M bytes
+    "gsr_chamfer_forward": (_i32, [_p, _i32, _i32, _i32, _i32, _p, _p,                   # stream B N M D x1 x2
+                                   _p, _p, _p, _p, _p, _sz]),                            # dist1 dist2 idx1 idx2 ws ws_bytes
+    "gsr_chamfer_backward": (_i32, [_p, _i32, _i32, _i32, _i32, _p, _p, _p, _p,          # stream B N M D x1 x2 idx1 idx2
+                                    _p, _p, _p, _p]),                                    # g1 g2 dx1 dx2
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -99,7 +108,7 @@ def load() -> C.CDLL:
             lib = C.CDLL(LIB_PATH)
         except OSError as e:
             raise GsrError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES}.items():
             fn = getattr(lib, name)       # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

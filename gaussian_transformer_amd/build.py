@@ -38,6 +38,11 @@ SOURCES = {
     "ssim_loss.hip": [],
     "knn.hip": [],
     "adam.hip": [],
+    # FMA contraction left ON: the (D + 3) ulp bound of a difference-form distance holds with or without it (tests/chamfer_ref.py) and
+    # it halves the inner loop; -munsafe-fp-atomics: the scattered gradient term uses the native float atomic add, as composite_bwd.hip;
+    # -fno-slp-vectorize: packed f32 ops have no higher rate here and cost v_movs (ISA of the D = 26 loop per 4 distances: 104 v_pk_* + 27 v_mov + 49 others
+    # packed, 208 v_sub / v_fmac + 16 others scalar; read from the ISA, not timed)
+    "chamfer.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result",
           "-fgpu-rdc" if False else "-fno-gpu-rdc"]
@@ -65,7 +70,7 @@ def build_variant(tag: str, defines, verbose: bool = False, force: bool = False)
     odir = os.path.join(OBJ, tag)
     os.makedirs(odir, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")] + [os.path.abspath(__file__)]
-    headers += [os.path.join(HERE, "..", "include", h) for h in ("gsr.h", "gsr_loss.h", "gsr_knn.h", "gsr_optim.h")]
+    headers += [os.path.join(HERE, "..", "include", h) for h in ("gsr.h", "gsr_loss.h", "gsr_knn.h", "gsr_optim.h", "gsr_chamfer.h")]
     jobs, objs = [], []
     for src, extra in SOURCES.items():
         s, o = os.path.join(CSRC, src), os.path.join(odir, src.replace(".hip", ".o"))
@@ -97,6 +102,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
     headers.append(os.path.join(HERE, "..", "include", "gsr_loss.h"))
     headers.append(os.path.join(HERE, "..", "include", "gsr_knn.h"))
     headers.append(os.path.join(HERE, "..", "include", "gsr_optim.h"))
+    headers.append(os.path.join(HERE, "..", "include", "gsr_chamfer.h"))
     headers.append(os.path.abspath(__file__))
     cc = hipcc()
     jobs = []

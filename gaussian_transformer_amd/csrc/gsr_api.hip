@@ -11,6 +11,7 @@
 #include <ctime>
 
 #include "../../include/gsr.h"
+#include "../../include/gsr_chamfer.h"
 #include "../../include/gsr_knn.h"
 #include "../../include/gsr_loss.h"
 #include "../../include/gsr_optim.h"
@@ -973,6 +974,43 @@ int32_t gsr_knn_mean_dist2(gsr_stream_t stream, int32_t N, const float *points, 
     HIP_TRY(knn_workspace_bytes(N, &need), "knn temp query");
     if (N > 0 && ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "knn workspace %zu < %zu", ws_bytes, need);
     HIP_TRY(launch_knn(N, points, mean_dist2, ws, (hipStream_t)stream), "knn launch");
+    return GSR_OK;
+}
+
+// ---- chamfer_distance.ChamferDistance equivalent (include/gsr_chamfer.h) ----
+// 0: nothing to do, 1: work, < 0: invalid (message set)
+static int chamfer_sizes(const char *who, int32_t B, int32_t N, int32_t M, int32_t D) {
+    if (B < 0 || N < 0 || M < 0) { fail(GSR_ERR_INVALID_ARGUMENT, "%s: negative size (B=%d N=%d M=%d)", who, B, N, M); return -1; }
+    if (D < 1 || D > 64) { fail(GSR_ERR_INVALID_ARGUMENT, "%s: D=%d not in 1..64", who, D); return -1; }
+    if (B == 0 || (N == 0 && M == 0)) return 0;
+    if (N == 0 || M == 0) { fail(GSR_ERR_INVALID_ARGUMENT, "%s: N=%d, M=%d: an empty set has no nearest neighbour", who, N, M); return -1; }
+    if (((long long)(N > M ? N : M) + 511) / 512 * B > 0x7fffffffLL) { fail(GSR_ERR_INVALID_ARGUMENT, "%s: B * max(N, M) too large", who); return -1; }
+    return 1;
+}
+
+int32_t gsr_chamfer_workspace(int32_t B, int32_t N, int32_t M, size_t *bytes) {
+    if (B < 0 || N < 0 || M < 0 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_chamfer_workspace: bad argument");
+    *bytes = (size_t)8 * (size_t)B * ((size_t)N + (size_t)M);
+    return GSR_OK;
+}
+
+int32_t gsr_chamfer_forward(gsr_stream_t stream, int32_t B, int32_t N, int32_t M, int32_t D, const float *x1, const float *x2,
+                            float *dist1, float *dist2, int32_t *idx1, int32_t *idx2, void *ws, size_t ws_bytes) {
+    const int k = chamfer_sizes("gsr_chamfer_forward", B, N, M, D);
+    if (k <= 0) return k < 0 ? GSR_ERR_INVALID_ARGUMENT : GSR_OK;
+    if (!x1 || !x2 || !dist1 || !dist2 || !idx1 || !idx2 || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_chamfer_forward: null pointer");
+    const size_t need = (size_t)8 * (size_t)B * ((size_t)N + (size_t)M);
+    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "chamfer workspace %zu < %zu", ws_bytes, need);
+    HIP_TRY(launch_chamfer_forward(B, N, M, D, x1, x2, dist1, dist2, idx1, idx2, ws, (hipStream_t)stream), "chamfer forward launch");
+    return GSR_OK;
+}
+
+int32_t gsr_chamfer_backward(gsr_stream_t stream, int32_t B, int32_t N, int32_t M, int32_t D, const float *x1, const float *x2,
+                             const int32_t *idx1, const int32_t *idx2, const float *g1, const float *g2, float *dx1, float *dx2) {
+    const int k = chamfer_sizes("gsr_chamfer_backward", B, N, M, D);
+    if (k <= 0) return k < 0 ? GSR_ERR_INVALID_ARGUMENT : GSR_OK;
+    if (!x1 || !x2 || !idx1 || !idx2) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_chamfer_backward: null pointer");
+    HIP_TRY(launch_chamfer_backward(B, N, M, D, x1, x2, idx1, idx2, g1, g2, dx1, dx2, (hipStream_t)stream), "chamfer backward launch");
     return GSR_OK;
 }
 

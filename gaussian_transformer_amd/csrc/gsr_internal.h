@@ -403,6 +403,12 @@ hipError_t launch_l1_ssim_backward(int C, int H, int W, const float *img, const 
 hipError_t knn_workspace_bytes(int N, size_t *bytes);
 hipError_t launch_knn(int N, const float *pts, float *out, void *ws, hipStream_t s);
 
+// chamfer.hip (include/gsr_chamfer.h); sizes validated by the caller: B, N, M >= 1, 1 <= D <= 64
+hipError_t launch_chamfer_forward(int B, int N, int M, int D, const float *x1, const float *x2, float *dist1, float *dist2,
+                                  int32_t *idx1, int32_t *idx2, void *ws, hipStream_t s);
+hipError_t launch_chamfer_backward(int B, int N, int M, int D, const float *x1, const float *x2, const int32_t *idx1, const int32_t *idx2,
+                                   const float *g1, const float *g2, float *dx1, float *dx2, hipStream_t s);
+
 hipError_t launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present, hipStream_t s);
 
 }  // namespace gsr
