@@ -82,6 +82,17 @@ CHAMFER_SIGNATURES = {
                                     _p, _p, _p, _p]),                                    # g1 g2 dx1 dx2
 }
 
+# include/gsr_sequence.h (likewise a table of its own)
+SEQUENCE_SIGNATURES = {
+    "gsr_box_sort_workspace": (_i32, [_i32, _i32, C.POINTER(_sz)]),                      # P n bytes
+    "gsr_box_sort": (_i32, [_p, _i32, _i32, _p, _i32, _i32,                              # stream P D rows xyz_col n
+                            _p, _p, _p, _p, _sz]),                                       # out_rows out_perm out_count ws ws_bytes
+    "gsr_visible_union": (_i32, [_p, _i32, _i32, _p, _p, _f, _p, _p, _i32,               # stream P B means3D scales mod rotations cov3D raw_params
+                                 _p, _p,                                                 # viewmatrices projmatrices (device)
+                                 C.POINTER(_f), C.POINTER(_f), C.POINTER(_i32), C.POINTER(_i32),   # tanfovx tanfovy widths heights (host)
+                                 _p, _p, _p]),                                           # radii_out visible_out counts_out
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -108,7 +119,7 @@ def load() -> C.CDLL:
             lib = C.CDLL(LIB_PATH)
         except OSError as e:
             raise GsrError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES, **SEQUENCE_SIGNATURES}.items():
             fn = getattr(lib, name)       # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

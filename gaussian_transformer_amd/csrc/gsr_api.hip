@@ -15,6 +15,7 @@
 #include "../../include/gsr_knn.h"
 #include "../../include/gsr_loss.h"
 #include "../../include/gsr_optim.h"
+#include "../../include/gsr_sequence.h"
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -1011,6 +1012,70 @@ int32_t gsr_chamfer_backward(gsr_stream_t stream, int32_t B, int32_t N, int32_t 
     if (k <= 0) return k < 0 ? GSR_ERR_INVALID_ARGUMENT : GSR_OK;
     if (!x1 || !x2 || !idx1 || !idx2) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_chamfer_backward: null pointer");
     HIP_TRY(launch_chamfer_backward(B, N, M, D, x1, x2, idx1, idx2, g1, g2, dx1, dx2, (hipStream_t)stream), "chamfer backward launch");
+    return GSR_OK;
+}
+
+// ---- sequence preparation: box sort and multi-camera visibility (include/gsr_sequence.h) ----
+static int box_sizes(const char *who, int32_t P, int32_t n) {
+    if (P < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: P=%d is negative", who, P);
+    if (n < 1 || n > GSR_BOX_MAX_N) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: n=%d not in 1..%d", who, n, GSR_BOX_MAX_N);
+    return GSR_OK;
+}
+
+int32_t gsr_box_sort_workspace(int32_t P, int32_t n, size_t *bytes) {
+    if (!bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort_workspace: bytes is NULL");
+    if (box_sizes("gsr_box_sort_workspace", P, n) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
+    HIP_TRY(box_sort_workspace_bytes(P, n, bytes), "box sort workspace size");
+    return GSR_OK;
+}
+
+int32_t gsr_box_sort(gsr_stream_t stream, int32_t P, int32_t D, const float *rows, int32_t xyz_col, int32_t n, float *out_rows,
+                     int32_t *out_perm, int32_t *out_count, void *ws, size_t ws_bytes) {
+    if (box_sizes("gsr_box_sort", P, n) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
+    if (D < 3 || D > GSR_BOX_MAX_D) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: D=%d not in 3..%d", D, GSR_BOX_MAX_D);
+    if (xyz_col < 0 || xyz_col > D - 3) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: xyz_col=%d not in 0..D-3=%d", xyz_col, D - 3);
+    if ((long long)P * D > 0x7fffffffLL) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: P * D = %lld too large", (long long)P * D);
+    if (!out_count) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: out_count is NULL");
+    if (P == 0) {
+        HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(int32_t), (hipStream_t)stream), "box sort: clear count");
+        return GSR_OK;
+    }
+    if (!rows || !out_rows || !out_perm || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: null pointer");
+    if (rows == out_rows) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: rows and out_rows must not overlap (same pointer)");
+    if (rows < out_rows + (size_t)P * D && out_rows < rows + (size_t)P * D)
+        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: rows and out_rows must not overlap (the ranges of P * D floats intersect)");
+    size_t need = 0;
+    HIP_TRY(box_sort_workspace_bytes(P, n, &need), "box sort workspace size");
+    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "box sort workspace %zu < %zu", ws_bytes, need);
+    HIP_TRY(launch_box_sort(P, D, rows, xyz_col, n, out_rows, out_perm, out_count, ws, (hipStream_t)stream), "box sort launch");
+    return GSR_OK;
+}
+
+int32_t gsr_visible_union(gsr_stream_t stream, int32_t P, int32_t B, const float *means3D, const float *scales, float scale_modifier,
+                          const float *rotations, const float *cov3D_precomp, int32_t raw_params, const float *viewmatrices,
+                          const float *projmatrices, const float *tanfovx, const float *tanfovy, const int32_t *widths,
+                          const int32_t *heights, int32_t *radii_out, uint8_t *visible_out, int32_t *counts_out) {
+    if (P < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: P=%d is negative", P);
+    if (B < 1 || B > GSR_VISIBLE_MAX_B) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: B=%d not in 1..%d", B, GSR_VISIBLE_MAX_B);
+    if (!tanfovx || !tanfovy || !widths || !heights) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: tanfovx/tanfovy/widths/heights (host) required");
+    VisibleArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int b = 0; b < B; b++) {
+        if (widths[b] <= 0 || heights[b] <= 0 || widths[b] > 65535 * GSR_TILE_HOST || heights[b] > 65535 * GSR_TILE_HOST)
+            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: camera %d: image size %d x %d", b, widths[b], heights[b]);
+        a.tanfovx[b] = tanfovx[b]; a.tanfovy[b] = tanfovy[b]; a.W[b] = widths[b]; a.H[b] = heights[b];
+    }
+    if (counts_out) HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)B * sizeof(int32_t), (hipStream_t)stream), "visible union: clear counts");
+    if (P == 0) return GSR_OK;
+    if (!means3D || !viewmatrices || !projmatrices) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: missing means3D or matrices");
+    if ((cov3D_precomp != nullptr) == (scales != nullptr || rotations != nullptr) || (!cov3D_precomp && (!scales || !rotations)))
+        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: exactly one of (scales, rotations) / cov3D_precomp must be given");
+    if (raw_params && cov3D_precomp) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: raw_params needs scales/rotations, not cov3D_precomp");
+    a.P = P; a.B = B; a.raw_params = raw_params ? 1 : 0; a.scale_modifier = scale_modifier;
+    a.means3D = means3D; a.scales = scales; a.rotations = rotations; a.cov3D_precomp = cov3D_precomp;
+    a.viewmatrices = viewmatrices; a.projmatrices = projmatrices;
+    a.radii_out = radii_out; a.visible_out = visible_out; a.counts_out = counts_out;
+    HIP_TRY(launch_visible_union(a, (hipStream_t)stream), "visible union launch");
     return GSR_OK;
 }
 

@@ -411,4 +411,22 @@ hipError_t launch_chamfer_backward(int B, int N, int M, int D, const float *x1, 
 
 hipError_t launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present, hipStream_t s);
 
+// sequence.hip (include/gsr_sequence.h); sizes validated by the caller, P >= 1
+#define GSR_SEQ_MAX_N 128   // == GSR_BOX_MAX_N
+#define GSR_SEQ_MAX_B 64    // == GSR_VISIBLE_MAX_B
+struct VisibleArgs {
+    int P, B, raw_params;
+    float scale_modifier;
+    const float *means3D, *scales, *rotations, *cov3D_precomp, *viewmatrices, *projmatrices;
+    int32_t *radii_out;
+    uint8_t *visible_out;
+    int32_t *counts_out;
+    float tanfovx[GSR_SEQ_MAX_B], tanfovy[GSR_SEQ_MAX_B];
+    int W[GSR_SEQ_MAX_B], H[GSR_SEQ_MAX_B];
+};
+hipError_t box_sort_workspace_bytes(int P, int n, size_t *bytes);
+hipError_t launch_box_sort(int P, int D, const float *rows, int xyz_col, int n, float *out_rows, int32_t *out_perm, int32_t *out_count,
+                           void *ws, hipStream_t s);
+hipError_t launch_visible_union(const VisibleArgs &a, hipStream_t s);
+
 }  // namespace gsr

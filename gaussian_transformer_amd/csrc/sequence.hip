@@ -1,0 +1,199 @@
+// sequence.hip -- sequence preparation of the Gaussian transformer (include/gsr_sequence.h):
+//   box sort : key kernel (box of every row, decided against the boundary table in LDS) -> stable rocPRIM radix sort of
+//              (box, index) over just the bits the boxes need -> gather kernel (rows, permutation, count, zero tail).
+//              Dropped rows carry the key n^3, so the stable sort leaves them behind every box: no compaction step, no atomic.
+//   visible_union : one lane per Gaussian, 3-D covariance built once, then the geometry stages S1-S5 of preprocess.hip per camera.
+// Compiled with -ffp-contract=off -fno-slp-vectorize like preprocess.hip: the radii round exactly as gsr_forward's.
+#include <cstring>  // ROCm 7.2 rocprim/texture_cache_iterator.hpp uses memset without including it
+#include <hip/hip_runtime.h>
+#include <rocprim/rocprim.hpp>
+
+#include "gsr_device.h"
+#include "gsr_internal.h"
+
+namespace gsr {
+
+// ---------------------------------------------------------------- box sort ----------------------------------------------------------------
+
+struct BoxKeyArgs {
+    int P, D, xyz_col, n;
+    const float *rows;
+    uint32_t *keys;
+    float b[GSR_SEQ_MAX_N + 1];     // (float)((1.0 / n) * k), computed by the host in double
+};
+
+// axis cell of c among the n cells [b_a, b_{a+1}), -1 if none (c < b_0, c >= b_n, NaN).  The guess from c * n is off by at most a
+// cell near a boundary; the comparisons against the table decide.
+__device__ __forceinline__ int box_cell(float c, int n, const float *__restrict__ b) {
+    if (!(c >= b[0] && c < b[n])) return -1;
+    int g = (int)(c * (float)n);
+    g = g < 0 ? 0 : (g > n - 1 ? n - 1 : g);
+    while (g > 0 && c < b[g]) g--;
+    while (g < n - 1 && c >= b[g + 1]) g++;
+    return g;
+}
+
+__global__ __launch_bounds__(256) void box_key_kernel(BoxKeyArgs a) {
+    __shared__ float s_b[GSR_SEQ_MAX_N + 1];
+    for (int k = threadIdx.x; k <= a.n; k += 256) s_b[k] = a.b[k];
+    __syncthreads();
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.P) return;
+    const float *r = a.rows + (size_t)i * a.D + a.xyz_col;
+    const int cx = box_cell(r[0], a.n, s_b), cy = box_cell(r[1], a.n, s_b), cz = box_cell(r[2], a.n, s_b);
+    const uint32_t n = (uint32_t)a.n;
+    a.keys[i] = (cx < 0 || cy < 0 || cz < 0) ? n * n * n : (uint32_t)cx + n * ((uint32_t)cy + n * (uint32_t)cz);
+}
+
+// one thread per output float: consecutive lanes read consecutive floats of a source row and write consecutive floats of the output.
+// P * D < 2^31 (checked by the caller), so the index arithmetic is 32-bit.
+__global__ __launch_bounds__(256) void box_gather_kernel(int P, int D, uint32_t nbox, const float *__restrict__ rows,
+                                                         const uint32_t *__restrict__ skeys, const uint32_t *__restrict__ sidx,
+                                                         float *__restrict__ out_rows, int32_t *__restrict__ out_perm,
+                                                         int32_t *__restrict__ out_count) {
+    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+    if (e >= (uint32_t)P * (uint32_t)D) return;
+    const uint32_t j = e / (uint32_t)D, c = e - j * (uint32_t)D;
+    const bool kept = skeys[j] < nbox;
+    const uint32_t src = sidx[j];
+    out_rows[e] = kept ? rows[src * (uint32_t)D + c] : 0.f;
+    if (c == 0) {
+        out_perm[j] = kept ? (int32_t)src : -1;
+        // the kept rows are a prefix: exactly one j sees its end
+        if (kept && (j + 1 == (uint32_t)P || !(skeys[j + 1] < nbox))) *out_count = (int32_t)(j + 1);
+        if (!kept && j == 0) *out_count = 0;
+    }
+}
+
+struct BoxWs { uint32_t *keys, *skeys, *sidx; void *temp; size_t temp_bytes, total; };
+
+static int box_bits(int n) { return ceil_log2_u32((uint32_t)n * n * n + 1u); }      // keys 0 .. n^3 inclusive
+
+static hipError_t carve_box_ws(void *base, int P, int n, BoxWs &w) {
+    const size_t np = (size_t)(P > 0 ? P : 1);
+    size_t tb = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                             rocprim::counting_iterator<uint32_t>(0), (uint32_t *)nullptr, np, 0u,
+                                             (unsigned)box_bits(n), (hipStream_t)0, false);
+    if (e != hipSuccess) return e;
+    char *p = (char *)base;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += align_up(bytes); return r; };
+    w.keys = (uint32_t *)take(np * 4);
+    w.skeys = (uint32_t *)take(np * 4);
+    w.sidx = (uint32_t *)take(np * 4);
+    w.temp = take(tb > 0 ? tb : 1);
+    w.temp_bytes = tb;
+    w.total = off;
+    return hipSuccess;
+}
+
+hipError_t box_sort_workspace_bytes(int P, int n, size_t *bytes) {
+    BoxWs w;
+    hipError_t e = carve_box_ws(nullptr, P, n, w);
+    if (e == hipSuccess) *bytes = w.total;
+    return e;
+}
+
+// sizes validated by the caller; P >= 1
+hipError_t launch_box_sort(int P, int D, const float *rows, int xyz_col, int n, float *out_rows, int32_t *out_perm, int32_t *out_count,
+                           void *ws, hipStream_t s) {
+    BoxWs w;
+    hipError_t e = carve_box_ws(ws, P, n, w);
+    if (e != hipSuccess) return e;
+    BoxKeyArgs ka;
+    ka.P = P; ka.D = D; ka.xyz_col = xyz_col; ka.n = n; ka.rows = rows; ka.keys = w.keys;
+    const double interval = 1.0 / (double)n;
+    for (int k = 0; k <= GSR_SEQ_MAX_N; k++) ka.b[k] = k <= n ? (float)(interval * (double)k) : 0.f;
+    hipLaunchKernelGGL(box_key_kernel, dim3((P + 255) / 256), dim3(256), 0, s, ka);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    size_t tb = w.temp_bytes;
+    e = rocprim::radix_sort_pairs(w.temp, tb, (const uint32_t *)w.keys, w.skeys, rocprim::counting_iterator<uint32_t>(0), w.sidx,
+                                  (size_t)P, 0u, (unsigned)box_bits(n), s, false);
+    if (e != hipSuccess) return e;
+    const uint32_t total = (uint32_t)P * (uint32_t)D;
+    hipLaunchKernelGGL(box_gather_kernel, dim3((total + 255u) / 256u), dim3(256), 0, s, P, D, (uint32_t)n * n * n, rows,
+                       (const uint32_t *)w.skeys, (const uint32_t *)w.sidx, out_rows, out_perm, out_count);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- visibility ----------------------------------------------------------------
+
+// 256 threads, one Gaussian per lane; the cameras' matrices sit in LDS (8 KB at B = 64), their scalars in the kernel arguments.
+// Per camera the sequence of operations is that of preprocess_fwd_kernel up to `area != 0`, on the same helpers.
+template <bool RAW>
+__global__ __launch_bounds__(256) void visible_union_kernel(VisibleArgs a) {
+    __shared__ float s_vm[GSR_SEQ_MAX_B * 16], s_pm[GSR_SEQ_MAX_B * 16];
+    for (int k = threadIdx.x; k < a.B * 16; k += 256) { s_vm[k] = a.viewmatrices[k]; s_pm[k] = a.projmatrices[k]; }
+    __syncthreads();
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < a.P;
+    const size_t si = (size_t)(live ? i : a.P - 1);       // lanes past the end recompute Gaussian P-1 and store nothing
+    const float p[3] = {a.means3D[3 * si], a.means3D[3 * si + 1], a.means3D[3 * si + 2]};
+    float c6[6];
+    if (a.cov3D_precomp) {                                // uniform
+#pragma unroll
+        for (int k = 0; k < 6; k++) c6[k] = a.cov3D_precomp[6 * si + k];
+    } else {                                              // S2, once for all cameras
+        float s[3] = {a.scales[3 * si], a.scales[3 * si + 1], a.scales[3 * si + 2]};
+        const float4 q4 = reinterpret_cast<const float4 *>(a.rotations)[si];
+        float q[4] = {q4.x, q4.y, q4.z, q4.w};
+        if (RAW) {
+            s[0] = expf(s[0]); s[1] = expf(s[1]); s[2] = expf(s[2]);
+            float inv_norm;
+            act_normalize4(q, inv_norm);
+        }
+        cov3d_from_scale_rot(s, a.scale_modifier, q, c6);
+    }
+    bool any = false;
+    for (int b = 0; b < a.B; b++) {
+        float vm[16], pm[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) { vm[k] = s_vm[b * 16 + k]; pm[k] = s_pm[b * 16 + k]; }
+        const int W = a.W[b], H = a.H[b];
+        const int gridx = (W + GSR_TILE - 1) / GSR_TILE, gridy = (H + GSR_TILE - 1) / GSR_TILE;
+        int radius_out = 0;
+        float pv[3];
+        xform4x3(vm, p, pv);
+        if (pv[2] > GSR_NEAR_Z) {                                                       // S1
+            float ph[4];
+            xform4x4(pm, p, ph);
+            const float pw = 1.f / (ph[3] + GSR_W_EPS);
+            const float ndcx = ph[0] * pw, ndcy = ph[1] * pw;
+            Ewa e;
+            ewa_project(pv, c6, vm, a.tanfovx[b], a.tanfovy[b], W, H, e);               // S3
+            const float det = e.a * e.c - e.b * e.b;                                    // S4
+            if (det != 0.f) {
+                const float mid = 0.5f * (e.a + e.c);
+                float disc = mid * mid - det;
+                if (disc < GSR_LAMBDA_FLOOR) disc = GSR_LAMBDA_FLOOR;
+                const float l1 = mid + sqrtf(disc), l2 = mid - sqrtf(disc);
+                const float lmax = l1 > l2 ? l1 : l2;
+                const int radius = (int)ceilf(GSR_SIGMA_EXTENT * sqrtf(lmax));
+                const float px = ((ndcx + 1.f) * (float)W - 1.f) * 0.5f;                // S5
+                const float py = ((ndcy + 1.f) * (float)H - 1.f) * 0.5f;
+                int x0, y0, x1, y1;
+                tile_rect(px, py, radius, gridx, gridy, x0, y0, x1, y1);
+                if ((x1 - x0) * (y1 - y0) != 0) radius_out = radius;
+            }
+        }
+        const bool vis = live && radius_out > 0;
+        any |= vis;
+        if (a.radii_out && live) a.radii_out[(size_t)b * a.P + si] = radius_out;
+        if (a.counts_out) {                               // one integer atomic per wave and camera
+            const unsigned long long m = __ballot(vis);
+            if ((threadIdx.x & 63) == 0 && m) atomicAdd(&a.counts_out[b], (int)__popcll(m));
+        }
+    }
+    if (a.visible_out && live) a.visible_out[si] = any ? 1 : 0;
+}
+
+// sizes validated by the caller; P >= 1; counts_out zeroed by the caller on the same stream
+hipError_t launch_visible_union(const VisibleArgs &a, hipStream_t s) {
+    const dim3 grid((a.P + 255) / 256), block(256);
+    if (a.raw_params) hipLaunchKernelGGL((visible_union_kernel<true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((visible_union_kernel<false>), grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace gsr
