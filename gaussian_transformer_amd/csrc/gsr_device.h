@@ -346,7 +346,14 @@ __device__ __forceinline__ void load_sh_row_split(const float *__restrict__ dc, 
 }
 
 // activations of scene/gaussian_model.py:33-41 for the fused (raw parameter) path
-__device__ __forceinline__ float act_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+// 1 / (1 + expf(-x)) rounds 1 + e to the grid of 1.0 before dividing: for x > 0 the result is up to two float32 steps off, and the
+// backward chain o (1 - o) magnifies that by 1 / (1 - o) (1e-4 of the logit's gradient at x = 7.5, more beyond).  t = e / (1 + e) with
+// e = exp(-|x|) <= 1 is accurate relative to itself, and 1 - t is rounded once: o is the correctly rounded sigmoid but for rare ties.
+__device__ __forceinline__ float act_sigmoid(float x) {
+    const float e = expf(-fabsf(x));
+    const float t = e / (1.f + e);
+    return x >= 0.f ? 1.f - t : t;
+}
 __device__ __forceinline__ void act_normalize4(float q[4], float &inv_norm) {     // F.normalize: x / max(|x|, 1e-12)
     const float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     inv_norm = 1.f / fmaxf(n, 1e-12f);

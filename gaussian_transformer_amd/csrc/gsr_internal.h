@@ -383,6 +383,7 @@ struct PergaussBwdArgs {
     float *dL_dmeans2D, *dL_dopacity, *dL_dcolors, *dL_dmeans3D, *dL_dcov3D, *dL_dsh, *dL_dscales, *dL_drots;
 };
 hipError_t launch_pergauss_bwd(const PergaussBwdArgs &a, hipStream_t s);
+int pergauss_last_path();      // bit 0: dense kernel, bit 1: LDS tile for dL/dshs -- of the last launch_pergauss_bwd
 hipError_t launch_fill_zero(const PergaussBwdArgs &a, hipStream_t s);      // zeros into every gradient output of `a`
 hipError_t launch_gather_visible(const PergaussBwdArgs &a, hipStream_t s);  // vis_count / vis_list / vis_rec of `a` (vis_count zeroed by the caller)
 bool pergauss_dense_eligible(const PergaussBwdArgs &a);

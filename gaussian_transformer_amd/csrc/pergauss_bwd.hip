@@ -475,6 +475,11 @@ hipError_t launch_fill_zero(const PergaussBwdArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// which variant the process's last launch_pergauss_bwd took (read-only option "pergauss_path"): bit 0 the dense kernel, bit 1 the
+// LDS tile for the dL/dshs rows.  Both depend on the caller's pointers (16-byte alignment), so a test has to be able to see them.
+static std::atomic<int> g_last_path{0};
+int pergauss_last_path() { return g_last_path.load(); }
+
 hipError_t launch_pergauss_bwd(const PergaussBwdArgs &a_in, hipStream_t s) {
     if (a_in.P <= 0) return hipSuccess;
     PergaussBwdArgs a = a_in;
@@ -482,6 +487,7 @@ hipError_t launch_pergauss_bwd(const PergaussBwdArgs &a_in, hipStream_t s) {
     const int d = a.shs ? a.D : 0;
     const bool raw = a.raw_params != 0, split = a.shs_rest != nullptr;
     a.sh_tile = (a.shs && !split && a.M == 16 && (reinterpret_cast<uintptr_t>(a.dL_dsh) & 15) == 0) ? 1 : 0;
+    g_last_path.store((a.dense ? 1 : 0) | (a.sh_tile ? 2 : 0));
     const size_t lds = a.sh_tile ? (size_t)4 * 64 * SH_TILE_ROW * sizeof(float4) : 0;      // 52 KiB per workgroup: 3 workgroups per CU
     if (lds > 48 * 1024) {
         static std::atomic<uint64_t> attr_set{0};            // one bit per device (per-device attribute, idempotent)

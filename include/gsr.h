@@ -240,6 +240,9 @@ int32_t gsr_debug_read_wave_trace(int32_t which, uint32_t *out /*[4 * max_units]
  *        kernel then runs on those only.  Applies to shs with M = 16 and scales + rotations (other layouts: the streaming kernel).
  *        The caller's stream sees one event record and one event wait; the join is enqueued before gsr_backward returns.  Same
  *        gradients (bit for bit under "deterministic_bwd").  Speed only.
+ *   "pergauss_path" (read-only, gsr_get_option): which per-Gaussian backward variant the process's last gsr_backward launched --
+ *        bit 0: the dense kernel, bit 1: the LDS tile for the dL/dshs rows.  Both need 16-byte aligned dL_dsh (and, dense, shs and
+ *        rotations): a caller that carves its outputs from one buffer can check that it got the variant it meant.
  *   "prefill_at" (0, 1, 2; default 1): where a gsr_forward zero-fills gradient outputs announced through gsr_backward_prefill --
  *   1 beside its compositing kernel, 2 beside the list-ordering kernel already, 0 announcements are ignored.
  *   "dense_fork" (0, 1, 2; default 2): where that fork happens -- 1 after the accumulator rows are cleared, 0 before, 2 = after below

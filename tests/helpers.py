@@ -269,33 +269,39 @@ def parity_report(S, dL, hip=None, nthreads=0):
     r32, r64 = ref.get("f32"), ref.get("f64")
     nt = nthreads or r32.max_threads()
     f32 = r32.forward(S, nthreads=nt); g32 = r32.backward(f32, dL, nthreads=nt)
-    margin = f32["state"].decision_margin()
     f64 = r64.forward(S, nthreads=nt); g64 = r64.backward(f64, dL, nthreads=nt)
     h = hip if hip is not None else hip_forward_backward(S, dL)
-    # where the max-norm difference against the float32 oracle sits, and how far HIP and the float32 oracle each are from float64 THERE:
-    # a large max-norm figure at an element where the float32 oracle itself is as far from float64 is the oracle's rounding, not the kernels'
-    worst = {}
+    H, G32, G64 = {}, {}, {}
     for hk, rk in GRAD_KEYS:
         if h["grads"].get(hk) is None or g32.get(rk) is None:
             continue
-        a = np.asarray(h["grads"][hk], np.float64); b = np.asarray(g32[rk], np.float64).reshape(a.shape); c = np.asarray(g64[rk], np.float64).reshape(a.shape)
+        H[hk] = np.asarray(h["grads"][hk], np.float64)
+        G32[hk] = np.asarray(g32[rk], np.float64).reshape(H[hk].shape); G64[hk] = np.asarray(g64[rk], np.float64).reshape(H[hk].shape)
+    return build_report(S, f32, f64, h["color"], H, G32, G64, radii_equal=bool(np.array_equal(h["radii"], f32["radii"])))
+
+
+def build_report(S, f32, f64, hip_color, H, G32, G64, **radii):
+    """The report assert_parity() reads, from the two oracle forward results, the HIP image and three dicts of gradients with the
+    same keys and shapes (HIP, float32 oracle, float64 oracle -- in whatever parameter space the caller compares in).
+    radii: `radii_equal` and whatever else the caller records about the radii."""
+    # where the max-norm difference against the float32 oracle sits, and how far HIP and the float32 oracle each are from float64 THERE:
+    # a large max-norm figure at an element where the float32 oracle itself is as far from float64 is the oracle's rounding, not the kernels'
+    worst = {}
+    for k, a in H.items():
+        b, c = G32[k], G64[k]
         if a.size == 0:
             continue
         i = int(np.abs(a - b).argmax()); scale = max(float(np.abs(b).max()), 1e-30)
-        worst[hk] = dict(flat_index=i, gaussian=int(i // max(1, a.size // a.shape[0])), hip=float(a.flat[i]), f32=float(b.flat[i]), f64=float(c.flat[i]),
-                         hip_vs_f64=float(abs(a.flat[i] - c.flat[i]) / scale), f32_vs_f64=float(abs(b.flat[i] - c.flat[i]) / scale),
-                         hip_vs_f32=float(abs(a.flat[i] - b.flat[i]) / scale))
-    rep = dict(P=int(np.asarray(S.means3D).shape[0]), W=S.W, H=S.H, num_rendered_reference_rule=int(f32["num_rendered"]),
-               image_constructive=certify_image_constructive(h["color"], f32), grads_maxnorm_where=worst,
-               radii_equal=bool(np.array_equal(h["radii"], f32["radii"])),
-               radii_f32_vs_f64_differ=int((f32["radii"] != f64["radii"]).sum()),
-               image=certify_image(h["color"], f32["color"], margin),
-               image_vs_f64=certify_image(h["color"], f64["color"], f64["state"].decision_margin()),
-               grads=grad_report(h["grads"], g64), grads_f32_oracle=grad_report(_as_hip_keys(g32), g64),
-               grads_vs_f32=grad_report(h["grads"], g32),
-               grads_maxnorm_vs_f32={hk: grad_err(h["grads"][hk], np.asarray(g32[rk]).reshape(np.asarray(h["grads"][hk]).shape))
-                                     for hk, rk in GRAD_KEYS if h["grads"].get(hk) is not None and g32.get(rk) is not None})
-    return rep
+        worst[k] = dict(flat_index=i, gaussian=int(i // max(1, a.size // a.shape[0])), hip=float(a.flat[i]), f32=float(b.flat[i]), f64=float(c.flat[i]),
+                        hip_vs_f64=float(abs(a.flat[i] - c.flat[i]) / scale), f32_vs_f64=float(abs(b.flat[i] - c.flat[i]) / scale),
+                        hip_vs_f32=float(abs(a.flat[i] - b.flat[i]) / scale))
+    return dict(P=int(np.asarray(S.means3D).shape[0]), W=S.W, H=S.H, num_rendered_reference_rule=int(f32["num_rendered"]),
+                image_constructive=certify_image_constructive(hip_color, f32), grads_maxnorm_where=worst,
+                radii_f32_vs_f64_differ=int((f32["radii"] != f64["radii"]).sum()),
+                image=certify_image(hip_color, f32["color"], f32["state"].decision_margin()),
+                image_vs_f64=certify_image(hip_color, f64["color"], f64["state"].decision_margin()),
+                grads={k: grad_rows(H[k], G64[k]) for k in H}, grads_f32_oracle={k: grad_rows(G32[k], G64[k]) for k in H},
+                grads_vs_f32={k: grad_rows(H[k], G32[k]) for k in H}, grads_maxnorm_vs_f32={k: grad_err(H[k], G32[k]) for k in H}, **radii)
 
 
 # gates on the HIP kernels against the float32 oracle directly (what they were observed to deliver in round 2: fail fraction <= 1.1e-3,
