@@ -9,6 +9,7 @@ upstream package; the native layer underneath is libgsr_hip.so th
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from typing import NamedTuple, Optional
 
 import torch
@@ -58,6 +59,25 @@ class HipBackend:
         self._ws_cache = {}
         self._announced = {}         # device index -> (geom pointer, P, M, gradient tensors) of a forward(announce_backward=True)
         self._bin_hint = {}          # (P, W, H) -> bytes of binning workspace the last forward pass of that shape asked for
+        self._arena_claims = {}      # geom pointer -> (weak reference to geom, first byte, end byte) of the gradient arena a render in flight owns
+
+    def _claim_arena(self, arena, geom):
+        """A gradient arena entered around a forward call belongs to that render until its backward call: a second render in flight
+        whose forward call is given the same memory would have its gradient views alias the first one's (the later backward call
+        overwrites the earlier one's gradients, and autograd then adds a tensor to itself): refused, not summed wrongly."""
+        lo, hi = arena.data_ptr(), arena.data_ptr() + 4 * arena.numel()
+        for key, (ref_, a, b) in list(self._arena_claims.items()):
+            if ref_() is None:                   # that render's graph is gone: it never ran backward, and never will
+                del self._arena_claims[key]
+            elif a < hi and lo < b:
+                raise _lib.GsrError("gradient arena is still owned by another render in flight (its forward call was given the same "
+                                    "memory and its backward call has not run): one arena per render between forward and backward -- "
+                                    "render the other cameras into a scratch arena and add")
+        self._arena_claims[geom.data_ptr()] = (weakref.ref(geom), lo, hi)
+
+    def _release_arena(self, geom):
+        """The arena claimed for the render that owns `geom` is the caller's again: its backward call has run, or its forward call failed."""
+        self._arena_claims.pop(geom.data_ptr(), None)
 
     def _sizes(self, P, W, H):
         key = (P, W, H)
@@ -102,7 +122,9 @@ class HipBackend:
         """announce_backward: a backward() call for this render will follow.  Its gradient tensors are created now and announced
         to the library (gsr_backward_prefill), which writes their zeros beside this forward pass where that pays; backward() picks
         them up.  With a gradient arena they are its slices if the arena is set around this call as well as around backward() (the
-        same one: anything else makes backward() carve and fill as before).  Not in the fused form."""
+        same one: anything else makes backward() carve and fill as before).  The fused form (shs_rest given) announces nothing --
+        its backward() carves and fills by itself -- but a gradient arena set around the call is claimed for it all the same
+        (_claim_arena), so that no second render in flight is given the same memory."""
         dev = means3D.device
         if dev.type != "cuda":
             raise _lib.GsrError(f"the HIP rasterizer needs tensors on a HIP device, got {dev} (no CPU fallback)")
@@ -142,25 +164,35 @@ class HipBackend:
             n = C.c_int64(0)
             bg = _f32c(rs.bg, "bg", dev); vm = _f32c(rs.viewmatrix, "viewmatrix", dev)
             pm = _f32c(rs.projmatrix, "projmatrix", dev); cp = _f32c(rs.campos, "campos", dev)
-            stale = self._announced.pop(dev.index, None)      # kept allocated until gsr_forward has ordered its fill (include/gsr.h)
             grads = None
             arena = _grad_arena            # set around the forward call too: the announced tensors are its slices (and get zeroed now)
             if arena is not None and (arena.device != dev or arena.dtype != torch.float32 or not arena.is_contiguous()
                                       or arena.numel() < arena_floats(P, M, scales.numel() > 0)):
                 announce_backward = False  # backward() raises the error
-            if announce_backward and shs_rest is None and P > 0:
-                grads = self._gradient_outputs(dev, P, M, 0, scales.numel() > 0, colors_precomp.numel() > 0, cov3D_precomp.numel() > 0, arena)
-                g_means3D, g_means2D, g_sh, g_colors, g_opacity, g_scales, g_rots, g_cov3D, _ = grads
-                _lib.check(self.lib.gsr_backward_prefill(P, M, _ptr(g_means2D), _ptr(g_opacity), _ptr(g_colors), _ptr(g_means3D), _ptr(g_cov3D),
-                                                         _ptr(g_sh), _ptr(g_scales), _ptr(g_rots), None), "gsr_backward_prefill")
-            rc = self.lib.gsr_forward(
-                stream, P, int(rs.sh_degree), M, W, H, _ptr(bg), _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
-                _ptr(opacities), _ptr(scales), float(rs.scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                _ptr(vm), _ptr(pm), _ptr(cp), float(rs.tanfovx), float(rs.tanfovy), int(bool(rs.prefiltered)),
-                int(bool(rs.debug)), color.data_ptr(), _ptr(radii), geom.data_ptr(), gb, cb, None, img.data_ptr(), ib,
-                C.byref(n), _ptr(shs_rest), int(bool(raw_params)))
+            claimed = arena is not None and announce_backward and P > 0
+            if claimed:
+                self._claim_arena(arena, geom)          # may refuse: before anything announced earlier is let go
+            stale = self._announced.pop(dev.index, None)      # kept allocated until gsr_forward has ordered its fill (include/gsr.h)
+            try:
+                if announce_backward and shs_rest is None and P > 0:
+                    grads = self._gradient_outputs(dev, P, M, 0, scales.numel() > 0, colors_precomp.numel() > 0, cov3D_precomp.numel() > 0, arena)
+                    g_means3D, g_means2D, g_sh, g_colors, g_opacity, g_scales, g_rots, g_cov3D, _ = grads
+                    _lib.check(self.lib.gsr_backward_prefill(P, M, _ptr(g_means2D), _ptr(g_opacity), _ptr(g_colors), _ptr(g_means3D), _ptr(g_cov3D),
+                                                             _ptr(g_sh), _ptr(g_scales), _ptr(g_rots), None), "gsr_backward_prefill")
+                rc = self.lib.gsr_forward(
+                    stream, P, int(rs.sh_degree), M, W, H, _ptr(bg), _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
+                    _ptr(opacities), _ptr(scales), float(rs.scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
+                    _ptr(vm), _ptr(pm), _ptr(cp), float(rs.tanfovx), float(rs.tanfovy), int(bool(rs.prefiltered)),
+                    int(bool(rs.debug)), color.data_ptr(), _ptr(radii), geom.data_ptr(), gb, cb, None, img.data_ptr(), ib,
+                    C.byref(n), _ptr(shs_rest), int(bool(raw_params)))
+            except BaseException:
+                if claimed:
+                    self._release_arena(geom)           # no render came of it: nothing waits for a backward call
+                raise
             if rc != 0 and grads is not None:
                 self.lib.gsr_backward_prefill(0, 0, None, None, None, None, None, None, None, None, None)
+            if rc != 0 and claimed:
+                self._release_arena(geom)
             del stale
             _lib.check(rc, "gsr_forward")
             if grads is not None:
@@ -191,6 +223,7 @@ class HipBackend:
                                       or arena.numel() < arena_floats(P, M + Mrest, has_sr)):
                 raise _lib.GsrError("gradient arena must be a contiguous float32 tensor on the render device with "
                                     f"at least {arena_floats(P, M + Mrest, has_sr)} elements")
+            self._release_arena(geom)      # the arena claimed at forward time is the caller's again after this call
             ann = self._announced.pop(dev.index, None)
             if ann is not None and ann[:3] == (geom.data_ptr(), P, M) and Mrest == 0 and \
                     ann[4] == (None if arena is None else (arena.data_ptr(), arena.numel())):
@@ -248,7 +281,6 @@ def _remember_forward(geom, P):
     """composited_mask() without arguments refers to the most recent forward pass; a weak reference, so that the workspace (hundreds
     of MB at 5 M Gaussians) is released with its autograd graph instead of living on until the next render."""
     global _last_forward
-    import weakref
     _last_forward = (weakref.ref(geom), P)
 
 
@@ -257,7 +289,14 @@ class gradient_arena:
     straight into consecutive slices of `flat` (59 floats per Gaussian at M = 16, in that order), so a
     data-parallel step can all-reduce `flat` without a packing copy.  The returned gradient tensors are
     views of `flat`.  Entered around the forward call as well, it lets the library zero those slices beside the forward pass already
-    (gsr_backward_prefill): `flat` then belongs to that render from its forward call on."""
+    (gsr_backward_prefill): `flat` then belongs to that render from its forward call until its backward call.  ONE arena around the
+    forward calls of several renders that are all still waiting for their backward calls is not supported -- their gradient views
+    would be the same memory -- and the second such forward call raises GsrError; give every render in flight an arena of its own
+    (the other cameras into a scratch arena, then add_, as bench.py does).  The refusal is decided at forward time, from the arena
+    set around the forward calls alone, whatever arena -- or none -- the backward calls later run under: the claim ends with the
+    owner's backward call, with a forward call that fails, or when the owner's autograd graph is freed, so a render with gradients
+    whose image is kept but never run backward holds its arena for as long as that image lives.  An arena entered around backward
+    calls only is never claimed and is overwritten by each of them in turn: consume or add it before the next one."""
 
     def __init__(self, flat: torch.Tensor):
         self.flat = flat
@@ -396,8 +435,11 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
         if dc.dim() != 3 or dc.shape[1] != 1 or rest.dim() != 3 or rest.shape[1] < 1:
             raise _lib.GsrError("features_dc must be [P,1,3] and features_rest [P,M-1,3] with M >= 2")
         empty = m3.new_empty((0,))
+        # announce_backward: nothing is announced in the fused form (HipBackend.forward); it only lets a gradient arena set around
+        # this call be claimed for this render, so that ONE arena around several renders in flight is refused here as well
         num_rendered, color, radii, geom, binning, img = be.forward(raster_settings, m3, dc, empty, op, sc, rot, empty,
-                                                                    shs_rest=rest, raw_params=True)
+                                                                    shs_rest=rest, raw_params=True,
+                                                                    **({"announce_backward": True} if any(ctx.needs_input_grad) and hasattr(be, "_announced") else {}))
         ctx.raster_settings, ctx.num_rendered = raster_settings, num_rendered
         _remember_forward(geom, int(m3.shape[0]))
         ctx.save_for_backward(m3, dc, rest, sc, rot, radii, geom, binning, img)

@@ -257,7 +257,17 @@ def _as_hip_keys(ref_grads):
     return {hk: ref_grads.get(rk) for hk, rk in GRAD_KEYS}
 
 
-def parity_report(S, dL, hip=None, nthreads=0):
+def oracle_runs(S, dL, nthreads=0):
+    """(float32 forward, float32 backward, float64 forward, float64 backward) of the oracle on S with upstream gradient dL: what
+    parity_report() compares against, for callers that judge several HIP results against one oracle run."""
+    r32, r64 = ref.get("f32"), ref.get("f64")
+    nt = nthreads or r32.max_threads()
+    f32 = r32.forward(S, nthreads=nt); g32 = r32.backward(f32, dL, nthreads=nt)
+    f64 = r64.forward(S, nthreads=nt); g64 = r64.backward(f64, dL, nthreads=nt)
+    return f32, g32, f64, g64
+
+
+def parity_report(S, dL, hip=None, nthreads=0, oracles=None):
     """HIP vs oracle on one scene, everything the bar names:
       * radii bit-equal to the float32 oracle;
       * image: every pixel within RGB_ATOL of the float32 oracle unless the oracle's own decision margin certifies it;
@@ -265,11 +275,9 @@ def parity_report(S, dL, hip=None, nthreads=0):
         float32 CPU oracle -- the HIP kernels compute in float32, so "as close to float64 as a plain float32 evaluation"
         is the honest form of the 1e-3 bar (borderline alpha tests and cancelling sums make ~0.2 % of the Gaussians of
         ANY float32 evaluation miss 1e-3 of their own magnitude).
+    `oracles`: oracle_runs(S, dL) computed earlier (the same S and dL), instead of running the oracle again.
     Returns the report; assert_parity() applies the thresholds."""
-    r32, r64 = ref.get("f32"), ref.get("f64")
-    nt = nthreads or r32.max_threads()
-    f32 = r32.forward(S, nthreads=nt); g32 = r32.backward(f32, dL, nthreads=nt)
-    f64 = r64.forward(S, nthreads=nt); g64 = r64.backward(f64, dL, nthreads=nt)
+    f32, g32, f64, g64 = oracles if oracles is not None else oracle_runs(S, dL, nthreads)
     h = hip if hip is not None else hip_forward_backward(S, dL)
     H, G32, G64 = {}, {}, {}
     for hk, rk in GRAD_KEYS:

@@ -34,6 +34,8 @@ class OracleBackend:
         f = self.r.forward(S)
         key = self._next; self._next += 1
         self._states[key] = f
+        while len(self._states) > 64:          # kept for a retain_graph second backward; bounded
+            self._states.pop(next(iter(self._states)))
         handle = torch.tensor([key], dtype=torch.int64)
         return (f["num_rendered"], torch.from_numpy(f["color"].astype(np.float32)), torch.from_numpy(f["radii"].copy()),
                 handle, torch.zeros((0,), dtype=torch.uint8), torch.zeros((0,), dtype=torch.uint8))
@@ -41,7 +43,7 @@ class OracleBackend:
     def backward(self, rs, num_rendered, dL_dpix, means3D, radii, shs, colors_precomp, scales, rotations, cov3D_precomp,
                  geom, binning, img):
         P = means3D.shape[0]
-        f = self._states.pop(int(geom[0]))
+        f = self._states[int(geom[0])]
         g = self.r.backward(f, dL_dpix.detach().cpu().numpy())
         t = lambda a, shape: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).reshape(shape) if a is not None else torch.zeros((0,))
         M = shs.shape[1] if shs.numel() else 0
