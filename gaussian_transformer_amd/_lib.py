@@ -64,6 +64,11 @@ SIGNATURES = {
     "gsr_l1_ssim_workspace": (_i32, [_i32, _i32, _i32, C.POINTER(_sz)]),
     "gsr_l1_ssim_forward": (_i32, [_p, _i32, _i32, _i32, _p, _p, _f, _p, _p, _sz]),
     "gsr_l1_ssim_backward": (_i32, [_p, _i32, _i32, _i32, _p, _p, _f, _p, _p, _sz, _p]),
+    "gsr_views_loss_workspace": (_i32, [_i32, _i32, _i32, C.POINTER(_sz)]),                        # B H W bytes
+    "gsr_views_loss_forward": (_i32, [_p, _i32, _i32, _i32, C.POINTER(_p), C.POINTER(_p),          # stream B H W imgs gts (host arrays of device pointers)
+                                      _f, _f, _i32, _p, _p, _p, _sz]),                             # w_l1 w_ssim sanitize out3 terms ws ws_bytes
+    "gsr_views_loss_backward": (_i32, [_p, _i32, _i32, _i32, C.POINTER(_p), C.POINTER(_p),
+                                       _f, _f, _i32, _p, _p, _sz, C.POINTER(_p)]),                 # ... grad_loss ws ws_bytes grad_imgs
     "gsr_knn_workspace": (_i32, [_i32, C.POINTER(_sz)]),
     "gsr_knn_mean_dist2": (_i32, [_p, _i32, _p, _p, _p, _sz]),
     "gsr_adam_step": (_i32, [_p, _i32, C.POINTER(AdamGroup), C.c_double, C.c_double, C.c_double]),

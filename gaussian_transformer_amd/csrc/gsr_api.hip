@@ -949,6 +949,49 @@ int32_t gsr_l1_ssim_backward(gsr_stream_t stream, int32_t C, int32_t H, int32_t 
     return GSR_OK;
 }
 
+// ---- the same loss over B views (include/gsr_loss.h) ----
+static_assert(GSR_VIEWS_MAX_B == GSR_VIEWS_LOSS_MAX_B, "per-launch view limit of ssim_loss.hip and gsr_loss.h");
+// 0 = ok; everything the forward and the backward check alike, before anything is launched
+static int views_loss_check(const char *who, int32_t B, int32_t H, int32_t W, const float *const *imgs, const float *const *gts,
+                            const void *ws, size_t ws_bytes) {
+    size_t need = 0;
+    if (gsr_views_loss_workspace(B, H, W, &need) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
+    if (!imgs || !gts || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: null pointer (imgs, gts or workspace)", who);
+    for (int b = 0; b < B; b++)
+        if (!imgs[b] || !gts[b]) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: view %d: null %s pointer", who, b, imgs[b] ? "target" : "image");
+    if (ws_bytes < need) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: workspace %zu < %zu", who, ws_bytes, need);
+    return GSR_OK;
+}
+
+int32_t gsr_views_loss_workspace(int32_t B, int32_t H, int32_t W, size_t *bytes) {
+    if (B < 1 || H < 1 || W < 1 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_workspace: bad argument (B=%d H=%d W=%d)", B, H, W);
+    if ((H + 15) / 16 > 65535 || (size_t)3 * loss_blocks(1, H, W) > (size_t)INT32_MAX)
+        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_workspace: image %d x %d too large", W, H);
+    *bytes = views_loss_workspace_bytes(B, H, W);
+    return GSR_OK;
+}
+
+int32_t gsr_views_loss_forward(gsr_stream_t stream, int32_t B, int32_t H, int32_t W, const float *const *imgs, const float *const *gts,
+                               float w_l1, float w_ssim, int32_t sanitize, float *out3, float *terms, void *ws, size_t ws_bytes) {
+    const int rc = views_loss_check("gsr_views_loss_forward", B, H, W, imgs, gts, ws, ws_bytes);
+    if (rc != GSR_OK) return rc;
+    if (!out3 || !terms) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_forward: null pointer (out3 or terms)");
+    HIP_TRY(launch_views_loss_forward(B, H, W, imgs, gts, w_l1, w_ssim, sanitize ? 1 : 0, out3, terms, ws, (hipStream_t)stream),
+            "views loss forward launch");
+    return GSR_OK;
+}
+
+int32_t gsr_views_loss_backward(gsr_stream_t stream, int32_t B, int32_t H, int32_t W, const float *const *imgs, const float *const *gts,
+                                float w_l1, float w_ssim, int32_t sanitize, const float *grad_loss, const void *ws, size_t ws_bytes,
+                                float *const *grad_imgs) {
+    const int rc = views_loss_check("gsr_views_loss_backward", B, H, W, imgs, gts, ws, ws_bytes);
+    if (rc != GSR_OK) return rc;
+    if (!grad_imgs) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_backward: null pointer (grad_imgs)");
+    HIP_TRY(launch_views_loss_backward(B, H, W, imgs, gts, w_l1, w_ssim, sanitize ? 1 : 0, grad_loss, ws, grad_imgs, (hipStream_t)stream),
+            "views loss backward launch");
+    return GSR_OK;
+}
+
 // ---- Adam step over all parameter groups (include/gsr_optim.h) ----
 int32_t gsr_adam_step(gsr_stream_t stream, int32_t n_groups, const gsr_adam_group_t *groups, double beta1, double beta2, double eps) {
     if (n_groups < 0 || n_groups > GSR_ADAM_MAX_GROUPS || (n_groups > 0 && !groups))

@@ -401,6 +401,14 @@ hipError_t launch_l1_ssim_forward(int C, int H, int W, const float *img, const f
 hipError_t launch_l1_ssim_backward(int C, int H, int W, const float *img, const float *gt, float lambda, const float *dmaps,
                                    const float *grad_loss, float *grad_img, hipStream_t s);
 
+// the multi-view form (ssim_loss.hip); sizes and pointers validated by the caller: B, H, W >= 1, no NULL among imgs / gts
+#define GSR_VIEWS_MAX_B 16   // == GSR_VIEWS_LOSS_MAX_B: views whose pointers one launch carries in its kernel arguments
+size_t views_loss_workspace_bytes(int B, int H, int W);
+hipError_t launch_views_loss_forward(int B, int H, int W, const float *const *imgs, const float *const *gts, float w_l1, float w_ssim,
+                                     int sanitize, float *out3, float *terms, void *ws, hipStream_t s);
+hipError_t launch_views_loss_backward(int B, int H, int W, const float *const *imgs, const float *const *gts, float w_l1, float w_ssim,
+                                      int sanitize, const float *grad_loss, const void *ws, float *const *grad_imgs, hipStream_t s);
+
 hipError_t knn_workspace_bytes(int N, size_t *bytes);
 hipError_t launch_knn(int N, const float *pts, float *out, void *ws, hipStream_t s);
 

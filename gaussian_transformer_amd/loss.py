@@ -110,3 +110,165 @@ def fused_l1_ssim_loss(image: torch.Tensor, gt_image: torch.Tensor, lambda_dssim
     """Drop-in for training_loss() on a HIP device: same value and gradient w.r.t. `image`
     (gt_image gets no gradient, as in the reference's use at train.py:90-93)."""
     return _FusedL1SSIM.apply(image, gt_image, lambda_dssim)
+
+
+# ---------------------------------------------------------------- B views in one call ----------------------------------------------------------------
+# The image loss of the stacked trainer's step (train_stacked_transformer.py:203-222): B renders and B targets, each sanitised with
+# clamp(nan_to_num(.), 0, 1), L1Loss and 1 - ssim over the whole batch, weighted 5.0/B * 0.1 and 0.2/B * 0.1.  One HIP kernel per
+# direction over all views (include/gsr_loss.h: gsr_views_loss_*); every view is handed over by pointer, nothing is stacked.
+
+MAX_VIEWS_PER_LAUNCH = 16          # GSR_VIEWS_LOSS_MAX_B: the native call splits a larger B into further launches
+STACKED_W_L1 = 5.0 * 0.1           # train_stacked_transformer.py:219-220, each divided by the number of views
+STACKED_W_SSIM = 0.2 * 0.1
+
+
+def _as_view_inputs(who: str, name: str, x):
+    """`x` as a list of tensors, each [3,H,W] (one view) or [k,3,H,W] (k views): a sequence of B images or one [B,3,H,W] tensor.
+    Types, dtypes and shapes only; returns (tensors, number of views, (H, W))."""
+    from . import _lib
+    if isinstance(x, torch.Tensor):
+        if x.dtype != torch.float32:
+            raise _lib.GsrError(f"{who}: {name} must be float32, got {str(x.dtype).replace('torch.', '')}")
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1 or x.shape[2] < 1 or x.shape[3] < 1:
+            raise _lib.GsrError(f"{who}: {name} must be a sequence of [3,H,W] tensors or one [B,3,H,W] tensor with B >= 1, got shape {tuple(x.shape)}")
+        return [x], int(x.shape[0]), (int(x.shape[2]), int(x.shape[3]))
+    if not isinstance(x, (list, tuple)):
+        raise _lib.GsrError(f"{who}: {name} must be a sequence of tensors or one [B,3,H,W] tensor, got {type(x).__name__}")
+    if len(x) == 0:
+        raise _lib.GsrError(f"{who}: {name} is empty (at least one view is needed)")
+    for i, t in enumerate(x):
+        if not isinstance(t, torch.Tensor):
+            raise _lib.GsrError(f"{who}: {name}[{i}] must be a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise _lib.GsrError(f"{who}: {name}[{i}] must be float32, got {str(t.dtype).replace('torch.', '')}")
+        if t.dim() != 3 or t.shape[0] != 3 or t.shape[1] < 1 or t.shape[2] < 1:
+            raise _lib.GsrError(f"{who}: {name}[{i}] must have shape [3,H,W], got {tuple(t.shape)}")
+        if tuple(t.shape) != tuple(x[0].shape):
+            raise _lib.GsrError(f"{who}: all views must have one size: {name}[{i}] is {tuple(t.shape)}, {name}[0] is {tuple(x[0].shape)}")
+    return list(x), len(x), (int(x[0].shape[1]), int(x[0].shape[2]))
+
+
+def _validate_views(who: str, images, targets):
+    """Types, dtypes, shapes, equal view sizes and matching counts first, devices last (a CPU test can check every message)."""
+    from . import _lib
+    imgs, B, hw = _as_view_inputs(who, "images", images)
+    gts, Bt, hwt = _as_view_inputs(who, "targets", targets)
+    if B != Bt:
+        raise _lib.GsrError(f"{who}: {B} images but {Bt} targets")
+    if hw != hwt:
+        raise _lib.GsrError(f"{who}: images are {hw[0]} x {hw[1]} (H x W) but targets are {hwt[0]} x {hwt[1]}")
+    for name, ts in (("images", imgs), ("targets", gts)):
+        for i, t in enumerate(ts):
+            label = f"{name}[{i}]" if t.dim() == 3 else name
+            if t.device.type != "cuda":
+                raise _lib.GsrError(f"{who}: {label} must be on a HIP device, got {t.device} (no CPU fallback)")
+            if t.device != imgs[0].device:
+                raise _lib.GsrError(f"{who}: all views must be on one device: {label} is on {t.device}, the first image on {imgs[0].device}")
+    return imgs, gts, B, hw
+
+
+def _view_pointers(tensors):
+    """Device pointers of the views held by `tensors` (contiguous, [3,H,W] or [k,3,H,W] each), in order."""
+    ptrs = []
+    for t in tensors:
+        if t.dim() == 3:
+            ptrs.append(t.data_ptr())
+        else:
+            step = t.stride(0) * t.element_size()
+            ptrs.extend(t.data_ptr() + b * step for b in range(t.shape[0]))
+    return ptrs
+
+
+def _pointer_array(ptrs):
+    import ctypes as C
+    return (C.c_void_p * len(ptrs))(*ptrs)
+
+
+def _views_forward(imgs, gts, B, hw, w_l1, w_ssim, sanitize):
+    """imgs, gts: contiguous tensors on one HIP device.  Returns (out3, terms [B,3], workspace), enqueued on the current stream."""
+    import ctypes as C
+    from . import _lib
+    lib = _lib.load()
+    dev = imgs[0].device
+    nb = C.c_size_t()
+    _lib.check(lib.gsr_views_loss_workspace(B, hw[0], hw[1], C.byref(nb)), "gsr_views_loss_workspace")
+    with torch.cuda.device(dev):
+        ws = torch.empty((nb.value,), dtype=torch.uint8, device=dev)
+        out = torch.empty((3,), dtype=torch.float32, device=dev)
+        terms = torch.empty((B, 3), dtype=torch.float32, device=dev)
+        _lib.check(lib.gsr_views_loss_forward(torch.cuda.current_stream(dev).cuda_stream, B, hw[0], hw[1],
+                                              _pointer_array(_view_pointers(imgs)), _pointer_array(_view_pointers(gts)),
+                                              float(w_l1), float(w_ssim), 1 if sanitize else 0, out.data_ptr(), terms.data_ptr(),
+                                              ws.data_ptr(), nb.value), "gsr_views_loss_forward")
+    return out, terms, ws
+
+
+class _MultiViewLoss(torch.autograd.Function):
+    """w_l1 L1 + w_ssim (1 - SSIM) over B views in one HIP kernel per direction.  Inputs: n_img image tensors, then the target
+    tensors, each [3,H,W] or [k,3,H,W]; one gradient per image tensor that requires grad, written in place by one launch."""
+
+    @staticmethod
+    def forward(ctx, w_l1, w_ssim, sanitize, n_img, B, hw, *tensors):
+        imgs = [t.contiguous() for t in tensors[:n_img]]
+        gts = [t.detach().contiguous() for t in tensors[n_img:]]
+        out, terms, ws = _views_forward(imgs, gts, B, hw, w_l1, w_ssim, sanitize)
+        ctx.save_for_backward(ws, *imgs, *gts)
+        ctx.cfg = (float(w_l1), float(w_ssim), bool(sanitize), n_img, B, hw)
+        ctx.terms = terms
+        ctx.mark_non_differentiable(terms)
+        return out[0], terms
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_terms):
+        from . import _lib
+        lib = _lib.load()
+        w_l1, w_ssim, sanitize, n_img, B, hw = ctx.cfg
+        ws, *rest = ctx.saved_tensors
+        imgs, gts = rest[:n_img], rest[n_img:]
+        dev = imgs[0].device
+        with torch.cuda.device(dev):
+            g = grad_loss.to(device=dev, dtype=torch.float32).contiguous().reshape(1)
+            grads, gptrs = [], []
+            for i, t in enumerate(imgs):
+                k = 1 if t.dim() == 3 else int(t.shape[0])
+                if ctx.needs_input_grad[6 + i]:
+                    grads.append(torch.empty_like(t))
+                    gptrs.extend(_view_pointers([grads[-1]]))
+                else:
+                    grads.append(None)
+                    gptrs.extend([None] * k)                 # NULL: the kernel stores nothing for this view
+            if any(p is not None for p in gptrs):
+                _lib.check(lib.gsr_views_loss_backward(torch.cuda.current_stream(dev).cuda_stream, B, hw[0], hw[1],
+                                                       _pointer_array(_view_pointers(imgs)), _pointer_array(_view_pointers(gts)),
+                                                       w_l1, w_ssim, 1 if sanitize else 0, g.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                       _pointer_array(gptrs)), "gsr_views_loss_backward")
+        return (None,) * 6 + tuple(grads) + (None,) * len(gts)
+
+
+def multi_view_loss(images, targets, w_l1: float, w_ssim: float, sanitize: bool = True) -> torch.Tensor:
+    """w_l1 * L1 + w_ssim * (1 - SSIM) over B views, both means taken over all B*3*H*W entries (no SSIM window crosses a view).
+
+    images, targets: a sequence of B float32 [3,H,W] tensors or one [B,3,H,W] tensor, all of one size on one HIP device.  With
+    `sanitize`, every pixel x of both is read as clamp(nan_to_num(x), 0, 1) and the gradient is exactly 0 where the image's pixel
+    is not finite or outside [0, 1], as autograd has it for those torch ops.  Each image that requires grad receives its gradient
+    from one launch (targets get none); contiguous inputs are read in place.  The result carries `.terms`: [B,3], detached, per
+    view (mean |x-y|, mean SSIM, mean (x-y)^2) of the sanitised images.  Raises GsrError for anything else: no CPU fallback."""
+    imgs, gts, B, hw = _validate_views("multi_view_loss", images, targets)
+    out, terms = _MultiViewLoss.apply(float(w_l1), float(w_ssim), bool(sanitize), len(imgs), B, hw, *imgs, *gts)
+    out.terms = terms
+    return out
+
+
+def stacked_image_loss(images, targets) -> torch.Tensor:
+    """The image loss of the reference's stacked trainer for B = len(images) views (train_stacked_transformer.py:203-222):
+    0.5/B * L1 + 0.02/B * (1 - SSIM) of the sanitised renders and targets."""
+    _, _, B, _ = _validate_views("stacked_image_loss", images, targets)
+    return multi_view_loss(images, targets, STACKED_W_L1 / B, STACKED_W_SSIM / B, sanitize=True)
+
+
+def view_metrics(images, targets, sanitize: bool = False) -> dict:
+    """Per-view l1, ssim and psnr ([B] each, as train.py:163-186 reports them) from one forward launch; no graph is recorded."""
+    imgs, gts, B, hw = _validate_views("view_metrics", images, targets)
+    with torch.no_grad():
+        _, terms, _ = _views_forward([t.detach().contiguous() for t in imgs], [t.detach().contiguous() for t in gts], B, hw, 0.0, 0.0, sanitize)
+        return {"l1": terms[:, 0], "ssim": terms[:, 1], "psnr": 20 * torch.log10(1.0 / torch.sqrt(terms[:, 2]))}
