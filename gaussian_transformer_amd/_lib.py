@@ -98,6 +98,26 @@ SEQUENCE_SIGNATURES = {
                                  _p, _p, _p]),                                           # radii_out visible_out counts_out
 }
 
+# include/gsr_density.h (likewise a table of its own)
+DENSITY_MAX_GROUPS = 16
+DENSITY_COPY, DENSITY_XYZ, DENSITY_SCALING = 0, 1, 2
+
+
+class DensityGroup(C.Structure):       # gsr_density_group_t of include/gsr_density.h
+    _fields_ = [("src", C.c_void_p), ("src_exp_avg", C.c_void_p), ("src_exp_avg_sq", C.c_void_p),
+                ("dst", C.c_void_p), ("dst_exp_avg", C.c_void_p), ("dst_exp_avg_sq", C.c_void_p),
+                ("width_floats", C.c_int32), ("role", C.c_int32)]
+
+
+DENSITY_SIGNATURES = {
+    "gsr_density_record": (_i32, [_p, _i32, _p, _i32, _p, _p, _p, _p, _p]),             # stream P grad2d stride radii visible accum denom max_radii
+    "gsr_densify_plan_workspace": (_i32, [_i32, _i32, C.POINTER(_sz)]),                  # P N bytes
+    "gsr_densify_plan": (_i32, [_p, _i32, _p, _p, _p, _p, _f, _f, _f, _f, _i32,          # stream P opacity scaling accum denom thr min_opacity cut prune_world N
+                                _p, _p, _sz]),                                           # counts_host ws ws_bytes
+    "gsr_densify_apply": (_i32, [_p, _i32, _i32, _i32, _i32, _i32, C.POINTER(DensityGroup),   # stream P N n_split P_new n_groups groups
+                                 _p, _p, _p, _p, _sz]),                                  # scaling rotation noise ws ws_bytes
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -124,7 +144,7 @@ def load() -> C.CDLL:
             lib = C.CDLL(LIB_PATH)
         except OSError as e:
             raise GsrError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES, **SEQUENCE_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES, **SEQUENCE_SIGNATURES, **DENSITY_SIGNATURES}.items():
             fn = getattr(lib, name)       # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

@@ -44,6 +44,7 @@ SOURCES = {
     # packed, 208 v_sub / v_fmac + 16 others scalar; read from the ISA, not timed)
     "chamfer.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],
     "sequence.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],   # as preprocess.hip: gsr_visible_union's radii must round as gsr_forward's
+    "density.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],    # record's norm and the split children round as written (include/gsr_density.h)
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result",
           "-fgpu-rdc" if False else "-fno-gpu-rdc"]
@@ -71,7 +72,7 @@ def build_variant(tag: str, defines, verbose: bool = False, force: bool = False)
     odir = os.path.join(OBJ, tag)
     os.makedirs(odir, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")] + [os.path.abspath(__file__)]
-    headers += [os.path.join(HERE, "..", "include", h) for h in ("gsr.h", "gsr_loss.h", "gsr_knn.h", "gsr_optim.h", "gsr_chamfer.h", "gsr_sequence.h")]
+    headers += [os.path.join(HERE, "..", "include", h) for h in ("gsr.h", "gsr_loss.h", "gsr_knn.h", "gsr_optim.h", "gsr_chamfer.h", "gsr_sequence.h", "gsr_density.h")]
     jobs, objs = [], []
     for src, extra in SOURCES.items():
         s, o = os.path.join(CSRC, src), os.path.join(odir, src.replace(".hip", ".o"))
@@ -105,6 +106,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
     headers.append(os.path.join(HERE, "..", "include", "gsr_optim.h"))
     headers.append(os.path.join(HERE, "..", "include", "gsr_chamfer.h"))
     headers.append(os.path.join(HERE, "..", "include", "gsr_sequence.h"))
+    headers.append(os.path.join(HERE, "..", "include", "gsr_density.h"))
     headers.append(os.path.abspath(__file__))
     cc = hipcc()
     jobs = []

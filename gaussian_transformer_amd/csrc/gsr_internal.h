@@ -438,4 +438,11 @@ hipError_t launch_box_sort(int P, int D, const float *rows, int xyz_col, int n, 
                            void *ws, hipStream_t s);
 hipError_t launch_visible_union(const VisibleArgs &a, hipStream_t s);
 
+// density.hip (include/gsr_density.h); sizes, pointers and roles validated by the caller, P >= 1
+hipError_t launch_density_record(int P, const float *grad2d, int stride, const int32_t *radii, const uint8_t *visible, float *accum,
+                                 float *denom, float *max_radii, hipStream_t s);
+hipError_t densify_plan_workspace_bytes(int P, int N, size_t *bytes);
+hipError_t launch_densify_plan(int P, const float *opacity, const float *scaling, const float *accum, const float *denom, float grad_threshold,
+                               float min_opacity, float cut, float prune_world, int N, uint32_t *counts_host, void *ws, hipStream_t s);
+
 }  // namespace gsr

@@ -4,19 +4,24 @@ Restates the behaviour of the reference's scene/gaussian_model.py: training_setu
 update_learning_rate :169-175 with utils/general_utils.py:29-61 (log-linear decay of the position rate),
 reset_opacity :210-213, the optimiser-state surgery :258-322, densify_and_split :349-371, densify_and_clone :373-387,
 densify_and_prune :389-403 -- and of train.py:113-123, which drives it.  Everything is torch index arithmetic on the
-device that holds the Gaussians; no kernel of its own is needed.
+device that holds the Gaussians; no kernel of its own is needed.  FusedDensityController, at the end, is the same
+controller with the statistics and the clone / split / prune on the HIP path (include/gsr_density.h): opt-in, and held to
+DensityController, which stays the oracle.
 
 One deliberate extension: `densify_and_split` draws its samples from a caller-supplied torch.Generator, so
 data-parallel ranks that seed it identically split identically (the reference uses the global RNG).
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from dataclasses import dataclass
 from typing import Callable, Dict, Optional
 
+import numpy as np
 import torch
 
+from . import _lib
 from .model import GaussianParams, inverse_sigmoid
 
 GROUPS = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")          # order of training_setup :155-162
@@ -222,3 +227,140 @@ class DensityController:
             if iteration % o.opacity_reset_interval == 0 or (white_background and iteration == o.densify_from_iter):
                 self.reset_opacity()
         return out
+
+
+_ROLE = {"xyz": _lib.DENSITY_XYZ, "scaling": _lib.DENSITY_SCALING}          # every other group is a plain copy
+
+
+class FusedDensityController(DensityController):
+    """DensityController with `record` and `densify_and_prune` on the device (include/gsr_density.h, csrc/density.hip):
+    record is one launch without a host wait; densify_and_prune decides every Gaussian once, waits once for the four counts,
+    and writes the new parameters and Adam moments in one launch instead of rebuilding them four times.  Same constructor,
+    same public methods, same results: copied rows bit for bit, the split children to float32 rounding of the same formula
+    on the same samples.  No CPU fallback."""
+
+    SPLIT_N = 2                        # densify_and_split's N (:349)
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._counts = None            # pinned host words {n_clone, n_split, n_pruned, P_new}
+        self._ws = None
+
+    @staticmethod
+    def _device_f32(name: str, t: torch.Tensor) -> torch.Tensor:
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise _lib.GsrError(f"FusedDensityController: {name} must be on a HIP device (no CPU fallback)")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.GsrError(f"FusedDensityController: {name} must be contiguous float32, got {t.dtype}")
+        return t
+
+    def record(self, viewspace_points: torch.Tensor, visibility: Optional[torch.Tensor], radii: torch.Tensor) -> None:
+        """train.py:113-116 in one launch.  viewspace_points.grad is taken as it comes: [P, >= 2] float32 with unit column
+        stride and any row stride (a view into a gradient arena).  visibility None: radii > 0."""
+        m = self.model
+        grad = viewspace_points.grad
+        if grad is None:
+            raise _lib.GsrError("FusedDensityController.record: viewspace_points has no gradient")
+        if grad.device.type != "cuda":
+            raise _lib.GsrError("FusedDensityController.record: the gradient must be on a HIP device (no CPU fallback)")
+        P = m._xyz.shape[0]
+        if grad.dtype != torch.float32 or grad.dim() != 2 or grad.shape[0] != P or grad.shape[1] < 2 or (P > 1 and grad.stride(0) < 2) or \
+                grad.stride(1) != 1:
+            grad = grad[:, :2].to(torch.float32).contiguous()
+        accum, denom, mx = (self._device_f32(n, t) for n, t in (("xyz_gradient_accum", m.xyz_gradient_accum), ("denom", m.denom),
+                                                                ("max_radii2D", m.max_radii2D)))
+        radii = radii if radii.dtype == torch.int32 and radii.is_contiguous() else radii.to(torch.int32).contiguous()
+        if visibility is not None:
+            visibility = visibility if visibility.dtype in (torch.bool, torch.uint8) and visibility.is_contiguous() else (visibility != 0).contiguous()
+            if visibility.shape[0] != P:
+                raise _lib.GsrError(f"FusedDensityController.record: visibility has {visibility.shape[0]} rows, the model {P}")
+        if radii.shape[0] != P or radii.device != grad.device or (visibility is not None and visibility.device != grad.device):
+            raise _lib.GsrError("FusedDensityController.record: radii / visibility must have P rows on the gradient's device")
+        if P == 0:
+            return
+        with torch.cuda.device(grad.device):
+            stream = torch.cuda.current_stream(grad.device).cuda_stream
+            _lib.check(_lib.load().gsr_density_record(stream, P, grad.data_ptr(), max(int(grad.stride(0)), 2), radii.data_ptr(),
+                                                      visibility.data_ptr() if visibility is not None else None,
+                                                      accum.data_ptr(), denom.data_ptr(), mx.data_ptr()), "gsr_density_record")
+
+    def _reset_statistics(self, P: int, dev) -> None:
+        m = self.model
+        m.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
+        m.denom = torch.zeros((P, 1), device=dev)
+        m.max_radii2D = torch.zeros((P,), device=dev)
+
+    def densify_and_prune(self, max_grad: float, min_opacity: float, extent: float, max_screen_size: Optional[float],
+                          generator: Optional[torch.Generator] = None, normal_fn: Optional[Callable] = None) -> Dict[str, int]:
+        """:389-403 as plan -> one wait for the counts -> samples -> allocate -> apply -> install."""
+        m = self.model
+        N = self.SPLIT_N
+        olds = {g["name"]: g["params"][0] for g in self.optimizer.param_groups}
+        for n in GROUPS:
+            self._device_f32(n, olds[n].detach())
+        accum, denom = self._device_f32("xyz_gradient_accum", m.xyz_gradient_accum), self._device_f32("denom", m.denom)
+        dev = olds["xyz"].device
+        P = olds["xyz"].shape[0]
+        if P == 0:
+            self._reset_statistics(0, dev)
+            return {"cloned": 0, "split": 0, "pruned": 0}
+        lib = _lib.load()
+        f32 = lambda v: float(np.float32(v))       # torch compares a float32 tensor with float32(number)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            need = C.c_size_t(0)
+            _lib.check(lib.gsr_densify_plan_workspace(P, N, C.byref(need)), "gsr_densify_plan_workspace")
+            if self._ws is None or self._ws.numel() < need.value or self._ws.device != dev:
+                self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+            if self._counts is None:
+                self._counts = torch.zeros(4, dtype=torch.int32).pin_memory()
+            ws = self._ws
+            # 1. plan
+            _lib.check(lib.gsr_densify_plan(stream.cuda_stream, P, olds["opacity"].data_ptr(), olds["scaling"].data_ptr(), accum.data_ptr(),
+                                            denom.data_ptr(), f32(max_grad), f32(min_opacity), f32(self.opt.percent_dense * extent),
+                                            f32(0.1 * extent) if max_screen_size else -1.0, N, self._counts.data_ptr(), ws.data_ptr(),
+                                            ws.numel()), "gsr_densify_plan")
+            # 2. the only host wait of the call
+            stream.synchronize()
+            n_clone, n_split, n_pruned, P_new = (int(v) for v in self._counts.tolist())
+            # 3. the samples of the split, drawn as densify_and_split draws them (torch.normal(0, stds) is randn * stds)
+            ones = torch.ones((N * n_split, 3), device=dev)
+            noise = normal_fn(ones) if normal_fn is not None else torch.normal(mean=torch.zeros_like(ones), std=ones, generator=generator)
+            noise = noise.to(device=dev, dtype=torch.float32).contiguous()
+            # 4. the new tensors
+            new, states, descs = {}, {}, []
+            for g in self.optimizer.param_groups:
+                n, old = g["name"], g["params"][0]
+                state = self.optimizer.state.get(old, None)
+                has = state is not None and "exp_avg" in state
+                if has:
+                    self._device_f32(n + " exp_avg", state["exp_avg"]); self._device_f32(n + " exp_avg_sq", state["exp_avg_sq"])
+                shape = (P_new,) + tuple(old.shape[1:])
+                new[n] = torch.empty(shape, device=dev)
+                states[n] = (torch.empty(shape, device=dev), torch.empty(shape, device=dev)) if has else None
+                width = old[0].numel()
+                ptr = lambda t: t.data_ptr() if t.numel() else None
+                if width:
+                    descs.append(_lib.DensityGroup(old.data_ptr(), state["exp_avg"].data_ptr() if has else None,
+                                                   state["exp_avg_sq"].data_ptr() if has else None, ptr(new[n]),
+                                                   ptr(states[n][0]) if has else None, ptr(states[n][1]) if has else None, width, _ROLE.get(n, _lib.DENSITY_COPY)))
+            # 5. apply
+            if P_new:
+                arr = (_lib.DensityGroup * len(descs))(*descs)
+                _lib.check(lib.gsr_densify_apply(stream.cuda_stream, P, N, n_split, P_new, len(descs), arr, olds["scaling"].data_ptr(),
+                                                 olds["rotation"].data_ptr(), noise.data_ptr() if noise.numel() else None, ws.data_ptr(), ws.numel()),
+                           "gsr_densify_apply")
+        # 6. install, as _remap does
+        for g in self.optimizer.param_groups:
+            n, old = g["name"], g["params"][0]
+            state = self.optimizer.state.pop(old, None)
+            p = torch.nn.Parameter(new[n].requires_grad_(True))
+            if state is not None:
+                if states[n] is not None:
+                    state["exp_avg"], state["exp_avg_sq"] = states[n]
+                self.optimizer.state[p] = state
+            g["params"][0] = p
+            setattr(m, _ATTR[n], p)
+        # 7. statistics of the new set
+        self._reset_statistics(P_new, dev)
+        return {"cloned": n_clone, "split": n_split, "pruned": n_pruned}
