@@ -98,6 +98,12 @@ SEQUENCE_SIGNATURES = {
                                  _p, _p, _p]),                                           # radii_out visible_out counts_out
 }
 
+# include/gsr_rows.h (likewise a table of its own)
+ROWS_SIGNATURES = {
+    "gsr_rows_unpack": (_i32, [_p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p]),             # stream P D rows xyz f_dc f_rest opacity scaling rotation
+    "gsr_rows_grad_pack": (_i32, [_p, _i32, _i32, _i32, C.POINTER(_p), _p]),             # stream P D B arenas (host array of device pointers) grad_rows
+}
+
 # include/gsr_density.h (likewise a table of its own)
 DENSITY_MAX_GROUPS = 16
 DENSITY_COPY, DENSITY_XYZ, DENSITY_SCALING = 0, 1, 2
@@ -144,7 +150,7 @@ def load() -> C.CDLL:
             lib = C.CDLL(LIB_PATH)
         except OSError as e:
             raise GsrError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES, **SEQUENCE_SIGNATURES, **DENSITY_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES, **SEQUENCE_SIGNATURES, **ROWS_SIGNATURES, **DENSITY_SIGNATURES}.items():
             fn = getattr(lib, name)       # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

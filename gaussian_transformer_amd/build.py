@@ -45,6 +45,7 @@ SOURCES = {
     "chamfer.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],
     "sequence.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],   # as preprocess.hip: gsr_visible_union's radii must round as gsr_forward's
     "density.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],    # record's norm and the split children round as written (include/gsr_density.h)
+    "rows.hip": [],                # copies and float adds only (include/gsr_rows.h): nothing to contract
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result",
           "-fgpu-rdc" if False else "-fno-gpu-rdc"]
@@ -72,7 +73,7 @@ def build_variant(tag: str, defines, verbose: bool = False, force: bool = False)
     odir = os.path.join(OBJ, tag)
     os.makedirs(odir, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")] + [os.path.abspath(__file__)]
-    headers += [os.path.join(HERE, "..", "include", h) for h in ("gsr.h", "gsr_loss.h", "gsr_knn.h", "gsr_optim.h", "gsr_chamfer.h", "gsr_sequence.h", "gsr_density.h")]
+    headers += [os.path.join(HERE, "..", "include", h) for h in ("gsr.h", "gsr_loss.h", "gsr_knn.h", "gsr_optim.h", "gsr_chamfer.h", "gsr_sequence.h", "gsr_density.h", "gsr_rows.h")]
     jobs, objs = [], []
     for src, extra in SOURCES.items():
         s, o = os.path.join(CSRC, src), os.path.join(odir, src.replace(".hip", ".o"))
@@ -107,6 +108,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
     headers.append(os.path.join(HERE, "..", "include", "gsr_chamfer.h"))
     headers.append(os.path.join(HERE, "..", "include", "gsr_sequence.h"))
     headers.append(os.path.join(HERE, "..", "include", "gsr_density.h"))
+    headers.append(os.path.join(HERE, "..", "include", "gsr_rows.h"))
     headers.append(os.path.abspath(__file__))
     cc = hipcc()
     jobs = []
