@@ -22,6 +22,7 @@ _f = C.c_float
 _sz = C.c_size_t
 
 ADAM_MAX_GROUPS = 16
+ADAM_MASK_BYTES, ADAM_MASK_RADII = 0, 1
 
 
 class AdamGroup(C.Structure):          # gsr_adam_group_t of include/gsr_optim.h
@@ -72,6 +73,7 @@ SIGNATURES = {
     "gsr_knn_workspace": (_i32, [_i32, C.POINTER(_sz)]),
     "gsr_knn_mean_dist2": (_i32, [_p, _i32, _p, _p, _p, _sz]),
     "gsr_adam_step": (_i32, [_p, _i32, C.POINTER(AdamGroup), C.c_double, C.c_double, C.c_double]),
+    "gsr_adam_step_masked": (_i32, [_p, _i32, C.POINTER(AdamGroup), C.c_double, C.c_double, C.c_double, _i32, _p, _i32]),   # ... P mask mask_kind
     "gsr_set_option": (_i32, [C.c_char_p, _i32]),
     "gsr_get_option": (_i32, [C.c_char_p, C.POINTER(_i32)]),
     "gsr_set_profiling": (_i32, [_i32]),

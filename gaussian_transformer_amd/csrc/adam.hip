@@ -1,8 +1,11 @@
 // adam.hip -- one launch for the Adam step of all parameter groups (include/gsr_optim.h).  Pure streaming:
 // 16 bytes read + 12 written per element, float4 wide where the group's length and pointers allow.
+// Below it the visibility-masked step (gsr_adam_step_masked): the same update through the same adam_one, on the visible rows only.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stdarg.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "../../include/gsr_optim.h"
 #include "gsr_internal.h"
@@ -94,4 +97,172 @@ hipError_t launch_adam(int n_groups, const gsr_adam_group_t *groups, double beta
     return hipGetLastError();
 }
 
+// ---- the visibility-masked step (gsr_adam_step_masked) ----
+// Same grid as adam_kernel: a block owns 4096 consecutive elements of one group, a lane the same elements as there.  A group is
+// [P, w] row-major, so element j lies in row j / w.  One division per thread; from one of its elements to the next the row and the
+// remainder advance by the group's (step / w, step % w), step = 1024 floats in the float4 body and 256 in the scalar one.
+struct AdamMaskedArgs {
+    AdamArgs a;
+    int w[GSR_ADAM_MAX_GROUPS];              // floats per row
+    int q_step[GSR_ADAM_MAX_GROUPS];         // step / w
+    int r_step[GSR_ADAM_MAX_GROUPS];         // step % w
+    const void *mask;
+};
+
+template <int KIND>
+__device__ __forceinline__ bool row_visible(const void *mask, unsigned row) {
+    if (KIND == GSR_ADAM_MASK_RADII) return static_cast<const int32_t *>(mask)[row] > 0;
+    return static_cast<const uint8_t *>(mask)[row] != 0;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void adam_masked_kernel(AdamMaskedArgs A) {
+    const AdamArgs &a = A.a;
+    int gi = 0;
+#pragma unroll 1
+    for (int k = 1; k < a.n_groups; k++)
+        if (blockIdx.x >= a.grp[k].first_block) gi = k;          // block-uniform
+    const AdamGroupDev &G = a.grp[gi];
+    const unsigned w = (unsigned)A.w[gi], q_step = (unsigned)A.q_step[gi], r_step = (unsigned)A.r_step[gi];
+    const unsigned n = (unsigned)G.n;                            // n <= 2^31 - 1 (checked on the host)
+    const unsigned base = (blockIdx.x - G.first_block) * ADAM_PER_BLOCK;
+    if (G.vec4) {
+        // pass 1: the visibility of this lane's 4 x 4 elements, one mask read per row entered (bit c of vis[it] = element i + c)
+        unsigned vis[4];
+        {
+            const unsigned i0 = base + threadIdx.x * 4;
+            unsigned row = i0 / w, rem = i0 - row * w;
+#pragma unroll
+            for (int it = 0; it < 4; it++) {
+                const unsigned i = i0 + it * 1024;
+                unsigned bits = 0;
+                if (i < n) {
+                    unsigned r = row, q = rem;
+                    bool on = row_visible<KIND>(A.mask, r);
+#pragma unroll
+                    for (int c = 0; c < 4; c++) {
+                        if (on) bits |= 1u << c;
+                        if (++q == w && c < 3 && i + c + 1 < n) { q = 0; r++; on = row_visible<KIND>(A.mask, r); }
+                    }
+                }
+                vis[it] = bits;
+                row += q_step; rem += r_step;
+                if (rem >= w) { rem -= w; row++; }
+            }
+        }
+        // pass 2: adam_kernel's float4 body; a wave without a visible element touches neither the four arrays nor anything else
+#pragma unroll
+        for (int it = 0; it < 4; it++) {
+            const unsigned bits = vis[it];
+            if (__ballot(bits != 0) == 0) continue;              // wave-uniform
+            if (bits == 0) continue;
+            const unsigned i = base + (it * 256 + threadIdx.x) * 4;
+            if (i + 3 < n) {
+                // a float4 may straddle rows of different visibility: all four lanes of it are computed as in adam_kernel, the invisible
+                // ones get their loaded bits back (a NaN there passes through v_cndmask untouched and reaches nothing)
+                const float4 p0 = *reinterpret_cast<float4 *>(G.p + i), m0 = *reinterpret_cast<float4 *>(G.m + i), v0 = *reinterpret_cast<float4 *>(G.v + i);
+                const float4 g = *reinterpret_cast<const float4 *>(G.g + i);
+                float4 p = p0, m = m0, v = v0;
+                adam_one(p.x, g.x, m.x, v.x, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
+                adam_one(p.y, g.y, m.y, v.y, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
+                adam_one(p.z, g.z, m.z, v.z, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
+                adam_one(p.w, g.w, m.w, v.w, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
+                if (!(bits & 1)) { p.x = p0.x; m.x = m0.x; v.x = v0.x; }
+                if (!(bits & 2)) { p.y = p0.y; m.y = m0.y; v.y = v0.y; }
+                if (!(bits & 4)) { p.z = p0.z; m.z = m0.z; v.z = v0.z; }
+                if (!(bits & 8)) { p.w = p0.w; m.w = m0.w; v.w = v0.w; }
+                *reinterpret_cast<float4 *>(G.p + i) = p; *reinterpret_cast<float4 *>(G.m + i) = m; *reinterpret_cast<float4 *>(G.v + i) = v;
+            } else {
+#pragma unroll 1
+                for (unsigned c = 0; c < 4 && i + c < n; c++) {
+                    if (!(bits >> c & 1)) continue;
+                    const unsigned j = i + c;
+                    float p = G.p[j], m = G.m[j], v = G.v[j];
+                    adam_one(p, G.g[j], m, v, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
+                    G.p[j] = p; G.m[j] = m; G.v[j] = v;
+                }
+            }
+        }
+    } else {
+        const unsigned j0 = base + threadIdx.x;
+        unsigned row = j0 / w, rem = j0 - row * w;
+        for (int it = 0; it < 16; it++) {
+            const unsigned j = j0 + it * 256;
+            const bool on = j < n && row_visible<KIND>(A.mask, row);
+            row += q_step; rem += r_step;
+            if (rem >= w) { rem -= w; row++; }
+            if (__ballot(on) == 0) continue;                     // wave-uniform
+            if (on) {
+                float p = G.p[j], m = G.m[j], v = G.v[j];
+                adam_one(p, G.g[j], m, v, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
+                G.p[j] = p; G.m[j] = m; G.v[j] = v;
+            }
+        }
+    }
+}
+
 }  // namespace gsr
+
+// gsr_last_error() hands out this thread's message buffer (gsr_api.hip: 512 bytes); the text goes there as every entry point's does.
+static int adam_fail(int code, const char *fmt, ...) {
+    char *buf = const_cast<char *>(gsr_last_error());
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, 256, fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+extern "C" int32_t gsr_adam_step_masked(gsr_stream_t stream, int32_t n_groups, const gsr_adam_group_t *groups, double beta1, double beta2,
+                                        double eps, int32_t P, const void *mask, int32_t mask_kind) {
+    using namespace gsr;
+    const char *const who = "gsr_adam_step_masked";
+    if (n_groups < 1 || n_groups > GSR_ADAM_MAX_GROUPS || !groups)
+        return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: %d groups (1 to %d)", who, n_groups, GSR_ADAM_MAX_GROUPS);
+    if (P < 0) return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P=%d is negative", who, P);
+    if (mask_kind != GSR_ADAM_MASK_BYTES && mask_kind != GSR_ADAM_MASK_RADII)
+        return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: unknown mask_kind %d", who, mask_kind);
+    if (P > 0 && !mask) return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: mask is NULL with P=%d", who, P);
+    if (mask_kind == GSR_ADAM_MASK_RADII && ((uintptr_t)mask & 3))
+        return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: an int32 mask must be 4-byte aligned", who);
+    for (int k = 0; k < n_groups; k++) {
+        const gsr_adam_group_t &g = groups[k];
+        if (g.n < 0 || g.n > 0x7fffffffLL) return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: n=%lld not in 0..2^31-1", who, k, (long long)g.n);
+        if (g.n > 0 && (P == 0 || g.n % P != 0))
+            return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: n=%lld is not a multiple of P=%d", who, k, (long long)g.n, P);
+        if (g.n > 0 && (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq))
+            return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: a NULL buffer with n=%lld", who, k, (long long)g.n);
+        if (g.step < 1) return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: step=%d", who, k, g.step);
+    }
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: betas", who);
+
+    AdamMaskedArgs A;
+    AdamArgs &a = A.a;
+    a.n_groups = 0; a.beta2 = (float)beta2; a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps;
+    A.mask = mask;
+    unsigned blocks = 0;                         // at most 16 groups of 2^19 blocks
+    for (int k = 0; k < n_groups; k++) {
+        const gsr_adam_group_t &h = groups[k];
+        if (h.n <= 0) continue;
+        const int s = a.n_groups++;
+        AdamGroupDev &d = a.grp[s];
+        d.p = h.param; d.g = h.grad; d.m = h.exp_avg; d.v = h.exp_avg_sq; d.n = h.n;
+        const double bc1 = 1.0 - pow(beta1, (double)h.step), bc2 = 1.0 - pow(beta2, (double)h.step);      // as launch_adam, to the letter
+        d.step_size = (float)((double)h.lr / bc1);
+        d.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+        d.first_block = blocks;
+        d.vec4 = ((((uintptr_t)h.param | (uintptr_t)h.grad | (uintptr_t)h.exp_avg | (uintptr_t)h.exp_avg_sq) & 15) == 0) ? 1 : 0;
+        const long long w = h.n / P, step = d.vec4 ? 1024 : 256;
+        A.w[s] = (int)w; A.q_step[s] = (int)(step / w); A.r_step[s] = (int)(step % w);
+        blocks += (unsigned)((h.n + ADAM_PER_BLOCK - 1) / ADAM_PER_BLOCK);
+    }
+    for (int s = a.n_groups; s < GSR_ADAM_MAX_GROUPS; s++) A.w[s] = A.q_step[s] = A.r_step[s] = 0;
+    if (blocks == 0) return GSR_OK;
+    if (mask_kind == GSR_ADAM_MASK_RADII)
+        hipLaunchKernelGGL(adam_masked_kernel<GSR_ADAM_MASK_RADII>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, A);
+    else
+        hipLaunchKernelGGL(adam_masked_kernel<GSR_ADAM_MASK_BYTES>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, A);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return adam_fail(GSR_ERR_HIP, "masked adam launch: %s (%d)", hipGetErrorString(e), (int)e);
+    return GSR_OK;
+}

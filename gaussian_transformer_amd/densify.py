@@ -79,7 +79,10 @@ class DensityController:
 
     def __init__(self, model: GaussianParams, opt: Optional[OptimizationParams] = None, spatial_lr_scale: float = 1.0,
                  fused_adam: bool = False, adam: str = "torch"):
-        """adam: "torch" (torch.optim.Adam; fused_adam=True for its fused kernels) or "hip" (optim.HipAdam, one launch)."""
+        """adam: "torch" (torch.optim.Adam; fused_adam=True for its fused kernels), "hip" (optim.HipAdam, one launch) or
+        "hip_sparse" (optim.HipSparseAdam: `optimizer.step(visibility=radii)` skips the Gaussians the view did not see)."""
+        if adam not in ("torch", "hip", "hip_sparse"):
+            raise ValueError(f"adam must be 'torch', 'hip' or 'hip_sparse', got {adam!r}")
         self.model = model
         self.opt = opt or OptimizationParams()
         self.spatial_lr_scale = spatial_lr_scale
@@ -96,6 +99,9 @@ class DensityController:
         if adam == "hip":
             from .optim import HipAdam
             self.optimizer = HipAdam(groups, lr=0.0, eps=1e-15)
+        elif adam == "hip_sparse":
+            from .optim import HipSparseAdam
+            self.optimizer = HipSparseAdam(groups, lr=0.0, eps=1e-15)
         else:
             self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15, **({"fused": True} if fused_adam else {}))
         self._xyz_lr = expon_lr(o.position_lr_init * spatial_lr_scale, o.position_lr_final * spatial_lr_scale,

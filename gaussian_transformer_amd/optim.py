@@ -4,6 +4,8 @@ A torch.optim.Optimizer with the state layout of torch.optim.Adam ("step", "exp_
 optimiser-state surgery of densify.py -- and anything else written against the reference's optimiser
 (scene/gaussian_model.py:155-164: six one-tensor groups, eps 1e-15) -- works on it unchanged.  No weight decay, no
 amsgrad, like the reference's.  There is no CPU fallback: parameters must be float32 tensors on a HIP device.
+
+HipSparseAdam is the opt-in variant whose step takes the iteration's visibility mask and skips the Gaussians no view saw.
 """
 from __future__ import annotations
 
@@ -20,11 +22,17 @@ class HipAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        return self._step(closure, None)
+
+    def _step(self, closure, visibility):
+        """One step of every tensor that has a gradient; visibility None: gsr_adam_step, else gsr_adam_step_masked with that mask
+        (checked by HipSparseAdam.step).  Every tensor is checked before any state changes and before anything is launched."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         lib = _lib.load()
+        name = type(self).__name__
         by_hyper = {}
         keep = []                                   # tensors that must outlive the launch call
         for g in self.param_groups:
@@ -32,7 +40,15 @@ class HipAdam(torch.optim.Optimizer):
                 if p.grad is None:
                     continue
                 if p.dtype != torch.float32 or p.device.type != "cuda" or not p.is_contiguous():
-                    raise _lib.GsrError("HipAdam needs contiguous float32 parameters on a HIP device (no CPU fallback)")
+                    raise _lib.GsrError(f"{name} needs contiguous float32 parameters on a HIP device (no CPU fallback)")
+                if visibility is not None and (p.device != visibility.device or p.dim() == 0 or p.shape[0] != visibility.shape[0]):
+                    who = g.get("name")
+                    raise _lib.GsrError(f"{name}: parameter {who + ' ' if who else ''}of shape {tuple(p.shape)} on {p.device} does not have the "
+                                        f"{visibility.shape[0]} rows of visibility on {visibility.device}")
+        for g in self.param_groups:
+            for p in g["params"]:
+                if p.grad is None:
+                    continue
                 st = self.state[p]
                 if len(st) == 0:
                     st["step"] = 0
@@ -45,11 +61,41 @@ class HipAdam(torch.optim.Optimizer):
                 by_hyper.setdefault(key, []).append(
                     _lib.AdamGroup(p.data_ptr(), grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                                    p.numel(), float(g["lr"]), st["step"]))
+        if visibility is not None:
+            kind = _lib.ADAM_MASK_RADII if visibility.dtype == torch.int32 else _lib.ADAM_MASK_BYTES
+            P, mask = int(visibility.shape[0]), (visibility.data_ptr() or None)
         for (dev, betas, eps), groups in by_hyper.items():
             with torch.cuda.device(dev):
                 stream = torch.cuda.current_stream(dev).cuda_stream
                 for i in range(0, len(groups), _lib.ADAM_MAX_GROUPS):
                     chunk = groups[i:i + _lib.ADAM_MAX_GROUPS]
                     arr = (_lib.AdamGroup * len(chunk))(*chunk)
-                    _lib.check(lib.gsr_adam_step(stream, len(chunk), arr, betas[0], betas[1], eps), "gsr_adam_step")
+                    if visibility is None:
+                        _lib.check(lib.gsr_adam_step(stream, len(chunk), arr, betas[0], betas[1], eps), "gsr_adam_step")
+                    else:
+                        _lib.check(lib.gsr_adam_step_masked(stream, len(chunk), arr, betas[0], betas[1], eps, P, mask, kind),
+                                   "gsr_adam_step_masked")
         return loss
+
+
+class HipSparseAdam(HipAdam):
+    """HipAdam whose step takes the per-Gaussian visibility of the iteration and leaves alone every row no view saw
+    (gsr_adam_step_masked, include/gsr_optim.h): `optimizer.step(visibility=radii)`.  A visible row gets HipAdam's update bit for
+    bit; an invisible one keeps parameter and moments bit for bit -- it neither decays its moments nor coasts on its momentum, which
+    is where this differs from dense Adam on a zero gradient.  `step` stays one count per tensor and advances on every call.
+    Same state layout as HipAdam, so densify.py works on it unchanged."""
+
+    @torch.no_grad()
+    def step(self, closure=None, *, visibility=None):
+        """visibility: None (exactly HipAdam.step) or a contiguous 1-D tensor of P entries on the parameters' device: torch.bool /
+        torch.uint8 (visible iff != 0) or torch.int32 (the rasterizer's radii, visible iff > 0).  Every tensor that has a gradient
+        must have P rows; tensors without one are skipped first, so the step right after a densification does nothing."""
+        if visibility is not None:
+            if not isinstance(visibility, torch.Tensor) or visibility.dtype not in (torch.bool, torch.uint8, torch.int32):
+                raise _lib.GsrError("HipSparseAdam: visibility must be a torch.bool, torch.uint8 or torch.int32 tensor, got "
+                                    f"{getattr(visibility, 'dtype', type(visibility).__name__)}")
+            if visibility.dim() != 1 or not visibility.is_contiguous():
+                raise _lib.GsrError(f"HipSparseAdam: visibility must be 1-D and contiguous, got shape {tuple(visibility.shape)}")
+            if visibility.device.type != "cuda":
+                raise _lib.GsrError("HipSparseAdam: visibility must be on a HIP device (no CPU fallback)")
+        return self._step(closure, visibility)

@@ -4,7 +4,7 @@
 -> Adam step.  Target images come from a hidden "ground truth" set of Gaussians seen from a ring of cameras; the trained
 set starts from a perturbed, thinned copy.  Informational (bench.py is the headline metric).
 
-    python scripts/train_synthetic.py [--iters 600] [--P 20000] [--size 256] [--density torch|hip]
+    python scripts/train_synthetic.py [--iters 600] [--P 20000] [--size 256] [--density torch|hip] [--adam hip|hip_sparse]
 """
 import argparse, json, math, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,7 +19,7 @@ from gaussian_transformer_amd.model import GaussianParams
 from gaussian_transformer_amd.render import PipelineParams, TorchCamera, render_fused
 
 
-def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_every=100, log=None, density="torch"):
+def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_every=100, log=None, density="torch", adam="hip"):
     dev = torch.device("cuda", 0)
     sc = synth.make_scene(P=P, width=size, height=size, sh_degree=1, s0=0.03, seed=seed, zmin=3.0, zmax=6.0)
     truth = GaussianParams.from_synthetic(sc, dev, requires_grad=False)
@@ -41,7 +41,7 @@ def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_
     model = GaussianParams.from_synthetic(sc0, dev)
     opt = OptimizationParams(densify_from_iter=densify_from, densification_interval=densify_every, opacity_reset_interval=10 ** 9,
                              densify_until_iter=iters)
-    ctl = (FusedDensityController if density == "hip" else DensityController)(model, opt, spatial_lr_scale=1.0, adam="hip")
+    ctl = (FusedDensityController if density == "hip" else DensityController)(model, opt, spatial_lr_scale=1.0, adam=adam)
     gen = torch.Generator(device=dev).manual_seed(seed)
 
     def evaluate():
@@ -60,7 +60,10 @@ def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_
         loss.backward()
         with torch.no_grad():
             ev = ctl.after_backward(it, pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"], extent=3.0, generator=gen)
-            ctl.optimizer.step()
+            if adam == "hip_sparse":       # rows of Gaussians outside this view stand still (include/gsr_optim.h); a no-op right after a densification
+                ctl.optimizer.step(visibility=pkg["radii"])
+            else:
+                ctl.optimizer.step()
             ctl.optimizer.zero_grad(set_to_none=True)
         if it % 50 == 0 or ev:
             rec = {"it": it, "loss": round(float(loss.detach()), 5), "P": int(model._xyz.shape[0]), "event": ev}
@@ -70,7 +73,7 @@ def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     loss1, psnr1 = evaluate()
-    return {"density": density, "iters": iters, "seconds": round(dt, 2), "it_per_s": round(iters / dt, 1), "P_start": len(keep), "P_end": int(model._xyz.shape[0]),
+    return {"density": density, "adam": adam, "iters": iters, "seconds": round(dt, 2), "it_per_s": round(iters / dt, 1), "P_start": len(keep), "P_end": int(model._xyz.shape[0]),
             "loss_first": round(loss0, 5), "loss_last": round(loss1, 5), "psnr_first": round(psnr0, 2), "psnr": round(psnr1, 2),
             "history": hist}
 
@@ -82,7 +85,9 @@ if __name__ == "__main__":
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--density", choices=("torch", "hip"), default="torch",
                     help="density control: torch index arithmetic (DensityController) or the HIP path (FusedDensityController)")
+    ap.add_argument("--adam", choices=("hip", "hip_sparse"), default="hip",
+                    help="hip = HipAdam over all rows; hip_sparse = HipSparseAdam with the view's radii as visibility")
     a = ap.parse_args()
-    out = run(a.iters, a.P, a.size, density=a.density, log=lambda r: print(json.dumps(r), flush=True))
+    out = run(a.iters, a.P, a.size, density=a.density, adam=a.adam, log=lambda r: print(json.dumps(r), flush=True))
     out.pop("history")
     print(json.dumps(out))
