@@ -47,8 +47,7 @@ SOURCES = {
     "density.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],    # record's norm and the split children round as written (include/gsr_density.h)
     "rows.hip": [],                # copies and float adds only (include/gsr_rows.h): nothing to contract
 }
-COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result",
-          "-fgpu-rdc" if False else "-fno-gpu-rdc"]
+COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result", "-fno-gpu-rdc"]
 
 
 def hipcc() -> str:
@@ -56,6 +55,12 @@ def hipcc() -> str:
     if not os.path.exists(exe):
         raise RuntimeError("hipcc not found: the HIP extension cannot be built on this machine")
     return exe
+
+
+def _dep_headers():
+    """What every object file depends on besides its own source: each header of csrc/ and include/, and this file (the flags)."""
+    inc = os.path.join(HERE, "..", "include")
+    return [os.path.join(d, h) for d in (CSRC, inc) for h in sorted(os.listdir(d)) if h.endswith(".h")] + [os.path.abspath(__file__)]
 
 
 def _newer(src_list, target) -> bool:
@@ -72,8 +77,7 @@ def build_variant(tag: str, defines, verbose: bool = False, force: bool = False)
     out = os.path.join(HERE, f"libgsr_hip_{tag}.so")
     odir = os.path.join(OBJ, tag)
     os.makedirs(odir, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")] + [os.path.abspath(__file__)]
-    headers += [os.path.join(HERE, "..", "include", h) for h in ("gsr.h", "gsr_loss.h", "gsr_knn.h", "gsr_optim.h", "gsr_chamfer.h", "gsr_sequence.h", "gsr_density.h", "gsr_rows.h")]
+    headers = _dep_headers()
     jobs, objs = [], []
     for src, extra in SOURCES.items():
         s, o = os.path.join(CSRC, src), os.path.join(odir, src.replace(".hip", ".o"))
@@ -100,16 +104,7 @@ def build_debug_bounds(force: bool = False, verbose: bool = False) -> str:
 
 def build_hip(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
-    headers.append(os.path.join(HERE, "..", "include", "gsr.h"))
-    headers.append(os.path.join(HERE, "..", "include", "gsr_loss.h"))
-    headers.append(os.path.join(HERE, "..", "include", "gsr_knn.h"))
-    headers.append(os.path.join(HERE, "..", "include", "gsr_optim.h"))
-    headers.append(os.path.join(HERE, "..", "include", "gsr_chamfer.h"))
-    headers.append(os.path.join(HERE, "..", "include", "gsr_sequence.h"))
-    headers.append(os.path.join(HERE, "..", "include", "gsr_density.h"))
-    headers.append(os.path.join(HERE, "..", "include", "gsr_rows.h"))
-    headers.append(os.path.abspath(__file__))
+    headers = _dep_headers()
     cc = hipcc()
     jobs = []
     for src, extra in SOURCES.items():

@@ -1,13 +1,13 @@
 // adam.hip -- one launch for the Adam step of all parameter groups (include/gsr_optim.h).  Pure streaming:
 // 16 bytes read + 12 written per element, float4 wide where the group's length and pointers allow.
 // Below it the visibility-masked step (gsr_adam_step_masked): the same update through the same adam_one, on the visible rows only.
+// Both entry points are at the end of the file.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/gsr_optim.h"
+#include "gsr_host.h"
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
     }
 }
 
-hipError_t launch_adam(int n_groups, const gsr_adam_group_t *groups, double beta1, double beta2, double eps, hipStream_t s) {
+static hipError_t launch_adam(int n_groups, const gsr_adam_group_t *groups, double beta1, double beta2, double eps, hipStream_t s) {
     AdamArgs a;
     a.n_groups = 0; a.beta2 = (float)beta2; a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps;
     unsigned blocks = 0;
@@ -203,38 +203,45 @@ __global__ __launch_bounds__(256) void adam_masked_kernel(AdamMaskedArgs A) {
 
 }  // namespace gsr
 
-// gsr_last_error() hands out this thread's message buffer (gsr_api.hip: 512 bytes); the text goes there as every entry point's does.
-static int adam_fail(int code, const char *fmt, ...) {
-    char *buf = const_cast<char *>(gsr_last_error());
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, 256, fmt, ap);
-    va_end(ap);
-    return code;
-}
+using namespace gsr;
 
-extern "C" int32_t gsr_adam_step_masked(gsr_stream_t stream, int32_t n_groups, const gsr_adam_group_t *groups, double beta1, double beta2,
-                                        double eps, int32_t P, const void *mask, int32_t mask_kind) {
-    using namespace gsr;
-    const char *const who = "gsr_adam_step_masked";
-    if (n_groups < 1 || n_groups > GSR_ADAM_MAX_GROUPS || !groups)
-        return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: %d groups (1 to %d)", who, n_groups, GSR_ADAM_MAX_GROUPS);
-    if (P < 0) return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P=%d is negative", who, P);
-    if (mask_kind != GSR_ADAM_MASK_BYTES && mask_kind != GSR_ADAM_MASK_RADII)
-        return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: unknown mask_kind %d", who, mask_kind);
-    if (P > 0 && !mask) return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: mask is NULL with P=%d", who, P);
-    if (mask_kind == GSR_ADAM_MASK_RADII && ((uintptr_t)mask & 3))
-        return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: an int32 mask must be 4-byte aligned", who);
+extern "C" {
+
+// ---- Adam step over all parameter groups (include/gsr_optim.h) ----
+int32_t gsr_adam_step(gsr_stream_t stream, int32_t n_groups, const gsr_adam_group_t *groups, double beta1, double beta2, double eps) {
+    if (n_groups < 0 || n_groups > GSR_ADAM_MAX_GROUPS || (n_groups > 0 && !groups))
+        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_adam_step: %d groups (at most %d)", n_groups, GSR_ADAM_MAX_GROUPS);
     for (int k = 0; k < n_groups; k++) {
         const gsr_adam_group_t &g = groups[k];
-        if (g.n < 0 || g.n > 0x7fffffffLL) return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: n=%lld not in 0..2^31-1", who, k, (long long)g.n);
-        if (g.n > 0 && (P == 0 || g.n % P != 0))
-            return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: n=%lld is not a multiple of P=%d", who, k, (long long)g.n, P);
-        if (g.n > 0 && (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq))
-            return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: a NULL buffer with n=%lld", who, k, (long long)g.n);
-        if (g.step < 1) return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: step=%d", who, k, g.step);
+        if (g.n < 0 || (g.n > 0 && (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq)) || g.step < 1)
+            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_adam_step: group %d: n=%lld step=%d or a NULL buffer", k, (long long)g.n, g.step);
     }
-    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return adam_fail(GSR_ERR_INVALID_ARGUMENT, "%s: betas", who);
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_adam_step: betas");
+    HIP_TRY(launch_adam(n_groups, groups, beta1, beta2, eps, (hipStream_t)stream), "adam launch");
+    return GSR_OK;
+}
+
+int32_t gsr_adam_step_masked(gsr_stream_t stream, int32_t n_groups, const gsr_adam_group_t *groups, double beta1, double beta2,
+                             double eps, int32_t P, const void *mask, int32_t mask_kind) {
+    const char *const who = "gsr_adam_step_masked";
+    if (n_groups < 1 || n_groups > GSR_ADAM_MAX_GROUPS || !groups)
+        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: %d groups (1 to %d)", who, n_groups, GSR_ADAM_MAX_GROUPS);
+    if (P < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: P=%d is negative", who, P);
+    if (mask_kind != GSR_ADAM_MASK_BYTES && mask_kind != GSR_ADAM_MASK_RADII)
+        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: unknown mask_kind %d", who, mask_kind);
+    if (P > 0 && !mask) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: mask is NULL with P=%d", who, P);
+    if (mask_kind == GSR_ADAM_MASK_RADII && ((uintptr_t)mask & 3))
+        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: an int32 mask must be 4-byte aligned", who);
+    for (int k = 0; k < n_groups; k++) {
+        const gsr_adam_group_t &g = groups[k];
+        if (g.n < 0 || g.n > 0x7fffffffLL) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: n=%lld not in 0..2^31-1", who, k, (long long)g.n);
+        if (g.n > 0 && (P == 0 || g.n % P != 0))
+            return fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: n=%lld is not a multiple of P=%d", who, k, (long long)g.n, P);
+        if (g.n > 0 && (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq))
+            return fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: a NULL buffer with n=%lld", who, k, (long long)g.n);
+        if (g.step < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: step=%d", who, k, g.step);
+    }
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: betas", who);
 
     AdamMaskedArgs A;
     AdamArgs &a = A.a;
@@ -263,6 +270,8 @@ extern "C" int32_t gsr_adam_step_masked(gsr_stream_t stream, int32_t n_groups, c
     else
         hipLaunchKernelGGL(adam_masked_kernel<GSR_ADAM_MASK_BYTES>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, A);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return adam_fail(GSR_ERR_HIP, "masked adam launch: %s (%d)", hipGetErrorString(e), (int)e);
+    if (e != hipSuccess) return fail(GSR_ERR_HIP, "masked adam launch: %s (%d)", hipGetErrorString(e), (int)e);
     return GSR_OK;
 }
+
+}  // extern "C"

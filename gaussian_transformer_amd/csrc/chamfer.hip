@@ -14,6 +14,8 @@
 // breaks the (D + 3) ulp bound the tests assert -- so there is no MFMA formulation.
 #include <stdint.h>
 
+#include "../../include/gsr_chamfer.h"
+#include "gsr_host.h"
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -128,7 +130,7 @@ static hipError_t launch_fwd_t(const ChamferFwdArgs &a, int nchunk, hipStream_t 
 }
 
 // B, N, M >= 1 and 1 <= D <= 64 (checked by gsr_chamfer_forward); ws holds 8 B (N + M) bytes
-hipError_t launch_chamfer_forward(int B, int N, int M, int D, const float *x1, const float *x2, float *dist1, float *dist2,
+static hipError_t launch_chamfer_forward(int B, int N, int M, int D, const float *x1, const float *x2, float *dist1, float *dist2,
                                   int32_t *idx1, int32_t *idx2, void *ws, hipStream_t s) {
     const size_t nkeys = (size_t)B * ((size_t)N + (size_t)M);
     hipError_t e = hipMemsetAsync(ws, 0xff, nkeys * 8, s);
@@ -220,7 +222,7 @@ __global__ __launch_bounds__(256) void chamfer_bwd_scatter_kernel(ChamferBwdArgs
 
 static unsigned grid_for(size_t n) { const size_t b = (n + 255) / 256; return (unsigned)(b < 8192 ? b : 8192); }
 
-hipError_t launch_chamfer_backward(int B, int N, int M, int D, const float *x1, const float *x2, const int32_t *idx1, const int32_t *idx2,
+static hipError_t launch_chamfer_backward(int B, int N, int M, int D, const float *x1, const float *x2, const int32_t *idx1, const int32_t *idx2,
                                    const float *g1, const float *g2, float *dx1, float *dx2, hipStream_t s) {
     ChamferBwdArgs a;
     a.B = B; a.N = N; a.M = M; a.D = D; a.x1 = x1; a.x2 = x2; a.idx1 = idx1; a.idx2 = idx2; a.g1 = g1; a.g2 = g2; a.dx1 = dx1; a.dx2 = dx2;
@@ -237,3 +239,46 @@ hipError_t launch_chamfer_backward(int B, int N, int M, int D, const float *x1, 
 }
 
 }  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+// ---- chamfer_distance.ChamferDistance equivalent (include/gsr_chamfer.h) ----
+// 0: nothing to do, 1: work, < 0: invalid (message set)
+static int chamfer_sizes(const char *who, int32_t B, int32_t N, int32_t M, int32_t D) {
+    if (B < 0 || N < 0 || M < 0) { fail(GSR_ERR_INVALID_ARGUMENT, "%s: negative size (B=%d N=%d M=%d)", who, B, N, M); return -1; }
+    if (D < 1 || D > 64) { fail(GSR_ERR_INVALID_ARGUMENT, "%s: D=%d not in 1..64", who, D); return -1; }
+    if (B == 0 || (N == 0 && M == 0)) return 0;
+    if (N == 0 || M == 0) { fail(GSR_ERR_INVALID_ARGUMENT, "%s: N=%d, M=%d: an empty set has no nearest neighbour", who, N, M); return -1; }
+    if (((long long)(N > M ? N : M) + 511) / 512 * B > 0x7fffffffLL) { fail(GSR_ERR_INVALID_ARGUMENT, "%s: B * max(N, M) too large", who); return -1; }
+    return 1;
+}
+
+int32_t gsr_chamfer_workspace(int32_t B, int32_t N, int32_t M, size_t *bytes) {
+    if (B < 0 || N < 0 || M < 0 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_chamfer_workspace: bad argument");
+    *bytes = (size_t)8 * (size_t)B * ((size_t)N + (size_t)M);
+    return GSR_OK;
+}
+
+int32_t gsr_chamfer_forward(gsr_stream_t stream, int32_t B, int32_t N, int32_t M, int32_t D, const float *x1, const float *x2,
+                            float *dist1, float *dist2, int32_t *idx1, int32_t *idx2, void *ws, size_t ws_bytes) {
+    const int k = chamfer_sizes("gsr_chamfer_forward", B, N, M, D);
+    if (k <= 0) return k < 0 ? GSR_ERR_INVALID_ARGUMENT : GSR_OK;
+    if (!x1 || !x2 || !dist1 || !dist2 || !idx1 || !idx2 || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_chamfer_forward: null pointer");
+    const size_t need = (size_t)8 * (size_t)B * ((size_t)N + (size_t)M);
+    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "chamfer workspace %zu < %zu", ws_bytes, need);
+    HIP_TRY(launch_chamfer_forward(B, N, M, D, x1, x2, dist1, dist2, idx1, idx2, ws, (hipStream_t)stream), "chamfer forward launch");
+    return GSR_OK;
+}
+
+int32_t gsr_chamfer_backward(gsr_stream_t stream, int32_t B, int32_t N, int32_t M, int32_t D, const float *x1, const float *x2,
+                             const int32_t *idx1, const int32_t *idx2, const float *g1, const float *g2, float *dx1, float *dx2) {
+    const int k = chamfer_sizes("gsr_chamfer_backward", B, N, M, D);
+    if (k <= 0) return k < 0 ? GSR_ERR_INVALID_ARGUMENT : GSR_OK;
+    if (!x1 || !x2 || !idx1 || !idx2) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_chamfer_backward: null pointer");
+    HIP_TRY(launch_chamfer_backward(B, N, M, D, x1, x2, idx1, idx2, g1, g2, dx1, dx2, (hipStream_t)stream), "chamfer backward launch");
+    return GSR_OK;
+}
+
+}  // extern "C"

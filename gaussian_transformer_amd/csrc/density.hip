@@ -11,6 +11,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/gsr_density.h"
+#include "gsr_host.h"
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -32,7 +33,7 @@ __global__ __launch_bounds__(256) void density_record_kernel(int P, const float 
     max_radii[i] = rf > m ? rf : m;
 }
 
-hipError_t launch_density_record(int P, const float *grad2d, int stride, const int32_t *radii, const uint8_t *visible, float *accum,
+static hipError_t launch_density_record(int P, const float *grad2d, int stride, const int32_t *radii, const uint8_t *visible, float *accum,
                                  float *denom, float *max_radii, hipStream_t s) {
     hipLaunchKernelGGL(density_record_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, grad2d, stride, radii, visible, accum, denom, max_radii);
     return hipGetLastError();
@@ -80,7 +81,7 @@ static hipError_t carve_plan_ws(void *base, int P, int N, PlanWs &w) {
     return hipSuccess;
 }
 
-hipError_t densify_plan_workspace_bytes(int P, int N, size_t *bytes) {
+static hipError_t densify_plan_workspace_bytes(int P, int N, size_t *bytes) {
     PlanWs w;
     hipError_t e = carve_plan_ws(nullptr, P, N, w);
     if (e == hipSuccess) *bytes = w.total;
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(256) void densify_map_kernel(int P, int N, const ui
 }
 
 // sizes validated by the caller; P >= 1
-hipError_t launch_densify_plan(int P, const float *opacity, const float *scaling, const float *accum, const float *denom, float grad_threshold,
+static hipError_t launch_densify_plan(int P, const float *opacity, const float *scaling, const float *accum, const float *denom, float grad_threshold,
                                float min_opacity, float cut, float prune_world, int N, uint32_t *counts_host, void *ws, hipStream_t s) {
     PlanWs w;
     hipError_t e = carve_plan_ws(ws, P, N, w);
@@ -266,7 +267,7 @@ __global__ __launch_bounds__(256) void densify_apply_kernel(ApplyArgs a) {
 }
 
 // sizes, pointers and roles validated by the caller; P >= 1, p_new >= 1
-hipError_t launch_densify_apply(int P, int N, uint32_t n_split, uint32_t p_new, int n_groups, const gsr_density_group_t *groups,
+static hipError_t launch_densify_apply(int P, int N, uint32_t n_split, uint32_t p_new, int n_groups, const gsr_density_group_t *groups,
                                 const float *scaling, const float *rotation, const float *noise, const void *ws, hipStream_t s) {
     PlanWs w;
     hipError_t e = carve_plan_ws(const_cast<void *>(ws), P, N, w);
@@ -294,3 +295,88 @@ hipError_t launch_densify_apply(int P, int N, uint32_t n_split, uint32_t p_new, 
 }
 
 }  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+// ---- density control on the device (include/gsr_density.h) ----
+int32_t gsr_density_record(gsr_stream_t stream, int32_t P, const float *grad2d, int32_t grad_stride_floats, const int32_t *radii,
+                           const uint8_t *visible, float *accum, float *denom, float *max_radii) {
+    if (P < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_density_record: P=%d is negative", P);
+    if (P == 0) return GSR_OK;
+    if (grad_stride_floats < 2) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_density_record: grad_stride_floats=%d, at least 2", grad_stride_floats);
+    if (!grad2d || !radii || !accum || !denom || !max_radii) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_density_record: null pointer");
+    HIP_TRY(launch_density_record(P, grad2d, grad_stride_floats, radii, visible, accum, denom, max_radii, (hipStream_t)stream), "density record launch");
+    return GSR_OK;
+}
+
+static int densify_sizes(const char *who, int32_t P, int32_t N) {
+    if (P < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: P=%d is negative", who, P);
+    if (N < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: N=%d, at least 1", who, N);
+    if ((long long)P * ((long long)N + 1) > 0x7fffffffLL)
+        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: P * (N + 1) = %lld, must stay below 2^31", who, (long long)P * ((long long)N + 1));
+    return GSR_OK;
+}
+
+int32_t gsr_densify_plan_workspace(int32_t P, int32_t N, size_t *bytes) {
+    if (!bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_plan_workspace: bytes is NULL");
+    if (densify_sizes("gsr_densify_plan_workspace", P, N) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
+    HIP_TRY(densify_plan_workspace_bytes(P, N, bytes), "densify workspace size");
+    return GSR_OK;
+}
+
+int32_t gsr_densify_plan(gsr_stream_t stream, int32_t P, const float *opacity, const float *scaling, const float *accum, const float *denom,
+                         float grad_threshold, float min_opacity, float cut, float prune_world_size, int32_t N, uint32_t *counts_host, void *ws,
+                         size_t ws_bytes) {
+    if (densify_sizes("gsr_densify_plan", P, N) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
+    if (!counts_host) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_plan: counts_host is NULL");
+    if (!(grad_threshold > 0.f)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_plan: grad_threshold=%g, must be > 0", (double)grad_threshold);
+    if (P == 0) {
+        counts_host[0] = counts_host[1] = counts_host[2] = counts_host[3] = 0;
+        return GSR_OK;
+    }
+    if (!opacity || !scaling || !accum || !denom || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_plan: null pointer");
+    size_t need = 0;
+    HIP_TRY(densify_plan_workspace_bytes(P, N, &need), "densify workspace size");
+    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "densify workspace %zu < %zu", ws_bytes, need);
+    HIP_TRY(launch_densify_plan(P, opacity, scaling, accum, denom, grad_threshold, min_opacity, cut, prune_world_size, N, counts_host, ws,
+                                (hipStream_t)stream), "densify plan launch");
+    return GSR_OK;
+}
+
+int32_t gsr_densify_apply(gsr_stream_t stream, int32_t P, int32_t N, int32_t n_split, int32_t P_new, int32_t n_groups,
+                          const gsr_density_group_t *groups, const float *scaling, const float *rotation, const float *noise, const void *ws,
+                          size_t ws_bytes) {
+    if (densify_sizes("gsr_densify_apply", P, N) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
+    if (n_groups < 0 || n_groups > GSR_DENSITY_MAX_GROUPS || (n_groups > 0 && !groups))
+        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: %d groups (at most %d)", n_groups, GSR_DENSITY_MAX_GROUPS);
+    if (n_split < 0 || n_split > P || P_new < 0 || (long long)P_new > (long long)P * ((long long)N + 1))
+        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: n_split=%d P_new=%d do not belong to a plan of P=%d N=%d", n_split, P_new, P, N);
+    if (P == 0 || P_new == 0) return GSR_OK;
+    if (!ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: null pointer (ws)");
+    size_t need = 0;
+    HIP_TRY(densify_plan_workspace_bytes(P, N, &need), "densify workspace size");
+    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "densify workspace %zu < %zu", ws_bytes, need);
+    for (int k = 0; k < n_groups; k++) {
+        const gsr_density_group_t &g = groups[k];
+        if (g.width_floats < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: width %d", k, g.width_floats);
+        if (g.width_floats == 0) continue;
+        if ((unsigned long long)P_new * (unsigned long long)g.width_floats > 0xffffffffULL)
+            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: P_new * width must stay below 2^32", k);
+        if (!g.src || !g.dst || g.src == g.dst) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: src / dst NULL or equal", k);
+        const int nm = (g.src_exp_avg != nullptr) + (g.src_exp_avg_sq != nullptr) + (g.dst_exp_avg != nullptr) + (g.dst_exp_avg_sq != nullptr);
+        if (nm != 0 && nm != 4) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: the four moment pointers must all be given or all be NULL", k);
+        if (g.role != GSR_DENSITY_COPY && g.role != GSR_DENSITY_XYZ && g.role != GSR_DENSITY_SCALING)
+            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: role %d", k, g.role);
+        if (g.role != GSR_DENSITY_COPY && g.width_floats != 3)
+            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: role %d needs width 3, got %d", k, g.role, g.width_floats);
+        if (g.role == GSR_DENSITY_XYZ && n_split > 0 && (!scaling || !rotation || !noise))
+            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: the xyz role needs scaling, rotation and noise", k);
+    }
+    HIP_TRY(launch_densify_apply(P, N, (uint32_t)n_split, (uint32_t)P_new, n_groups, groups, scaling, rotation, noise, ws, (hipStream_t)stream),
+            "densify apply launch");
+    return GSR_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,7 @@
-// gsr_api.hip -- the C ABI of libgsr_hip.so (include/gsr.h): argument validation, workspace
-// carving, stage sequencing on the caller's stream, error reporting.  Host code only.
+// gsr_api.hip -- the entry points of include/gsr.h: argument validation, workspace carving, stage sequencing on the caller's
+// stream, options, and the library's one error path (gsr_host.h: fail() and the message buffer gsr_last_error() returns).
+// Host code only.  The entry points of every other header (gsr_loss.h, gsr_optim.h, gsr_density.h, gsr_knn.h, gsr_chamfer.h,
+// gsr_sequence.h, gsr_rows.h) live in the translation unit that holds their kernels.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -11,20 +13,12 @@
 #include <ctime>
 
 #include "../../include/gsr.h"
-#include "../../include/gsr_chamfer.h"
-#include "../../include/gsr_density.h"
-#include "../../include/gsr_knn.h"
-#include "../../include/gsr_loss.h"
-#include "../../include/gsr_optim.h"
-#include "../../include/gsr_sequence.h"
+#include "gsr_host.h"
 #include "gsr_internal.h"
 
 namespace gsr {
-hipError_t launch_densify_apply(int P, int N, uint32_t n_split, uint32_t p_new, int n_groups, const gsr_density_group_t *groups, const float *scaling,
-                                const float *rotation, const float *noise, const void *ws, hipStream_t s);   // density.hip
-hipError_t launch_adam(int n_groups, const gsr_adam_group_t *groups, double beta1, double beta2, double eps, hipStream_t s);   // adam.hip
 
-static thread_local char g_err[512] = "";
+static thread_local char g_err[GSR_ERR_TEXT_BYTES] = "";
 // process-wide (not thread-local): PyTorch's autograd engine calls gsr_backward from its own thread
 static std::atomic<int> g_profiling{0};
 static std::atomic<int> g_exact_cull{1};       // output-invariant exact splat-vs-tile culling
@@ -132,18 +126,13 @@ static const char *const k_stage_names[GSR_NUM_STAGES] = {
     "fwd.preprocess", "fwd.lists.bin", "fwd.readback_N", "fwd.lists.emit_keys", "fwd.lists.order", "fwd.lists.ranges", "(unused)",
     "fwd.composite", "bwd.clear+plan", "bwd.composite", "bwd.pergauss", "fwd.total", "bwd.total"};
 
-static int fail(int code, const char *fmt, ...) {
+int fail(int code, const char *fmt, ...) {      // gsr_host.h: every entry point of every translation unit reports through this
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
 }
-#define HIP_TRY(expr, what)                                                                              \
-    do {                                                                                                 \
-        hipError_t _e = (expr);                                                                          \
-        if (_e != hipSuccess) return fail(GSR_ERR_HIP, "%s: %s (%d)", what, hipGetErrorString(_e), (int)_e); \
-    } while (0)
 
 GeomView carve_geom(void *base, int P, size_t scan_tb, size_t dsort_tb) {
     GeomView g;
@@ -366,81 +355,59 @@ extern "C" {
 int32_t gsr_abi_version(void) { return GSR_ABI_VERSION; }
 const char *gsr_last_error(void) { return g_err; }
 
+// ---- options: one row per regular knob, walked by gsr_set_option and gsr_get_option alike; the irregular ones (per device, remapped,
+// clamped, set-only, read-only) are explicit cases in the two functions.  include/gsr.h documents every name. ----
+enum OptRule { OPT_BOOL, OPT_RANGE, OPT_1_2_4, OPT_MULT_64 };     // any value -> 0 / 1; lo..hi; 1, 2 or 4; 0 or a multiple of 64 up to hi
+struct OptRow { const char *name; std::atomic<int> *var; OptRule rule; int lo, hi; const char *must; };
+static const OptRow k_options[] = {
+    {"exact_tile_cull", &g_exact_cull, OPT_BOOL, 0, 1, nullptr},
+    {"two_level_sort", &g_two_level_sort, OPT_BOOL, 0, 1, nullptr},
+    {"deterministic_bwd", &g_deterministic_bwd, OPT_BOOL, 0, 1, nullptr},
+    {"fill_in_tail", &g_fill_in_tail, OPT_BOOL, 0, 1, nullptr},
+    {"asm_walk", &g_asm_walk, OPT_BOOL, 0, 1, nullptr},
+    {"bwd_lpt", &g_bwd_lpt, OPT_BOOL, 0, 1, nullptr},
+    {"tile_lists", &g_tile_lists, OPT_RANGE, 0, 2, "0, 1 or 2"},
+    {"persistent_bwd", &g_persistent_bwd, OPT_RANGE, 0, 2, "0, 1 or 2"},
+    {"prefill_at", &g_prefill_at, OPT_RANGE, 0, 2, "0, 1 or 2"},
+    {"dense_fork", &g_dense_fork, OPT_RANGE, 0, 2, "0, 1 or 2"},
+    {"dense_pergauss", &g_dense_pergauss, OPT_RANGE, 0, 2, "0, 1 or 2"},
+    {"depth_buckets", &g_depth_buckets, OPT_RANGE, 0, 2, "0, 1 or 2"},
+    {"composite_waves_per_block", &g_wpb, OPT_1_2_4, 1, 4, "1, 2 or 4"},
+    {"fwd_blocks_per_wave", &g_fwd_npx, OPT_1_2_4, 1, 4, "1, 2 or 4"},
+    {"bwd_blocks_per_wave", &g_bwd_npx, OPT_1_2_4, 1, 4, "1, 2 or 4"},
+    {"segment_entries", &g_seg_len, OPT_MULT_64, 0, 65536, "0 or a multiple of 64 up to 65536"},
+};
+static const OptRow *find_option(const char *name) {
+    for (const OptRow &o : k_options) if (name && !strcmp(name, o.name)) return &o;
+    return nullptr;
+}
+static bool option_accepts(const OptRow &o, int v) {
+    if (o.rule == OPT_BOOL) return true;
+    if (v < o.lo || v > o.hi) return false;
+    return o.rule == OPT_1_2_4 ? v != 3 : o.rule == OPT_MULT_64 ? !(v & 63) : true;
+}
+
 int32_t gsr_set_option(const char *name, int32_t value) {
-    if (name && !strcmp(name, "exact_tile_cull")) { g_exact_cull.store(value ? 1 : 0); return GSR_OK; }
-    if (name && !strcmp(name, "two_level_sort")) { g_two_level_sort.store(value ? 1 : 0); return GSR_OK; }
-    if (name && !strcmp(name, "tile_lists")) {
-        if (value < 0 || value > 2) return fail(GSR_ERR_INVALID_ARGUMENT, "tile_lists must be 0, 1 or 2");
-        g_tile_lists.store(value); return GSR_OK;
+    if (const OptRow *o = find_option(name)) {
+        if (!option_accepts(*o, value)) return fail(GSR_ERR_INVALID_ARGUMENT, "%s must be %s", o->name, o->must);
+        o->var->store(o->rule == OPT_BOOL ? (value ? 1 : 0) : value);
+        return GSR_OK;
     }
     if (name && !strcmp(name, "depth_log_map")) { DeviceState &ds = dev_state(); ds.depth_log_map.store(value ? 1 : 0); ds.bucket_fail_p.store(0x7fffffff); return GSR_OK; }
     if (name && !strcmp(name, "count_lanes")) { g_count_lanes.store(value == 2 ? 2 : (value ? 1 : 0)); return GSR_OK; }
-    if (name && !strcmp(name, "composite_lds_pad")) { g_composite_lds_pad = value < 0 ? 0 : value; return GSR_OK; }
-    if (name && !strcmp(name, "deterministic_bwd")) { g_deterministic_bwd.store(value ? 1 : 0); return GSR_OK; }
-    if (name && !strcmp(name, "persistent_bwd")) {
-        if (value < 0 || value > 2) return fail(GSR_ERR_INVALID_ARGUMENT, "persistent_bwd must be 0, 1 or 2");
-        g_persistent_bwd.store(value); return GSR_OK;
-    }
-    if (name && !strcmp(name, "fill_in_tail")) { g_fill_in_tail.store(value ? 1 : 0); return GSR_OK; }
-    if (name && !strcmp(name, "asm_walk")) { g_asm_walk.store(value ? 1 : 0); return GSR_OK; }
-    if (name && !strcmp(name, "bwd_lpt")) { g_bwd_lpt.store(value ? 1 : 0); return GSR_OK; }
+    if (name && !strcmp(name, "composite_lds_pad")) { g_composite_lds_pad = value < 0 ? 0 : value; return GSR_OK; }     // set-only
     if (name && !strcmp(name, "fwd_pair_long")) { g_fwd_pair_long.store(value < -1 ? -1 : value); return GSR_OK; }
-    if (name && !strcmp(name, "prefill_at")) {
-        if (value < 0 || value > 2) return fail(GSR_ERR_INVALID_ARGUMENT, "prefill_at must be 0, 1 or 2");
-        g_prefill_at.store(value); return GSR_OK;
-    }
-    if (name && !strcmp(name, "dense_fork")) {
-        if (value < 0 || value > 2) return fail(GSR_ERR_INVALID_ARGUMENT, "dense_fork must be 0, 1 or 2");
-        g_dense_fork.store(value); return GSR_OK;
-    }
-    if (name && !strcmp(name, "dense_pergauss")) {
-        if (value < 0 || value > 2) return fail(GSR_ERR_INVALID_ARGUMENT, "dense_pergauss must be 0, 1 or 2");
-        g_dense_pergauss.store(value); return GSR_OK;
-    }
-    if (name && !strcmp(name, "segment_entries")) {
-        if (value < 0 || value > 65536 || (value & 63)) return fail(GSR_ERR_INVALID_ARGUMENT, "segment_entries must be 0 or a multiple of 64 up to 65536");
-        g_seg_len.store(value); return GSR_OK;
-    }
-    if (name && !strcmp(name, "depth_buckets")) {
-        if (value < 0 || value > 2) return fail(GSR_ERR_INVALID_ARGUMENT, "depth_buckets must be 0, 1 or 2");
-        g_depth_buckets.store(value); return GSR_OK;
-    }
-    if (name && !strcmp(name, "composite_waves_per_block")) {
-        if (value != 1 && value != 2 && value != 4) return fail(GSR_ERR_INVALID_ARGUMENT, "composite_waves_per_block must be 1, 2 or 4");
-        g_wpb.store(value); return GSR_OK;
-    }
-    if (name && !strcmp(name, "fwd_blocks_per_wave")) {
-        if (value != 1 && value != 2 && value != 4) return fail(GSR_ERR_INVALID_ARGUMENT, "fwd_blocks_per_wave must be 1, 2 or 4");
-        g_fwd_npx.store(value); return GSR_OK;
-    }
-    if (name && !strcmp(name, "bwd_blocks_per_wave")) {
-        if (value != 1 && value != 2 && value != 4) return fail(GSR_ERR_INVALID_ARGUMENT, "bwd_blocks_per_wave must be 1, 2 or 4");
-        g_bwd_npx.store(value); return GSR_OK;
-    }
     return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_set_option: unknown option '%s'", name ? name : "(null)");
 }
 int32_t gsr_get_option(const char *name, int32_t *value) {
-    if (name && value && !strcmp(name, "exact_tile_cull")) { *value = g_exact_cull.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "bwd_blocks_per_wave")) { *value = g_bwd_npx.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "fwd_blocks_per_wave")) { *value = g_fwd_npx.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "two_level_sort")) { *value = g_two_level_sort.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "tile_lists")) { *value = g_tile_lists.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "depth_log_map")) { *value = dev_state().depth_log_map.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "count_lanes")) { *value = g_count_lanes.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "deterministic_bwd")) { *value = g_deterministic_bwd.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "persistent_bwd")) { *value = g_persistent_bwd.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "segment_entries")) { *value = g_seg_len.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "fill_in_tail")) { *value = g_fill_in_tail.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "asm_walk")) { *value = g_asm_walk.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "bwd_lpt")) { *value = g_bwd_lpt.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "fwd_pair_long")) { *value = g_fwd_pair_long.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "prefill_at")) { *value = g_prefill_at.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "dense_fork")) { *value = g_dense_fork.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "dense_pergauss")) { *value = g_dense_pergauss.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "pergauss_path")) { *value = pergauss_last_path(); return GSR_OK; }
-    if (name && value && !strcmp(name, "poll_timeouts")) { *value = dev_state().poll_timeouts.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "depth_buckets")) { *value = g_depth_buckets.load(); return GSR_OK; }
-    if (name && value && !strcmp(name, "composite_waves_per_block")) { *value = g_wpb.load(); return GSR_OK; }
+    if (name && value) {
+        if (const OptRow *o = find_option(name)) { *value = o->var->load(); return GSR_OK; }
+        if (!strcmp(name, "depth_log_map")) { *value = dev_state().depth_log_map.load(); return GSR_OK; }
+        if (!strcmp(name, "count_lanes")) { *value = g_count_lanes.load(); return GSR_OK; }
+        if (!strcmp(name, "fwd_pair_long")) { *value = g_fwd_pair_long.load(); return GSR_OK; }
+        if (!strcmp(name, "pergauss_path")) { *value = pergauss_last_path(); return GSR_OK; }                          // read-only
+        if (!strcmp(name, "poll_timeouts")) { *value = dev_state().poll_timeouts.load(); return GSR_OK; }              // read-only
+    }
     return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_get_option: unknown option '%s'", name ? name : "(null)");
 }
 
@@ -917,291 +884,6 @@ int32_t gsr_backward(gsr_stream_t stream, int32_t P, int32_t D, int32_t M, int64
     if (debug) HIP_TRY(hipStreamSynchronize(s), "per-Gaussian backward");
     tm.mark(-1);
     tm.finish(12);
-    return GSR_OK;
-}
-
-// ---- fused training loss (include/gsr_loss.h) ----
-static inline size_t loss_blocks(int C, int H, int W) { return (size_t)((W + 15) / 16) * ((H + 15) / 16) * C; }
-
-int32_t gsr_l1_ssim_workspace(int32_t C, int32_t H, int32_t W, size_t *bytes) {
-    if (C <= 0 || H <= 0 || W <= 0 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_l1_ssim_workspace: bad argument");
-    *bytes = align_up((size_t)3 * C * H * W * sizeof(float)) + align_up(loss_blocks(C, H, W) * 2 * sizeof(float));
-    return GSR_OK;
-}
-
-int32_t gsr_l1_ssim_forward(gsr_stream_t stream, int32_t C, int32_t H, int32_t W, const float *img, const float *gt,
-                            float lambda_dssim, float *out3, void *ws, size_t ws_bytes) {
-    size_t need = 0;
-    if (gsr_l1_ssim_workspace(C, H, W, &need) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
-    if (!img || !gt || !out3 || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_l1_ssim_forward: null pointer");
-    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "loss workspace %zu < %zu", ws_bytes, need);
-    float *dmaps = (float *)ws;
-    float *partial = (float *)((char *)ws + align_up((size_t)3 * C * H * W * sizeof(float)));
-    HIP_TRY(launch_l1_ssim_forward(C, H, W, img, gt, lambda_dssim, dmaps, partial, out3, (hipStream_t)stream), "l1+ssim forward launch");
-    return GSR_OK;
-}
-
-int32_t gsr_l1_ssim_backward(gsr_stream_t stream, int32_t C, int32_t H, int32_t W, const float *img, const float *gt,
-                             float lambda_dssim, const float *grad_loss, const void *ws, size_t ws_bytes, float *grad_img) {
-    size_t need = 0;
-    if (gsr_l1_ssim_workspace(C, H, W, &need) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
-    if (!img || !gt || !ws || !grad_img) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_l1_ssim_backward: null pointer");
-    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "loss workspace %zu < %zu", ws_bytes, need);
-    HIP_TRY(launch_l1_ssim_backward(C, H, W, img, gt, lambda_dssim, (const float *)ws, grad_loss, grad_img, (hipStream_t)stream),
-            "l1+ssim backward launch");
-    return GSR_OK;
-}
-
-// ---- the same loss over B views (include/gsr_loss.h) ----
-static_assert(GSR_VIEWS_MAX_B == GSR_VIEWS_LOSS_MAX_B, "per-launch view limit of ssim_loss.hip and gsr_loss.h");
-// 0 = ok; everything the forward and the backward check alike, before anything is launched
-static int views_loss_check(const char *who, int32_t B, int32_t H, int32_t W, const float *const *imgs, const float *const *gts,
-                            const void *ws, size_t ws_bytes) {
-    size_t need = 0;
-    if (gsr_views_loss_workspace(B, H, W, &need) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
-    if (!imgs || !gts || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: null pointer (imgs, gts or workspace)", who);
-    for (int b = 0; b < B; b++)
-        if (!imgs[b] || !gts[b]) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: view %d: null %s pointer", who, b, imgs[b] ? "target" : "image");
-    if (ws_bytes < need) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: workspace %zu < %zu", who, ws_bytes, need);
-    return GSR_OK;
-}
-
-int32_t gsr_views_loss_workspace(int32_t B, int32_t H, int32_t W, size_t *bytes) {
-    if (B < 1 || H < 1 || W < 1 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_workspace: bad argument (B=%d H=%d W=%d)", B, H, W);
-    if ((H + 15) / 16 > 65535 || (size_t)3 * loss_blocks(1, H, W) > (size_t)INT32_MAX)
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_workspace: image %d x %d too large", W, H);
-    *bytes = views_loss_workspace_bytes(B, H, W);
-    return GSR_OK;
-}
-
-int32_t gsr_views_loss_forward(gsr_stream_t stream, int32_t B, int32_t H, int32_t W, const float *const *imgs, const float *const *gts,
-                               float w_l1, float w_ssim, int32_t sanitize, float *out3, float *terms, void *ws, size_t ws_bytes) {
-    const int rc = views_loss_check("gsr_views_loss_forward", B, H, W, imgs, gts, ws, ws_bytes);
-    if (rc != GSR_OK) return rc;
-    if (!out3 || !terms) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_forward: null pointer (out3 or terms)");
-    HIP_TRY(launch_views_loss_forward(B, H, W, imgs, gts, w_l1, w_ssim, sanitize ? 1 : 0, out3, terms, ws, (hipStream_t)stream),
-            "views loss forward launch");
-    return GSR_OK;
-}
-
-int32_t gsr_views_loss_backward(gsr_stream_t stream, int32_t B, int32_t H, int32_t W, const float *const *imgs, const float *const *gts,
-                                float w_l1, float w_ssim, int32_t sanitize, const float *grad_loss, const void *ws, size_t ws_bytes,
-                                float *const *grad_imgs) {
-    const int rc = views_loss_check("gsr_views_loss_backward", B, H, W, imgs, gts, ws, ws_bytes);
-    if (rc != GSR_OK) return rc;
-    if (!grad_imgs) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_backward: null pointer (grad_imgs)");
-    HIP_TRY(launch_views_loss_backward(B, H, W, imgs, gts, w_l1, w_ssim, sanitize ? 1 : 0, grad_loss, ws, grad_imgs, (hipStream_t)stream),
-            "views loss backward launch");
-    return GSR_OK;
-}
-
-// ---- Adam step over all parameter groups (include/gsr_optim.h) ----
-int32_t gsr_adam_step(gsr_stream_t stream, int32_t n_groups, const gsr_adam_group_t *groups, double beta1, double beta2, double eps) {
-    if (n_groups < 0 || n_groups > GSR_ADAM_MAX_GROUPS || (n_groups > 0 && !groups))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_adam_step: %d groups (at most %d)", n_groups, GSR_ADAM_MAX_GROUPS);
-    for (int k = 0; k < n_groups; k++) {
-        const gsr_adam_group_t &g = groups[k];
-        if (g.n < 0 || (g.n > 0 && (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq)) || g.step < 1)
-            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_adam_step: group %d: n=%lld step=%d or a NULL buffer", k, (long long)g.n, g.step);
-    }
-    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_adam_step: betas");
-    HIP_TRY(launch_adam(n_groups, groups, beta1, beta2, eps, (hipStream_t)stream), "adam launch");
-    return GSR_OK;
-}
-
-// ---- density control on the device (include/gsr_density.h) ----
-int32_t gsr_density_record(gsr_stream_t stream, int32_t P, const float *grad2d, int32_t grad_stride_floats, const int32_t *radii,
-                           const uint8_t *visible, float *accum, float *denom, float *max_radii) {
-    if (P < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_density_record: P=%d is negative", P);
-    if (P == 0) return GSR_OK;
-    if (grad_stride_floats < 2) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_density_record: grad_stride_floats=%d, at least 2", grad_stride_floats);
-    if (!grad2d || !radii || !accum || !denom || !max_radii) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_density_record: null pointer");
-    HIP_TRY(launch_density_record(P, grad2d, grad_stride_floats, radii, visible, accum, denom, max_radii, (hipStream_t)stream), "density record launch");
-    return GSR_OK;
-}
-
-static int densify_sizes(const char *who, int32_t P, int32_t N) {
-    if (P < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: P=%d is negative", who, P);
-    if (N < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: N=%d, at least 1", who, N);
-    if ((long long)P * ((long long)N + 1) > 0x7fffffffLL)
-        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: P * (N + 1) = %lld, must stay below 2^31", who, (long long)P * ((long long)N + 1));
-    return GSR_OK;
-}
-
-int32_t gsr_densify_plan_workspace(int32_t P, int32_t N, size_t *bytes) {
-    if (!bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_plan_workspace: bytes is NULL");
-    if (densify_sizes("gsr_densify_plan_workspace", P, N) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
-    HIP_TRY(densify_plan_workspace_bytes(P, N, bytes), "densify workspace size");
-    return GSR_OK;
-}
-
-int32_t gsr_densify_plan(gsr_stream_t stream, int32_t P, const float *opacity, const float *scaling, const float *accum, const float *denom,
-                         float grad_threshold, float min_opacity, float cut, float prune_world_size, int32_t N, uint32_t *counts_host, void *ws,
-                         size_t ws_bytes) {
-    if (densify_sizes("gsr_densify_plan", P, N) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
-    if (!counts_host) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_plan: counts_host is NULL");
-    if (!(grad_threshold > 0.f)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_plan: grad_threshold=%g, must be > 0", (double)grad_threshold);
-    if (P == 0) {
-        counts_host[0] = counts_host[1] = counts_host[2] = counts_host[3] = 0;
-        return GSR_OK;
-    }
-    if (!opacity || !scaling || !accum || !denom || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_plan: null pointer");
-    size_t need = 0;
-    HIP_TRY(densify_plan_workspace_bytes(P, N, &need), "densify workspace size");
-    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "densify workspace %zu < %zu", ws_bytes, need);
-    HIP_TRY(launch_densify_plan(P, opacity, scaling, accum, denom, grad_threshold, min_opacity, cut, prune_world_size, N, counts_host, ws,
-                                (hipStream_t)stream), "densify plan launch");
-    return GSR_OK;
-}
-
-int32_t gsr_densify_apply(gsr_stream_t stream, int32_t P, int32_t N, int32_t n_split, int32_t P_new, int32_t n_groups,
-                          const gsr_density_group_t *groups, const float *scaling, const float *rotation, const float *noise, const void *ws,
-                          size_t ws_bytes) {
-    if (densify_sizes("gsr_densify_apply", P, N) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
-    if (n_groups < 0 || n_groups > GSR_DENSITY_MAX_GROUPS || (n_groups > 0 && !groups))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: %d groups (at most %d)", n_groups, GSR_DENSITY_MAX_GROUPS);
-    if (n_split < 0 || n_split > P || P_new < 0 || (long long)P_new > (long long)P * ((long long)N + 1))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: n_split=%d P_new=%d do not belong to a plan of P=%d N=%d", n_split, P_new, P, N);
-    if (P == 0 || P_new == 0) return GSR_OK;
-    if (!ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: null pointer (ws)");
-    size_t need = 0;
-    HIP_TRY(densify_plan_workspace_bytes(P, N, &need), "densify workspace size");
-    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "densify workspace %zu < %zu", ws_bytes, need);
-    for (int k = 0; k < n_groups; k++) {
-        const gsr_density_group_t &g = groups[k];
-        if (g.width_floats < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: width %d", k, g.width_floats);
-        if (g.width_floats == 0) continue;
-        if ((unsigned long long)P_new * (unsigned long long)g.width_floats > 0xffffffffULL)
-            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: P_new * width must stay below 2^32", k);
-        if (!g.src || !g.dst || g.src == g.dst) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: src / dst NULL or equal", k);
-        const int nm = (g.src_exp_avg != nullptr) + (g.src_exp_avg_sq != nullptr) + (g.dst_exp_avg != nullptr) + (g.dst_exp_avg_sq != nullptr);
-        if (nm != 0 && nm != 4) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: the four moment pointers must all be given or all be NULL", k);
-        if (g.role != GSR_DENSITY_COPY && g.role != GSR_DENSITY_XYZ && g.role != GSR_DENSITY_SCALING)
-            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: role %d", k, g.role);
-        if (g.role != GSR_DENSITY_COPY && g.width_floats != 3)
-            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: role %d needs width 3, got %d", k, g.role, g.width_floats);
-        if (g.role == GSR_DENSITY_XYZ && n_split > 0 && (!scaling || !rotation || !noise))
-            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: the xyz role needs scaling, rotation and noise", k);
-    }
-    HIP_TRY(launch_densify_apply(P, N, (uint32_t)n_split, (uint32_t)P_new, n_groups, groups, scaling, rotation, noise, ws, (hipStream_t)stream),
-            "densify apply launch");
-    return GSR_OK;
-}
-
-// ---- simple_knn.distCUDA2 equivalent (include/gsr_knn.h) ----
-int32_t gsr_knn_workspace(int32_t N, size_t *bytes) {
-    if (N < 0 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_knn_workspace: bad argument");
-    HIP_TRY(knn_workspace_bytes(N, bytes), "knn temp query");
-    return GSR_OK;
-}
-
-int32_t gsr_knn_mean_dist2(gsr_stream_t stream, int32_t N, const float *points, float *mean_dist2, void *ws, size_t ws_bytes) {
-    if (N < 0 || (N > 0 && (!points || !mean_dist2 || !ws))) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_knn_mean_dist2: bad argument");
-    size_t need = 0;
-    HIP_TRY(knn_workspace_bytes(N, &need), "knn temp query");
-    if (N > 0 && ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "knn workspace %zu < %zu", ws_bytes, need);
-    HIP_TRY(launch_knn(N, points, mean_dist2, ws, (hipStream_t)stream), "knn launch");
-    return GSR_OK;
-}
-
-// ---- chamfer_distance.ChamferDistance equivalent (include/gsr_chamfer.h) ----
-// 0: nothing to do, 1: work, < 0: invalid (message set)
-static int chamfer_sizes(const char *who, int32_t B, int32_t N, int32_t M, int32_t D) {
-    if (B < 0 || N < 0 || M < 0) { fail(GSR_ERR_INVALID_ARGUMENT, "%s: negative size (B=%d N=%d M=%d)", who, B, N, M); return -1; }
-    if (D < 1 || D > 64) { fail(GSR_ERR_INVALID_ARGUMENT, "%s: D=%d not in 1..64", who, D); return -1; }
-    if (B == 0 || (N == 0 && M == 0)) return 0;
-    if (N == 0 || M == 0) { fail(GSR_ERR_INVALID_ARGUMENT, "%s: N=%d, M=%d: an empty set has no nearest neighbour", who, N, M); return -1; }
-    if (((long long)(N > M ? N : M) + 511) / 512 * B > 0x7fffffffLL) { fail(GSR_ERR_INVALID_ARGUMENT, "%s: B * max(N, M) too large", who); return -1; }
-    return 1;
-}
-
-int32_t gsr_chamfer_workspace(int32_t B, int32_t N, int32_t M, size_t *bytes) {
-    if (B < 0 || N < 0 || M < 0 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_chamfer_workspace: bad argument");
-    *bytes = (size_t)8 * (size_t)B * ((size_t)N + (size_t)M);
-    return GSR_OK;
-}
-
-int32_t gsr_chamfer_forward(gsr_stream_t stream, int32_t B, int32_t N, int32_t M, int32_t D, const float *x1, const float *x2,
-                            float *dist1, float *dist2, int32_t *idx1, int32_t *idx2, void *ws, size_t ws_bytes) {
-    const int k = chamfer_sizes("gsr_chamfer_forward", B, N, M, D);
-    if (k <= 0) return k < 0 ? GSR_ERR_INVALID_ARGUMENT : GSR_OK;
-    if (!x1 || !x2 || !dist1 || !dist2 || !idx1 || !idx2 || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_chamfer_forward: null pointer");
-    const size_t need = (size_t)8 * (size_t)B * ((size_t)N + (size_t)M);
-    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "chamfer workspace %zu < %zu", ws_bytes, need);
-    HIP_TRY(launch_chamfer_forward(B, N, M, D, x1, x2, dist1, dist2, idx1, idx2, ws, (hipStream_t)stream), "chamfer forward launch");
-    return GSR_OK;
-}
-
-int32_t gsr_chamfer_backward(gsr_stream_t stream, int32_t B, int32_t N, int32_t M, int32_t D, const float *x1, const float *x2,
-                             const int32_t *idx1, const int32_t *idx2, const float *g1, const float *g2, float *dx1, float *dx2) {
-    const int k = chamfer_sizes("gsr_chamfer_backward", B, N, M, D);
-    if (k <= 0) return k < 0 ? GSR_ERR_INVALID_ARGUMENT : GSR_OK;
-    if (!x1 || !x2 || !idx1 || !idx2) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_chamfer_backward: null pointer");
-    HIP_TRY(launch_chamfer_backward(B, N, M, D, x1, x2, idx1, idx2, g1, g2, dx1, dx2, (hipStream_t)stream), "chamfer backward launch");
-    return GSR_OK;
-}
-
-// ---- sequence preparation: box sort and multi-camera visibility (include/gsr_sequence.h) ----
-static int box_sizes(const char *who, int32_t P, int32_t n) {
-    if (P < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: P=%d is negative", who, P);
-    if (n < 1 || n > GSR_BOX_MAX_N) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: n=%d not in 1..%d", who, n, GSR_BOX_MAX_N);
-    return GSR_OK;
-}
-
-int32_t gsr_box_sort_workspace(int32_t P, int32_t n, size_t *bytes) {
-    if (!bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort_workspace: bytes is NULL");
-    if (box_sizes("gsr_box_sort_workspace", P, n) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
-    HIP_TRY(box_sort_workspace_bytes(P, n, bytes), "box sort workspace size");
-    return GSR_OK;
-}
-
-int32_t gsr_box_sort(gsr_stream_t stream, int32_t P, int32_t D, const float *rows, int32_t xyz_col, int32_t n, float *out_rows,
-                     int32_t *out_perm, int32_t *out_count, void *ws, size_t ws_bytes) {
-    if (box_sizes("gsr_box_sort", P, n) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
-    if (D < 3 || D > GSR_BOX_MAX_D) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: D=%d not in 3..%d", D, GSR_BOX_MAX_D);
-    if (xyz_col < 0 || xyz_col > D - 3) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: xyz_col=%d not in 0..D-3=%d", xyz_col, D - 3);
-    if ((long long)P * D > 0x7fffffffLL) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: P * D = %lld too large", (long long)P * D);
-    if (!out_count) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: out_count is NULL");
-    if (P == 0) {
-        HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(int32_t), (hipStream_t)stream), "box sort: clear count");
-        return GSR_OK;
-    }
-    if (!rows || !out_rows || !out_perm || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: null pointer");
-    if (rows == out_rows) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: rows and out_rows must not overlap (same pointer)");
-    if (rows < out_rows + (size_t)P * D && out_rows < rows + (size_t)P * D)
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: rows and out_rows must not overlap (the ranges of P * D floats intersect)");
-    size_t need = 0;
-    HIP_TRY(box_sort_workspace_bytes(P, n, &need), "box sort workspace size");
-    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "box sort workspace %zu < %zu", ws_bytes, need);
-    HIP_TRY(launch_box_sort(P, D, rows, xyz_col, n, out_rows, out_perm, out_count, ws, (hipStream_t)stream), "box sort launch");
-    return GSR_OK;
-}
-
-int32_t gsr_visible_union(gsr_stream_t stream, int32_t P, int32_t B, const float *means3D, const float *scales, float scale_modifier,
-                          const float *rotations, const float *cov3D_precomp, int32_t raw_params, const float *viewmatrices,
-                          const float *projmatrices, const float *tanfovx, const float *tanfovy, const int32_t *widths,
-                          const int32_t *heights, int32_t *radii_out, uint8_t *visible_out, int32_t *counts_out) {
-    if (P < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: P=%d is negative", P);
-    if (B < 1 || B > GSR_VISIBLE_MAX_B) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: B=%d not in 1..%d", B, GSR_VISIBLE_MAX_B);
-    if (!tanfovx || !tanfovy || !widths || !heights) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: tanfovx/tanfovy/widths/heights (host) required");
-    VisibleArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int b = 0; b < B; b++) {
-        if (widths[b] <= 0 || heights[b] <= 0 || widths[b] > 65535 * GSR_TILE_HOST || heights[b] > 65535 * GSR_TILE_HOST)
-            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: camera %d: image size %d x %d", b, widths[b], heights[b]);
-        a.tanfovx[b] = tanfovx[b]; a.tanfovy[b] = tanfovy[b]; a.W[b] = widths[b]; a.H[b] = heights[b];
-    }
-    if (counts_out) HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)B * sizeof(int32_t), (hipStream_t)stream), "visible union: clear counts");
-    if (P == 0) return GSR_OK;
-    if (!means3D || !viewmatrices || !projmatrices) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: missing means3D or matrices");
-    if ((cov3D_precomp != nullptr) == (scales != nullptr || rotations != nullptr) || (!cov3D_precomp && (!scales || !rotations)))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: exactly one of (scales, rotations) / cov3D_precomp must be given");
-    if (raw_params && cov3D_precomp) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: raw_params needs scales/rotations, not cov3D_precomp");
-    a.P = P; a.B = B; a.raw_params = raw_params ? 1 : 0; a.scale_modifier = scale_modifier;
-    a.means3D = means3D; a.scales = scales; a.rotations = rotations; a.cov3D_precomp = cov3D_precomp;
-    a.viewmatrices = viewmatrices; a.projmatrices = projmatrices;
-    a.radii_out = radii_out; a.visible_out = visible_out; a.counts_out = counts_out;
-    HIP_TRY(launch_visible_union(a, (hipStream_t)stream), "visible union launch");
     return GSR_OK;
 }
 

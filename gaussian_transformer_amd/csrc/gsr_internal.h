@@ -1,5 +1,7 @@
-// gsr_internal.h -- workspace layouts and kernel launchers shared by the translation units of
-// libgsr_hip.so.  Nothing here is part of the public ABI (include/gsr.h).
+// gsr_internal.h -- workspace layouts and kernel launchers of the rasterizer (include/gsr.h), shared between gsr_api.hip and the
+// translation units with its kernels.  Nothing here is part of the public ABI.  The other headers' features (loss, Adam, density
+// control, kNN, Chamfer, sequence preparation, rows) keep their launchers file-local, next to their own entry points; they include
+// this file for its helpers (align_up, ceil_log2_u32, GSR_TILE_HOST) only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -396,53 +398,9 @@ static inline size_t pergauss_vis_bytes(int P) {
     return 256 + (((size_t)P * 4 + 255) / 256 * 256) + (size_t)pergauss_vis_cap(P) * 15 * 16;
 }
 
-hipError_t launch_l1_ssim_forward(int C, int H, int W, const float *img, const float *gt, float lambda, float *dmaps,
-                                  float *partial, float *out, hipStream_t s);
-hipError_t launch_l1_ssim_backward(int C, int H, int W, const float *img, const float *gt, float lambda, const float *dmaps,
-                                   const float *grad_loss, float *grad_img, hipStream_t s);
-
-// the multi-view form (ssim_loss.hip); sizes and pointers validated by the caller: B, H, W >= 1, no NULL among imgs / gts
+// ssim_loss.hip's per-launch view limit (include/gsr_loss.h: GSR_VIEWS_LOSS_MAX_B, checked equal there)
 #define GSR_VIEWS_MAX_B 16   // == GSR_VIEWS_LOSS_MAX_B: views whose pointers one launch carries in its kernel arguments
-size_t views_loss_workspace_bytes(int B, int H, int W);
-hipError_t launch_views_loss_forward(int B, int H, int W, const float *const *imgs, const float *const *gts, float w_l1, float w_ssim,
-                                     int sanitize, float *out3, float *terms, void *ws, hipStream_t s);
-hipError_t launch_views_loss_backward(int B, int H, int W, const float *const *imgs, const float *const *gts, float w_l1, float w_ssim,
-                                      int sanitize, const float *grad_loss, const void *ws, float *const *grad_imgs, hipStream_t s);
 
-hipError_t knn_workspace_bytes(int N, size_t *bytes);
-hipError_t launch_knn(int N, const float *pts, float *out, void *ws, hipStream_t s);
-
-// chamfer.hip (include/gsr_chamfer.h); sizes validated by the caller: B, N, M >= 1, 1 <= D <= 64
-hipError_t launch_chamfer_forward(int B, int N, int M, int D, const float *x1, const float *x2, float *dist1, float *dist2,
-                                  int32_t *idx1, int32_t *idx2, void *ws, hipStream_t s);
-hipError_t launch_chamfer_backward(int B, int N, int M, int D, const float *x1, const float *x2, const int32_t *idx1, const int32_t *idx2,
-                                   const float *g1, const float *g2, float *dx1, float *dx2, hipStream_t s);
-
-hipError_t launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present, hipStream_t s);
-
-// sequence.hip (include/gsr_sequence.h); sizes validated by the caller, P >= 1
-#define GSR_SEQ_MAX_N 128   // == GSR_BOX_MAX_N
-#define GSR_SEQ_MAX_B 64    // == GSR_VISIBLE_MAX_B
-struct VisibleArgs {
-    int P, B, raw_params;
-    float scale_modifier;
-    const float *means3D, *scales, *rotations, *cov3D_precomp, *viewmatrices, *projmatrices;
-    int32_t *radii_out;
-    uint8_t *visible_out;
-    int32_t *counts_out;
-    float tanfovx[GSR_SEQ_MAX_B], tanfovy[GSR_SEQ_MAX_B];
-    int W[GSR_SEQ_MAX_B], H[GSR_SEQ_MAX_B];
-};
-hipError_t box_sort_workspace_bytes(int P, int n, size_t *bytes);
-hipError_t launch_box_sort(int P, int D, const float *rows, int xyz_col, int n, float *out_rows, int32_t *out_perm, int32_t *out_count,
-                           void *ws, hipStream_t s);
-hipError_t launch_visible_union(const VisibleArgs &a, hipStream_t s);
-
-// density.hip (include/gsr_density.h); sizes, pointers and roles validated by the caller, P >= 1
-hipError_t launch_density_record(int P, const float *grad2d, int stride, const int32_t *radii, const uint8_t *visible, float *accum,
-                                 float *denom, float *max_radii, hipStream_t s);
-hipError_t densify_plan_workspace_bytes(int P, int N, size_t *bytes);
-hipError_t launch_densify_plan(int P, const float *opacity, const float *scaling, const float *accum, const float *denom, float grad_threshold,
-                               float min_opacity, float cut, float prune_world, int N, uint32_t *counts_host, void *ws, hipStream_t s);
+hipError_t launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present, hipStream_t s);   // preprocess.hip, for gsr_mark_visible
 
 }  // namespace gsr

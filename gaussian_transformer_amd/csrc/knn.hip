@@ -17,6 +17,8 @@
 #include <float.h>
 #include <stdint.h>
 
+#include "../../include/gsr_knn.h"
+#include "gsr_host.h"
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -175,14 +177,14 @@ __global__ __launch_bounds__(256) void knn_query_kernel(int N, int nbox, const f
     out[i] = nn == 3 ? (best[0] + best[1] + best[2]) / 3.f : nn == 2 ? (best[0] + best[1]) / 2.f : nn == 1 ? best[0] : 0.f;
 }
 
-hipError_t knn_workspace_bytes(int N, size_t *bytes) {
+static hipError_t knn_workspace_bytes(int N, size_t *bytes) {
     size_t tb = 0;
     hipError_t e = knn_sort_temp(N, &tb);
     *bytes = carve_knn(nullptr, N, tb).total_bytes;
     return e;
 }
 
-hipError_t launch_knn(int N, const float *pts, float *out, void *ws, hipStream_t s) {
+static hipError_t launch_knn(int N, const float *pts, float *out, void *ws, hipStream_t s) {
     if (N <= 0) return hipSuccess;
     size_t tb = 0;
     hipError_t e = knn_sort_temp(N, &tb);
@@ -202,3 +204,25 @@ hipError_t launch_knn(int N, const float *pts, float *out, void *ws, hipStream_t
 }
 
 }  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+// ---- simple_knn.distCUDA2 equivalent (include/gsr_knn.h) ----
+int32_t gsr_knn_workspace(int32_t N, size_t *bytes) {
+    if (N < 0 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_knn_workspace: bad argument");
+    HIP_TRY(knn_workspace_bytes(N, bytes), "knn temp query");
+    return GSR_OK;
+}
+
+int32_t gsr_knn_mean_dist2(gsr_stream_t stream, int32_t N, const float *points, float *mean_dist2, void *ws, size_t ws_bytes) {
+    if (N < 0 || (N > 0 && (!points || !mean_dist2 || !ws))) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_knn_mean_dist2: bad argument");
+    size_t need = 0;
+    HIP_TRY(knn_workspace_bytes(N, &need), "knn temp query");
+    if (N > 0 && ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "knn workspace %zu < %zu", ws_bytes, need);
+    HIP_TRY(launch_knn(N, points, mean_dist2, ws, (hipStream_t)stream), "knn launch");
+    return GSR_OK;
+}
+
+}  // extern "C"

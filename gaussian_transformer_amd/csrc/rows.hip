@@ -6,15 +6,14 @@
 // access is flat and coalesced (16 bytes per lane on the row side when the base pointer allows it, consecutive dwords per lane on
 // the group side, whose runs start at multiples of w floats only).  The LDS tile has an odd pitch (D | 1 dwords): with the even
 // pitches 26 and 62, rows r and r + 16 would share a bank (ds_write_b32 / ds_read_b32 bank on dword address mod 32).
-// No floating-point contraction question: grad_pack only adds.  The entry points live here, not in gsr_api.hip, and keep to
-// its conventions; their error text goes into the same per-thread buffer gsr_last_error() returns.
+// No floating-point contraction question: grad_pack only adds.  The entry points live here, next to their kernels, as those of
+// every header but gsr.h do; refusals go through gsr::fail (gsr_host.h).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 
 #include "../../include/gsr_rows.h"
+#include "gsr_host.h"
 
 namespace gsr {
 
@@ -135,17 +134,6 @@ __global__ __launch_bounds__(256) void rows_grad_pack_kernel(RowsPackArgs a) {
 
 // ---------------------------------------------------------------- host ----------------------------------------------------------------
 
-// gsr_last_error() hands out this thread's message buffer (gsr_api.hip: 512 bytes, static to that file); the entry points below
-// leave their text in it like every other one.  No message here comes near the 256 bytes written at most.
-static int rows_fail(int code, const char *fmt, ...) {
-    char *buf = const_cast<char *>(gsr_last_error());
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, 256, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 // K of a D-column row, 0 if D is no row width
 static int rows_K(int D) {
     if (D < 17 || (D - 14) % 3) return 0;
@@ -159,10 +147,10 @@ static bool ranges_meet(const void *a, size_t a_floats, const void *b, size_t b_
 }
 
 static int rows_sizes(const char *who, int32_t P, int32_t D) {
-    if (P < 0) return rows_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P=%d is negative", who, P);
+    if (P < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: P=%d is negative", who, P);
     if (!rows_K(D))
-        return rows_fail(GSR_ERR_INVALID_ARGUMENT, "%s: D=%d is not 3 K + 14 for K in 1..%d SH coefficients", who, D, GSR_ROWS_MAX_K);
-    if ((long long)P * D > 0x7fffffffLL) return rows_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P * D = %lld too large", who, (long long)P * D);
+        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: D=%d is not 3 K + 14 for K in 1..%d SH coefficients", who, D, GSR_ROWS_MAX_K);
+    if ((long long)P * D > 0x7fffffffLL) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: P * D = %lld too large", who, (long long)P * D);
     return GSR_OK;
 }
 
@@ -178,15 +166,15 @@ int32_t gsr_rows_unpack(gsr_stream_t stream, int32_t P, int32_t D, const float *
     if (P == 0) return GSR_OK;                       // nothing to read or write: no pointer is looked at
     const int K = rows_K(D);
     if ((f_rest == nullptr) != (K == 1))
-        return rows_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_unpack: f_rest must be NULL if and only if K = 1 (D=%d holds K=%d)", D, K);
-    if (!rows || !xyz || !f_dc || !opacity || !scaling || !rotation) return rows_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_unpack: null pointer");
+        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_unpack: f_rest must be NULL if and only if K = 1 (D=%d holds K=%d)", D, K);
+    if (!rows || !xyz || !f_dc || !opacity || !scaling || !rotation) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_unpack: null pointer");
     if ((uintptr_t)rotation & 15)
-        return rows_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_unpack: rotation must be 16-byte aligned (gsr_forward reads a quaternion as one 16-byte load)");
+        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_unpack: rotation must be 16-byte aligned (gsr_forward reads a quaternion as one 16-byte load)");
     const struct { const char *name; const float *p; size_t w; } outs[6] = {
         {"xyz", xyz, 3}, {"f_dc", f_dc, 3}, {"f_rest", f_rest, (size_t)3 * (K - 1)}, {"opacity", opacity, 1}, {"scaling", scaling, 3}, {"rotation", rotation, 4}};
     for (const auto &o : outs)
         if (o.p && ranges_meet(rows, (size_t)P * D, o.p, (size_t)P * o.w))
-            return rows_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_unpack: %s overlaps rows", o.name);
+            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_unpack: %s overlaps rows", o.name);
     RowsUnpackArgs a;
     a.P = P; a.D = D; a.K = K; a.vec = ((uintptr_t)rows & 15) == 0;
     a.rows = (const uint32_t *)rows;
@@ -194,32 +182,32 @@ int32_t gsr_rows_unpack(gsr_stream_t stream, int32_t P, int32_t D, const float *
     a.opacity = (uint32_t *)opacity; a.scaling = (uint32_t *)scaling; a.rotation = (uint32_t *)rotation;
     hipLaunchKernelGGL(rows_unpack_kernel, dim3((P + ROWS_TILE - 1) / ROWS_TILE), dim3(256), 0, (hipStream_t)stream, a);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rows_fail(GSR_ERR_HIP, "rows unpack launch: %s (%d)", hipGetErrorString(e), (int)e);
+    if (e != hipSuccess) return fail(GSR_ERR_HIP, "rows unpack launch: %s (%d)", hipGetErrorString(e), (int)e);
     return GSR_OK;
 }
 
 int32_t gsr_rows_grad_pack(gsr_stream_t stream, int32_t P, int32_t D, int32_t B, const float *const *arenas, float *grad_rows) {
     if (rows_sizes("gsr_rows_grad_pack", P, D) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
-    if (B < 1 || B > GSR_ROWS_MAX_B) return rows_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_grad_pack: B=%d not in 1..%d", B, GSR_ROWS_MAX_B);
+    if (B < 1 || B > GSR_ROWS_MAX_B) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_grad_pack: B=%d not in 1..%d", B, GSR_ROWS_MAX_B);
     if (P == 0) return GSR_OK;                       // likewise
-    if (!arenas) return rows_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_grad_pack: arenas (host array) required");
-    if (!grad_rows) return rows_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_grad_pack: grad_rows is NULL");
+    if (!arenas) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_grad_pack: arenas (host array) required");
+    if (!grad_rows) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_grad_pack: grad_rows is NULL");
     const int K = rows_K(D);
     const size_t arena_floats = (size_t)P * (3 * K + 11);
     RowsPackArgs a;
     for (int b = 0; b < GSR_ROWS_MAX_B; b++) a.arena[b] = nullptr;
     for (int b = 0; b < B; b++) {
-        if (!arenas[b]) return rows_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_grad_pack: arenas[%d] is NULL", b);
-        if ((uintptr_t)arenas[b] & 3) return rows_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_grad_pack: arenas[%d] is not 4-byte aligned", b);
+        if (!arenas[b]) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_grad_pack: arenas[%d] is NULL", b);
+        if ((uintptr_t)arenas[b] & 3) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_grad_pack: arenas[%d] is not 4-byte aligned", b);
         if (ranges_meet(grad_rows, (size_t)P * D, arenas[b], arena_floats))
-            return rows_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_grad_pack: grad_rows overlaps arenas[%d]", b);
+            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_rows_grad_pack: grad_rows overlaps arenas[%d]", b);
         a.arena[b] = arenas[b];
     }
     a.P = P; a.D = D; a.K = K; a.B = B; a.vec = ((uintptr_t)grad_rows & 15) == 0;
     a.grad_rows = grad_rows;
     hipLaunchKernelGGL(rows_grad_pack_kernel, dim3((P + ROWS_TILE - 1) / ROWS_TILE), dim3(256), 0, (hipStream_t)stream, a);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rows_fail(GSR_ERR_HIP, "rows grad pack launch: %s (%d)", hipGetErrorString(e), (int)e);
+    if (e != hipSuccess) return fail(GSR_ERR_HIP, "rows grad pack launch: %s (%d)", hipGetErrorString(e), (int)e);
     return GSR_OK;
 }
 

@@ -8,10 +8,26 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
+#include "../../include/gsr_sequence.h"
 #include "gsr_device.h"
+#include "gsr_host.h"
 #include "gsr_internal.h"
 
 namespace gsr {
+
+#define GSR_SEQ_MAX_N 128   // == GSR_BOX_MAX_N
+#define GSR_SEQ_MAX_B 64    // == GSR_VISIBLE_MAX_B
+static_assert(GSR_SEQ_MAX_N == GSR_BOX_MAX_N && GSR_SEQ_MAX_B == GSR_VISIBLE_MAX_B, "limits of sequence.hip and gsr_sequence.h");
+struct VisibleArgs {
+    int P, B, raw_params;
+    float scale_modifier;
+    const float *means3D, *scales, *rotations, *cov3D_precomp, *viewmatrices, *projmatrices;
+    int32_t *radii_out;
+    uint8_t *visible_out;
+    int32_t *counts_out;
+    float tanfovx[GSR_SEQ_MAX_B], tanfovy[GSR_SEQ_MAX_B];
+    int W[GSR_SEQ_MAX_B], H[GSR_SEQ_MAX_B];
+};
 
 // ---------------------------------------------------------------- box sort ----------------------------------------------------------------
 
@@ -88,7 +104,7 @@ static hipError_t carve_box_ws(void *base, int P, int n, BoxWs &w) {
     return hipSuccess;
 }
 
-hipError_t box_sort_workspace_bytes(int P, int n, size_t *bytes) {
+static hipError_t box_sort_workspace_bytes(int P, int n, size_t *bytes) {
     BoxWs w;
     hipError_t e = carve_box_ws(nullptr, P, n, w);
     if (e == hipSuccess) *bytes = w.total;
@@ -96,7 +112,7 @@ hipError_t box_sort_workspace_bytes(int P, int n, size_t *bytes) {
 }
 
 // sizes validated by the caller; P >= 1
-hipError_t launch_box_sort(int P, int D, const float *rows, int xyz_col, int n, float *out_rows, int32_t *out_perm, int32_t *out_count,
+static hipError_t launch_box_sort(int P, int D, const float *rows, int xyz_col, int n, float *out_rows, int32_t *out_perm, int32_t *out_count,
                            void *ws, hipStream_t s) {
     BoxWs w;
     hipError_t e = carve_box_ws(ws, P, n, w);
@@ -189,7 +205,7 @@ __global__ __launch_bounds__(256) void visible_union_kernel(VisibleArgs a) {
 }
 
 // sizes validated by the caller; P >= 1; counts_out zeroed by the caller on the same stream
-hipError_t launch_visible_union(const VisibleArgs &a, hipStream_t s) {
+static hipError_t launch_visible_union(const VisibleArgs &a, hipStream_t s) {
     const dim3 grid((a.P + 255) / 256), block(256);
     if (a.raw_params) hipLaunchKernelGGL((visible_union_kernel<true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((visible_union_kernel<false>), grid, block, 0, s, a);
@@ -197,3 +213,73 @@ hipError_t launch_visible_union(const VisibleArgs &a, hipStream_t s) {
 }
 
 }  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+// ---- sequence preparation: box sort and multi-camera visibility (include/gsr_sequence.h) ----
+static int box_sizes(const char *who, int32_t P, int32_t n) {
+    if (P < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: P=%d is negative", who, P);
+    if (n < 1 || n > GSR_BOX_MAX_N) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: n=%d not in 1..%d", who, n, GSR_BOX_MAX_N);
+    return GSR_OK;
+}
+
+int32_t gsr_box_sort_workspace(int32_t P, int32_t n, size_t *bytes) {
+    if (!bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort_workspace: bytes is NULL");
+    if (box_sizes("gsr_box_sort_workspace", P, n) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
+    HIP_TRY(box_sort_workspace_bytes(P, n, bytes), "box sort workspace size");
+    return GSR_OK;
+}
+
+int32_t gsr_box_sort(gsr_stream_t stream, int32_t P, int32_t D, const float *rows, int32_t xyz_col, int32_t n, float *out_rows,
+                     int32_t *out_perm, int32_t *out_count, void *ws, size_t ws_bytes) {
+    if (box_sizes("gsr_box_sort", P, n) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
+    if (D < 3 || D > GSR_BOX_MAX_D) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: D=%d not in 3..%d", D, GSR_BOX_MAX_D);
+    if (xyz_col < 0 || xyz_col > D - 3) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: xyz_col=%d not in 0..D-3=%d", xyz_col, D - 3);
+    if ((long long)P * D > 0x7fffffffLL) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: P * D = %lld too large", (long long)P * D);
+    if (!out_count) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: out_count is NULL");
+    if (P == 0) {
+        HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(int32_t), (hipStream_t)stream), "box sort: clear count");
+        return GSR_OK;
+    }
+    if (!rows || !out_rows || !out_perm || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: null pointer");
+    if (rows == out_rows) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: rows and out_rows must not overlap (same pointer)");
+    if (rows < out_rows + (size_t)P * D && out_rows < rows + (size_t)P * D)
+        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_box_sort: rows and out_rows must not overlap (the ranges of P * D floats intersect)");
+    size_t need = 0;
+    HIP_TRY(box_sort_workspace_bytes(P, n, &need), "box sort workspace size");
+    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "box sort workspace %zu < %zu", ws_bytes, need);
+    HIP_TRY(launch_box_sort(P, D, rows, xyz_col, n, out_rows, out_perm, out_count, ws, (hipStream_t)stream), "box sort launch");
+    return GSR_OK;
+}
+
+int32_t gsr_visible_union(gsr_stream_t stream, int32_t P, int32_t B, const float *means3D, const float *scales, float scale_modifier,
+                          const float *rotations, const float *cov3D_precomp, int32_t raw_params, const float *viewmatrices,
+                          const float *projmatrices, const float *tanfovx, const float *tanfovy, const int32_t *widths,
+                          const int32_t *heights, int32_t *radii_out, uint8_t *visible_out, int32_t *counts_out) {
+    if (P < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: P=%d is negative", P);
+    if (B < 1 || B > GSR_VISIBLE_MAX_B) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: B=%d not in 1..%d", B, GSR_VISIBLE_MAX_B);
+    if (!tanfovx || !tanfovy || !widths || !heights) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: tanfovx/tanfovy/widths/heights (host) required");
+    VisibleArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int b = 0; b < B; b++) {
+        if (widths[b] <= 0 || heights[b] <= 0 || widths[b] > 65535 * GSR_TILE_HOST || heights[b] > 65535 * GSR_TILE_HOST)
+            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: camera %d: image size %d x %d", b, widths[b], heights[b]);
+        a.tanfovx[b] = tanfovx[b]; a.tanfovy[b] = tanfovy[b]; a.W[b] = widths[b]; a.H[b] = heights[b];
+    }
+    if (counts_out) HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)B * sizeof(int32_t), (hipStream_t)stream), "visible union: clear counts");
+    if (P == 0) return GSR_OK;
+    if (!means3D || !viewmatrices || !projmatrices) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: missing means3D or matrices");
+    if ((cov3D_precomp != nullptr) == (scales != nullptr || rotations != nullptr) || (!cov3D_precomp && (!scales || !rotations)))
+        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: exactly one of (scales, rotations) / cov3D_precomp must be given");
+    if (raw_params && cov3D_precomp) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_visible_union: raw_params needs scales/rotations, not cov3D_precomp");
+    a.P = P; a.B = B; a.raw_params = raw_params ? 1 : 0; a.scale_modifier = scale_modifier;
+    a.means3D = means3D; a.scales = scales; a.rotations = rotations; a.cov3D_precomp = cov3D_precomp;
+    a.viewmatrices = viewmatrices; a.projmatrices = projmatrices;
+    a.radii_out = radii_out; a.visible_out = visible_out; a.counts_out = counts_out;
+    HIP_TRY(launch_visible_union(a, (hipStream_t)stream), "visible union launch");
+    return GSR_OK;
+}
+
+}  // extern "C"

@@ -22,6 +22,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/gsr_loss.h"
+#include "gsr_host.h"
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -269,7 +271,7 @@ __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int C, int H, int W, c
     }
 }
 
-hipError_t launch_l1_ssim_forward(int C, int H, int W, const float *img, const float *gt, float lambda, float *dmaps,
+static hipError_t launch_l1_ssim_forward(int C, int H, int W, const float *img, const float *gt, float lambda, float *dmaps,
                                   float *partial, float *out, hipStream_t s) {
     const SsimWeights w = make_weights();
     const dim3 grid((W + SSIM_T - 1) / SSIM_T, (H + SSIM_T - 1) / SSIM_T, C);
@@ -279,7 +281,7 @@ hipError_t launch_l1_ssim_forward(int C, int H, int W, const float *img, const f
     return hipGetLastError();
 }
 
-hipError_t launch_l1_ssim_backward(int C, int H, int W, const float *img, const float *gt, float lambda, const float *dmaps,
+static hipError_t launch_l1_ssim_backward(int C, int H, int W, const float *img, const float *gt, float lambda, const float *dmaps,
                                    const float *grad_loss, float *grad_img, hipStream_t s) {
     const SsimWeights w = make_weights();
     const dim3 grid((W + SSIM_T - 1) / SSIM_T, (H + SSIM_T - 1) / SSIM_T, C);
@@ -302,7 +304,7 @@ static inline ViewsWs views_carve(void *ws, int B, int H, int W, size_t *bytes) 
     if (bytes) *bytes = off;
     return v;
 }
-size_t views_loss_workspace_bytes(int B, int H, int W) {
+static size_t views_loss_workspace_bytes(int B, int H, int W) {
     size_t n = 0;
     views_carve(nullptr, B, H, W, &n);
     return n;
@@ -421,7 +423,7 @@ __global__ __launch_bounds__(256) void views_loss_bwd_kernel(ViewsBwdArgs a) {
 }
 
 // B, H, W >= 1 and no NULL among imgs / gts (checked by gsr_views_loss_forward); ws holds views_loss_workspace_bytes(B, H, W)
-hipError_t launch_views_loss_forward(int B, int H, int W, const float *const *imgs, const float *const *gts, float w_l1, float w_ssim,
+static hipError_t launch_views_loss_forward(int B, int H, int W, const float *const *imgs, const float *const *gts, float w_l1, float w_ssim,
                                      int sanitize, float *out3, float *terms, void *ws, hipStream_t s) {
     const ViewsWs w = views_carve(ws, B, H, W, nullptr);
     ViewsFwdArgs a;
@@ -441,7 +443,7 @@ hipError_t launch_views_loss_forward(int B, int H, int W, const float *const *im
     return hipGetLastError();
 }
 
-hipError_t launch_views_loss_backward(int B, int H, int W, const float *const *imgs, const float *const *gts, float w_l1, float w_ssim,
+static hipError_t launch_views_loss_backward(int B, int H, int W, const float *const *imgs, const float *const *gts, float w_l1, float w_ssim,
                                       int sanitize, const float *grad_loss, const void *ws, float *const *grad_imgs, hipStream_t s) {
     const ViewsWs w = views_carve(const_cast<void *>(ws), B, H, W, nullptr);
     ViewsBwdArgs a;
@@ -467,3 +469,84 @@ hipError_t launch_views_loss_backward(int B, int H, int W, const float *const *i
 }
 
 }  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+// ---- fused training loss (include/gsr_loss.h) ----
+static inline size_t loss_blocks(int C, int H, int W) { return (size_t)((W + 15) / 16) * ((H + 15) / 16) * C; }
+
+int32_t gsr_l1_ssim_workspace(int32_t C, int32_t H, int32_t W, size_t *bytes) {
+    if (C <= 0 || H <= 0 || W <= 0 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_l1_ssim_workspace: bad argument");
+    *bytes = align_up((size_t)3 * C * H * W * sizeof(float)) + align_up(loss_blocks(C, H, W) * 2 * sizeof(float));
+    return GSR_OK;
+}
+
+int32_t gsr_l1_ssim_forward(gsr_stream_t stream, int32_t C, int32_t H, int32_t W, const float *img, const float *gt,
+                            float lambda_dssim, float *out3, void *ws, size_t ws_bytes) {
+    size_t need = 0;
+    if (gsr_l1_ssim_workspace(C, H, W, &need) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
+    if (!img || !gt || !out3 || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_l1_ssim_forward: null pointer");
+    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "loss workspace %zu < %zu", ws_bytes, need);
+    float *dmaps = (float *)ws;
+    float *partial = (float *)((char *)ws + align_up((size_t)3 * C * H * W * sizeof(float)));
+    HIP_TRY(launch_l1_ssim_forward(C, H, W, img, gt, lambda_dssim, dmaps, partial, out3, (hipStream_t)stream), "l1+ssim forward launch");
+    return GSR_OK;
+}
+
+int32_t gsr_l1_ssim_backward(gsr_stream_t stream, int32_t C, int32_t H, int32_t W, const float *img, const float *gt,
+                             float lambda_dssim, const float *grad_loss, const void *ws, size_t ws_bytes, float *grad_img) {
+    size_t need = 0;
+    if (gsr_l1_ssim_workspace(C, H, W, &need) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
+    if (!img || !gt || !ws || !grad_img) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_l1_ssim_backward: null pointer");
+    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "loss workspace %zu < %zu", ws_bytes, need);
+    HIP_TRY(launch_l1_ssim_backward(C, H, W, img, gt, lambda_dssim, (const float *)ws, grad_loss, grad_img, (hipStream_t)stream),
+            "l1+ssim backward launch");
+    return GSR_OK;
+}
+
+// ---- the same loss over B views (include/gsr_loss.h) ----
+static_assert(GSR_VIEWS_MAX_B == GSR_VIEWS_LOSS_MAX_B, "per-launch view limit of ssim_loss.hip and gsr_loss.h");
+// 0 = ok; everything the forward and the backward check alike, before anything is launched
+static int views_loss_check(const char *who, int32_t B, int32_t H, int32_t W, const float *const *imgs, const float *const *gts,
+                            const void *ws, size_t ws_bytes) {
+    size_t need = 0;
+    if (gsr_views_loss_workspace(B, H, W, &need) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
+    if (!imgs || !gts || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: null pointer (imgs, gts or workspace)", who);
+    for (int b = 0; b < B; b++)
+        if (!imgs[b] || !gts[b]) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: view %d: null %s pointer", who, b, imgs[b] ? "target" : "image");
+    if (ws_bytes < need) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: workspace %zu < %zu", who, ws_bytes, need);
+    return GSR_OK;
+}
+
+int32_t gsr_views_loss_workspace(int32_t B, int32_t H, int32_t W, size_t *bytes) {
+    if (B < 1 || H < 1 || W < 1 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_workspace: bad argument (B=%d H=%d W=%d)", B, H, W);
+    if ((H + 15) / 16 > 65535 || (size_t)3 * loss_blocks(1, H, W) > (size_t)INT32_MAX)
+        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_workspace: image %d x %d too large", W, H);
+    *bytes = views_loss_workspace_bytes(B, H, W);
+    return GSR_OK;
+}
+
+int32_t gsr_views_loss_forward(gsr_stream_t stream, int32_t B, int32_t H, int32_t W, const float *const *imgs, const float *const *gts,
+                               float w_l1, float w_ssim, int32_t sanitize, float *out3, float *terms, void *ws, size_t ws_bytes) {
+    const int rc = views_loss_check("gsr_views_loss_forward", B, H, W, imgs, gts, ws, ws_bytes);
+    if (rc != GSR_OK) return rc;
+    if (!out3 || !terms) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_forward: null pointer (out3 or terms)");
+    HIP_TRY(launch_views_loss_forward(B, H, W, imgs, gts, w_l1, w_ssim, sanitize ? 1 : 0, out3, terms, ws, (hipStream_t)stream),
+            "views loss forward launch");
+    return GSR_OK;
+}
+
+int32_t gsr_views_loss_backward(gsr_stream_t stream, int32_t B, int32_t H, int32_t W, const float *const *imgs, const float *const *gts,
+                                float w_l1, float w_ssim, int32_t sanitize, const float *grad_loss, const void *ws, size_t ws_bytes,
+                                float *const *grad_imgs) {
+    const int rc = views_loss_check("gsr_views_loss_backward", B, H, W, imgs, gts, ws, ws_bytes);
+    if (rc != GSR_OK) return rc;
+    if (!grad_imgs) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_backward: null pointer (grad_imgs)");
+    HIP_TRY(launch_views_loss_backward(B, H, W, imgs, gts, w_l1, w_ssim, sanitize ? 1 : 0, grad_loss, ws, grad_imgs, (hipStream_t)stream),
+            "views loss backward launch");
+    return GSR_OK;
+}
+
+}  // extern "C"

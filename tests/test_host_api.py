@@ -139,7 +139,82 @@ def test_every_option_the_library_accepts_is_documented_in_the_header():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     api = open(os.path.join(root, "gaussian_transformer_amd", "csrc", "gsr_api.hip")).read()
     hdr = open(os.path.join(root, "include", "gsr.h")).read()
-    names = sorted(set(re.findall(r'strcmp\(name, "([a-z_0-9]+)"\)', api)))
+    rows = re.findall(r'^\s*\{"([a-z_0-9]+)", &g_[a-z_]+, OPT_[A-Z_0-9]+,', api, flags=re.M)      # the option table
+    explicit = re.findall(r'strcmp\(name, "([a-z_0-9]+)"\)', api)                                # the irregular ones beside it
+    assert len(rows) == len(set(rows)) and len(rows) > 10 and len(set(explicit)) >= 6
+    names = sorted(set(rows) | set(explicit))
     assert len(names) > 15
     missing = [n for n in names if f'"{n}"' not in hdr]
     assert not missing, missing
+
+
+BOOLEAN_OPTIONS = ("exact_tile_cull", "two_level_sort", "deterministic_bwd", "fill_in_tail", "asm_walk", "bwd_lpt")
+# name -> (values accepted and read back unchanged, values refused, the refusal's text)
+CHECKED_OPTIONS = {
+    **{n: ((0, 1, 2), (-1, 3), f"{n} must be 0, 1 or 2")
+       for n in ("tile_lists", "persistent_bwd", "prefill_at", "dense_fork", "dense_pergauss", "depth_buckets")},
+    **{n: ((1, 2, 4), (0, 3, 8, -2), f"{n} must be 1, 2 or 4")
+       for n in ("composite_waves_per_block", "fwd_blocks_per_wave", "bwd_blocks_per_wave")},
+    "segment_entries": ((0, 64, 256, 65536), (-64, 63, 100, 65600), "segment_entries must be 0 or a multiple of 64 up to 65536"),
+}
+# name -> (value set, value read back): the options that map what they are given instead of refusing it
+MAPPED_OPTIONS = {
+    **{n: ((0, 0), (1, 1), (7, 1), (-3, 1)) for n in BOOLEAN_OPTIONS + ("depth_log_map",)},
+    "count_lanes": ((0, 0), (1, 1), (2, 2), (5, 1), (-1, 1)),
+    "fwd_pair_long": ((-1, -1), (0, 0), (64, 64), (100000, 100000), (-7, -1)),
+}
+
+
+def test_option_table_round_trip():
+    """Every option by name: what gsr_set_option accepts is what gsr_get_option reads back, a refusal has its exact text and changes
+    nothing, the read-only and the set-only names are unknown to the other function, and every value is put back."""
+    lib = _lib.load()
+    err = lambda: lib.gsr_last_error().decode()
+
+    def get(name):
+        v = ctypes.c_int32(-12345)
+        assert lib.gsr_get_option(name.encode(), ctypes.byref(v)) == 0, name
+        return v.value
+    for name, (legal, illegal, text) in CHECKED_OPTIONS.items():
+        prev = get(name)
+        try:
+            for v in legal:
+                assert lib.gsr_set_option(name.encode(), v) == 0 and get(name) == v, (name, v)
+                for bad in illegal:
+                    assert lib.gsr_set_option(name.encode(), bad) == 1 and err() == text and get(name) == v, (name, bad)
+        finally:
+            assert lib.gsr_set_option(name.encode(), prev) == 0
+    for name, pairs in MAPPED_OPTIONS.items():
+        prev = get(name)
+        try:
+            for v, back in pairs:
+                assert lib.gsr_set_option(name.encode(), v) == 0 and get(name) == back, (name, v)
+        finally:
+            assert lib.gsr_set_option(name.encode(), prev) == 0
+    # set-only: accepted (negative values mean 0), unknown to gsr_get_option
+    v = ctypes.c_int32(-12345)
+    try:
+        for pad in (128, -5, 0):
+            assert lib.gsr_set_option(b"composite_lds_pad", pad) == 0
+        assert lib.gsr_get_option(b"composite_lds_pad", ctypes.byref(v)) == 1 and v.value == -12345
+        assert err() == "gsr_get_option: unknown option 'composite_lds_pad'"
+    finally:
+        assert lib.gsr_set_option(b"composite_lds_pad", 0) == 0
+    # read-only: unknown to gsr_set_option
+    for name in ("pergauss_path", "poll_timeouts"):
+        before = get(name)
+        assert lib.gsr_set_option(name.encode(), 1) == 1 and err() == f"gsr_set_option: unknown option '{name}'"
+        assert get(name) == before
+    # unknown and missing names, a missing destination
+    assert lib.gsr_set_option(b"no_such_option", 1) == 1 and err() == "gsr_set_option: unknown option 'no_such_option'"
+    assert lib.gsr_get_option(b"no_such_option", ctypes.byref(v)) == 1 and err() == "gsr_get_option: unknown option 'no_such_option'"
+    assert lib.gsr_set_option(b"", 1) == 1 and err() == "gsr_set_option: unknown option ''"
+    assert lib.gsr_set_option(None, 1) == 1 and err() == "gsr_set_option: unknown option '(null)'"
+    assert lib.gsr_get_option(None, ctypes.byref(v)) == 1 and err() == "gsr_get_option: unknown option '(null)'"
+    assert lib.gsr_get_option(b"tile_lists", None) == 1 and err() == "gsr_get_option: unknown option 'tile_lists'"
+    assert lib.gsr_get_option(b"pergauss_path", None) == 1 and err() == "gsr_get_option: unknown option 'pergauss_path'"
+    assert v.value == -12345
+    # the three lists above are the library's whole option surface (the header test reads the same names out of the source)
+    api = open(os.path.join(ROOT, "gaussian_transformer_amd", "csrc", "gsr_api.hip")).read()
+    known = set(re.findall(r'^\s*\{"([a-z_0-9]+)", &g_', api, flags=re.M)) | set(re.findall(r'strcmp\(name, "([a-z_0-9]+)"\)', api))
+    assert known == set(CHECKED_OPTIONS) | set(MAPPED_OPTIONS) | {"composite_lds_pad", "pergauss_path", "poll_timeouts"}
