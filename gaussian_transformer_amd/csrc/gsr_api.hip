@@ -1,5 +1,5 @@
-// gsr_api.hip -- the entry points of include/gsr.h: argument validation, workspace carving, stage sequencing on the caller's
-// stream, options, and the library's one error path (gsr_host.h: fail() and the message buffer gsr_last_error() returns).
+// gsr_api.hip -- the entry points of include/gsr.h: argument validation, workspace carving, options (one snapshot per call), the plan both
+// passes share, stage sequencing on the caller's stream, and the library's one error path (gsr_host.h: fail() and the buffer of gsr_last_error()).
 // Host code only.  The entry points of every other header (gsr_loss.h, gsr_optim.h, gsr_density.h, gsr_knn.h, gsr_chamfer.h,
 // gsr_sequence.h, gsr_rows.h) live in the translation unit that holds their kernels.
 #include <hip/hip_runtime.h>
@@ -36,7 +36,7 @@ static std::atomic<int> g_seg_len{256};           // entries per segment of the 
 static std::atomic<int> g_dense_pergauss{2};      // per-Gaussian backward on the Gaussians with a gradient only, zero rows filled on a second stream: 0 off, 1 on, 2 = from GSR_DENSE_MIN_P Gaussians
 static std::atomic<int> g_prefill_at{1};           // announced gradient outputs (gsr_backward_prefill): zero-filled 1 = beside the forward compositing kernel, 2 = beside the list-ordering kernel already, 0 = announcements ignored
 static std::atomic<int> g_dense_fork{2};           // dense per-Gaussian stage: 1 = the second stream is forked after the accumulator rows are cleared, 0 = before, 2 = after below GSR_DENSE_FORK_EARLY_P Gaussians
-static std::atomic<int> g_fwd_pair_long{-1};       // forward pass on small images (seg_plan: persistent reverse kernel in use): half tiles whose list exceeds this many entries are walked by two waves, one per block; 0 = off, -1 = GSR_PAIR_LONG_DEFAULT
+static std::atomic<int> g_fwd_pair_long{-1};       // forward pass on small images (make_plan: persistent reverse kernel in use): half tiles whose list exceeds this many entries are walked by two waves, one per block; 0 = off, -1 = GSR_PAIR_LONG_DEFAULT
 static std::atomic<int> g_bwd_lpt{1};             // large images: the reverse pass's half tiles in order of decreasing length (composite_bwd_lpt_kernel); 0 = in tile order
 static std::atomic<int> g_asm_walk{1};            // 1: compositing walks written in gfx950 assembly where they exist (same results, bit for bit), 0: the C++ walks
 static std::atomic<int> g_fill_in_tail{0};        // 1: with the persistent reverse kernel, the zero rows of Gaussians without a gradient are written by its idle waves
@@ -46,10 +46,6 @@ static std::atomic<int> g_persistent_bwd{2};      // persistent reverse composit
                                                   // than 1.5 times over and the longest chain, not the throughput, sets the kernel's time (measured: -25 % at 800 x 800,
                                                   // -10 % at 1600 x 900, +-0 at 1080p and 4K where the classic kernel's second generation of waves hides the long chains)
 #define GSR_PERSISTENT_MAX_TILES 6144
-// what gsr_forward and gsr_backward decide from the image size and the options alone: is the segmented machinery on, with what
-// segment length (the forward pass then takes checkpoints and leaves the half tiles' lengths), is the reverse kernel the persistent one
-struct SegPlan { int seg_len; bool persistent_bwd, small_image; };
-static SegPlan seg_plan(int W, int H);
 #define GSR_DEPTH_BUCKETS_MIN_P 1024           // measured at P = 10 k: 25 us against 48 us for rocPRIM sort + scan + copy-back
 
 // State that adapts to what a device has rendered lives per DEVICE, not per process: a frame with depth outliers on one
@@ -73,12 +69,15 @@ struct DeviceState {
     struct Prefill { bool pending = false, done = false; int P = 0, M = 0; float *p[9] = {nullptr}; } prefill;
 };
 static DeviceState g_dev[GSR_MAX_DEVICES];
-static DeviceState &dev_state();
+static DeviceState &dev_state() {
+    int d = 0;
+    if (hipGetDevice(&d) != hipSuccess || d < 0) d = 0;
+    return g_dev[d % GSR_MAX_DEVICES];
+}
 // device buffer of the instrumented compositing kernels (debug facility: the only allocation the library makes besides
-// its pinned read-back words); NULL when counting is off or the allocation failed
-static CompositeCounters *lane_counters(int which) {
-    if (!g_count_lanes.load()) return nullptr;
-    DeviceState &ds = dev_state();
+// its pinned read-back words); NULL when counting is off (count_lanes: the call's Options) or the allocation failed
+static CompositeCounters *lane_counters(DeviceState &ds, int count_lanes, int which) {
+    if (!count_lanes) return nullptr;
     std::lock_guard<std::mutex> lk(ds.mu);
     if (!ds.counters) {
         // two counter blocks, then two per-unit trace arrays (wave timeline of the instrumented kernels)
@@ -94,11 +93,6 @@ static CompositeCounters *lane_counters(int which) {
         (void)hipMemcpy(ds.counters, h, sizeof(h), hipMemcpyHostToDevice);
     }
     return ds.counters + which;
-}
-static DeviceState &dev_state() {
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0) d = 0;
-    return g_dev[d % GSR_MAX_DEVICES];
 }
 // the device's second stream and its two events, made on first use (false: could not be made -- the caller keeps everything on one stream)
 static bool side_stream(DeviceState &ds) {
@@ -116,10 +110,92 @@ static bool side_stream(DeviceState &ds) {
     }
     return true;
 }
+// ---- gsr_forward's side of gsr_backward_prefill: take the announcement, fork the fill, publish it as done.  The zeros of the announced
+// gradient outputs are written on the device's second stream beside the forward pass's last kernels (half of the CUs idle under the
+// list-ordering kernel, most of them in the compositing kernel's tail) instead of beside the reverse compositing kernel, whose waves leave
+// no slot free until it drains.  The call's copy `pre` uses the flags for itself: pending = to be filled by this call, done = filled. ----
+// joins an earlier render's fill that no gsr_backward took over; pre->pending = announced for this (P, M), `wanted`, and there is a second stream
+static int32_t prefill_take(DeviceState &ds, hipStream_t s, bool wanted, int P, int M, DeviceState::Prefill *pre) {
+    std::lock_guard<std::mutex> lk(ds.mu);
+    if (ds.prefill.done) {
+        ds.prefill.done = false;
+        if (hipStreamWaitEvent(s, ds.ev_prefill, 0) != hipSuccess) return fail(GSR_ERR_HIP, "prefill join");
+    }
+    if (!ds.prefill.pending) return GSR_OK;
+    ds.prefill.pending = false;
+    *pre = ds.prefill;
+    pre->pending = wanted && pre->P == P && pre->M == M && pre->p[5] && !pre->p[6] && side_stream(ds);
+    return GSR_OK;
+}
+static int32_t prefill_fork(DeviceState &ds, hipStream_t s, const float *shs, DeviceState::Prefill *pre) {      // at most once per call
+    if (!pre->pending) return GSR_OK;
+    pre->pending = false;
+    std::lock_guard<std::mutex> lk(ds.mu);
+    PergaussBwdArgs fa{};
+    fa.P = pre->P; fa.M = pre->M; fa.shs = shs; fa.dL_dmeans2D = pre->p[0]; fa.dL_dopacity = pre->p[1]; fa.dL_dcolors = pre->p[2];
+    fa.dL_dmeans3D = pre->p[3]; fa.dL_dcov3D = pre->p[4]; fa.dL_dsh = pre->p[5]; fa.dL_dscales = pre->p[7]; fa.dL_drots = pre->p[8];
+    HIP_TRY(hipEventRecord(ds.ev_fork, s), "prefill fork event");
+    HIP_TRY(hipStreamWaitEvent(ds.side, ds.ev_fork, 0), "prefill fork wait");
+    HIP_TRY(launch_fill_zero(fa, ds.side), "gradient zero-fill launch");
+    HIP_TRY(hipEventRecord(ds.ev_prefill, ds.side), "prefill event");
+    pre->done = true;
+    return GSR_OK;
+}
+// joined by the gsr_backward that takes the buffers over, or by the next call on the device (the fill's tail runs on between the passes)
+static void prefill_publish(DeviceState &ds, const DeviceState::Prefill &pre) {
+    if (!pre.done) return;
+    std::lock_guard<std::mutex> lk(ds.mu);
+    ds.prefill = pre;
+}
 #define GSR_PAIR_LONG_DEFAULT 64
 #define GSR_LPT_SPAN 512              // length classes of the reverse pass's order on large images: 16 of 32 entries (SegView, plan_units)
 #define GSR_DENSE_MIN_P 500000
 #define GSR_DENSE_FORK_EARLY_P 2000000
+
+// One call's view of the options: gsr_forward, gsr_backward and gsr_backward_workspace_bytes make one at their top, which reads every atomic
+// once, and decide everything from it, so that a gsr_set_option from another thread cannot give one call two answers.
+struct Options {
+    const int profiling = g_profiling.load(), exact_cull = g_exact_cull.load(), bwd_npx = g_bwd_npx.load(), fwd_npx = g_fwd_npx.load(), wpb = g_wpb.load(),
+              two_level_sort = g_two_level_sort.load(), tile_lists = g_tile_lists.load(), depth_buckets = g_depth_buckets.load(),
+              count_lanes = g_count_lanes.load(), deterministic_bwd = g_deterministic_bwd.load(), seg_len = g_seg_len.load(),
+              dense_pergauss = g_dense_pergauss.load(), prefill_at = g_prefill_at.load(), dense_fork = g_dense_fork.load(), fwd_pair_long = g_fwd_pair_long.load(),
+              bwd_lpt = g_bwd_lpt.load(), asm_walk = g_asm_walk.load(), fill_in_tail = g_fill_in_tail.load(), persistent_bwd = g_persistent_bwd.load();
+};
+
+// What gsr_forward and gsr_backward must agree on, decided in this one place from the options, P and the image size alone: the forward
+// pass leaves checkpoints, half-tile lengths and zero-filled outputs only where the reverse pass of the same (options, P, W, H) uses them.
+// Each pass adds what only it can know (R > 0, deterministic buffers, lane counters, pointers, workspace sizes).  Where their rules differ, each keeps its own:
+//   - length order: the forward pass files the lengths under `lpt_span && seg_len == 0 && T <= 1 << 28`, the reverse pass reads them under
+//     `lpt_span && !persistent` (+ its own conjuncts, no bound on T).  seg_len == 0 is not !persistent_bwd: with deterministic_bwd or
+//     segment_entries 0 under persistent_bwd 1, a large image's forward pass files lengths that the persistent kernel never reads
+//   - dense stage: the forward pass prefills under `dense_wanted` and a short test of its own (SH colours in one tensor of M == 16,
+//     scales and rotations, dL_dsh announced without dL_dsh_rest), the reverse pass asks pergauss_dense_eligible()
+struct Plan {
+    int gridx, gridy, T;      // tiles; T as the forward pass has always computed it (int)
+    bool small_image;         // at most GSR_PERSISTENT_MAX_TILES tiles: the longest chain, not the throughput, sets the compositing kernels' time
+    bool persistent_bwd;      // the reverse compositing kernel is the persistent one (gsr_backward: and R > 0)
+    int seg_len;              // > 0: the forward pass takes checkpoints every seg_len entries and leaves the half tiles' lengths for that kernel
+    int pair_long_n;          // > 0: the forward pass walks half tiles with more entries than this by two waves, one per block
+    int lpt_span;             // > 0: image and options allow the reverse pass's half tiles in order of decreasing length (composite_bwd_lpt_kernel)
+    bool dense_wanted;        // dense_pergauss says the per-Gaussian stage runs on the Gaussians with a gradient only
+};
+static inline int grid_dim(int px) { return (int)(((long long)px + GSR_TILE_HOST - 1) / GSR_TILE_HOST); }      // (the plan is made before W and H are checked)
+static Plan make_plan(const Options &o, int P, int W, int H) {
+    Plan p;
+    p.gridx = grid_dim(W); p.gridy = grid_dim(H);
+    const long long T = (long long)p.gridx * p.gridy;
+    p.T = (int)T; p.small_image = T <= GSR_PERSISTENT_MAX_TILES;
+    const bool pk = (o.persistent_bwd == 1 || (o.persistent_bwd == 2 && p.small_image)) && T <= (1 << 28);
+    p.persistent_bwd = pk && o.bwd_npx == 2;
+    // not under deterministic_bwd: which half tiles get checkpoints once the pool runs out is a race between the forward waves, and a
+    // segment that starts from a stored transmittance differs in the last bits from the same entries reached by dividing back
+    p.seg_len = pk && o.fwd_npx == 2 && !o.deterministic_bwd ? o.seg_len : 0;
+    // long lists by pairs of block waves: only where the longest list sets the kernel's time (the images the persistent reverse kernel serves)
+    p.pair_long_n = p.small_image && o.fwd_npx == 2 ? (o.fwd_pair_long < 0 ? GSR_PAIR_LONG_DEFAULT : o.fwd_pair_long) : 0;
+    p.lpt_span = !p.small_image && o.bwd_lpt && o.fwd_npx == 2 && o.bwd_npx == 2 ? GSR_LPT_SPAN : 0;
+    p.dense_wanted = o.dense_pergauss == 1 || (o.dense_pergauss == 2 && P >= GSR_DENSE_MIN_P);
+    return p;
+}
 static const char *const k_stage_names[GSR_NUM_STAGES] = {
     // lists.bin = entries binned per super-tile (count + scan + scatter; round 1's path: depth order + scan); lists.order = per-super-tile order +
     // expansion into the tile lists (sort path: the radix sort); emit_keys / ranges only run on the sort path
@@ -133,127 +209,87 @@ int fail(int code, const char *fmt, ...) {      // gsr_host.h: every entry point
     va_end(ap);
     return code;
 }
+#define GSR_TRY(expr) do { const int32_t _rc = (expr); if (_rc != GSR_OK) return _rc; } while (0)
+static int32_t hip_rc(hipError_t e, const char *what) { HIP_TRY(e, what); return GSR_OK; }      // the last HIP call of a function
+
+struct Bump {      // hands out consecutive 256-byte-aligned pieces of a workspace; base NULL: only the sizes are wanted
+    char *base; size_t off;
+    template <class T> T *take(size_t count) { char *r = base ? base + off : nullptr; off += align_up(count * sizeof(T)); return (T *)r; }
+};
 
 GeomView carve_geom(void *base, int P, size_t scan_tb, size_t dsort_tb) {
     GeomView g;
     const size_t n = (size_t)(P > 0 ? P : 1);
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += align_up(bytes); return r; };
-    g.rec = (float *)take(n * GSR_REC_FLOATS * sizeof(float));
-    g.depth = (float *)take(n * sizeof(float));
-    g.opac = (float *)take(n * sizeof(float));
-    g.rect = (uint4 *)take(n * sizeof(uint4));
-    g.tiles = (uint32_t *)take(n * sizeof(uint32_t));
-    g.offsets = (uint32_t *)take(n * sizeof(uint32_t));
-    g.clamped = (uint8_t *)take(n);
-    g.perm = (uint32_t *)take(n * sizeof(uint32_t));
-    g.depth_sorted = (uint32_t *)take(n * sizeof(uint32_t));
-    g.orect = (uint4 *)take(n * sizeof(uint4));
-    g.ss_rec = (uint4 *)take(n * sizeof(uint4));
-    g.hot = (uint32_t *)take(n * sizeof(uint32_t));
-    g.ss_entries = (uint4 *)take((size_t)GSR_SS_ENT_PER_G * n * sizeof(uint4));
+    Bump w = {(char *)base, 0};
+    g.rec = w.take<float>(n * GSR_REC_FLOATS); g.depth = w.take<float>(n); g.opac = w.take<float>(n);
+    g.rect = w.take<uint4>(n); g.tiles = w.take<uint32_t>(n); g.offsets = w.take<uint32_t>(n); g.clamped = w.take<uint8_t>(n);
+    g.perm = w.take<uint32_t>(n); g.depth_sorted = w.take<uint32_t>(n); g.orect = w.take<uint4>(n);
+    g.ss_rec = w.take<uint4>(n); g.hot = w.take<uint32_t>(n); g.ss_entries = w.take<uint4>((size_t)GSR_SS_ENT_PER_G * n);
     // the bin count is an image property the workspace size cannot depend on (gsr_workspace_sizes is asked per (P, W, H) but
     // carve_geom only sees P): room for GSR_SS_WGCNT_WORDS words; supertile_sort.hip is skipped when nblk * S exceeds it
-    g.ss_wg_cnt = (uint32_t *)take((size_t)GSR_SS_WGCNT_WORDS * sizeof(uint32_t));
-    g.tl_mat1 = (uint32_t *)take((size_t)GSR_TL_MAX_S * ((n + GSR_TL_L1 - 1) / GSR_TL_L1) * sizeof(uint32_t));
-    g.tl_bin_total = (uint32_t *)take(GSR_TL_MAX_S * sizeof(uint32_t));
-    g.scan_temp = take(scan_tb);
-    g.scan_temp_bytes = scan_tb;
-    g.dsort_temp = take(dsort_tb);
-    g.dsort_temp_bytes = dsort_tb;
-    const DepthOrderPlan pl = depth_order_plan(P, 0);          // npre; the bucket tables are sized for the maximum
-    g.dord.hdr = (uint32_t *)take(GSR_DO_ZERO_WORDS * sizeof(uint32_t));
+    g.ss_wg_cnt = w.take<uint32_t>(GSR_SS_WGCNT_WORDS);
+    g.tl_mat1 = w.take<uint32_t>((size_t)GSR_TL_MAX_S * ((n + GSR_TL_L1 - 1) / GSR_TL_L1)); g.tl_bin_total = w.take<uint32_t>(GSR_TL_MAX_S);
+    g.scan_temp = w.take<char>(scan_tb); g.scan_temp_bytes = scan_tb;
+    g.dsort_temp = w.take<char>(dsort_tb); g.dsort_temp_bytes = dsort_tb;
+    const size_t npre = (size_t)depth_order_plan(P, 0).npre;   // the bucket tables are sized for the maximum
+    g.dord.hdr = w.take<uint32_t>(GSR_DO_ZERO_WORDS);
     g.dord.gpair = reinterpret_cast<unsigned long long *>(g.dord.hdr + DO_HDR_WORDS);     // DO_HDR_WORDS is even: 8-byte aligned
     g.dord.gcur = g.dord.hdr + DO_HDR_WORDS + 2 * GSR_DO_MAXB;
-    g.dord.bstart = (uint32_t *)take((GSR_DO_MAXB + 1) * sizeof(uint32_t));
-    g.dord.tbase = (uint32_t *)take((GSR_DO_MAXB + 1) * sizeof(uint32_t));
-    g.dord.blkmin = (uint32_t *)take(pl.npre * sizeof(uint32_t));
-    g.dord.blkmax = (uint32_t *)take(pl.npre * sizeof(uint32_t));
-    g.dord.blkent = (uint32_t *)take(pl.npre * sizeof(uint32_t));
-    g.dord.comp = (uint64_t *)take(n * sizeof(uint64_t));
-    g.touched = (uint8_t *)take(n);
-    g.touch_mark = (uint32_t *)take(sizeof(uint32_t));
-    g.total_bytes = off;
+    g.dord.bstart = w.take<uint32_t>(GSR_DO_MAXB + 1); g.dord.tbase = w.take<uint32_t>(GSR_DO_MAXB + 1);
+    g.dord.blkmin = w.take<uint32_t>(npre); g.dord.blkmax = w.take<uint32_t>(npre); g.dord.blkent = w.take<uint32_t>(npre);
+    g.dord.comp = w.take<uint64_t>(n); g.touched = w.take<uint8_t>(n); g.touch_mark = w.take<uint32_t>(1);
+    g.total_bytes = w.off;
     return g;
+}
+static int32_t geom_view(const void *ws, int P, GeomView *g) {      // the geometry workspace as every entry point sees it (rocPRIM says the temp sizes)
+    size_t stb = 0, dtb = 0;
+    HIP_TRY(scan_temp_bytes(P, &stb), "scan temp query");
+    HIP_TRY(depth_sort_temp_bytes(P, &dtb), "depth sort temp query");
+    *g = carve_geom(const_cast<void *>(ws), P, stb, dtb);
+    return GSR_OK;
 }
 
 ImageView carve_image(void *base, int W, int H) {
     ImageView v;
     const size_t T = (size_t)((W + GSR_TILE_HOST - 1) / GSR_TILE_HOST) * ((H + GSR_TILE_HOST - 1) / GSR_TILE_HOST);
     const size_t HW = (size_t)W * H;
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += align_up(bytes); return r; };
-    v.ranges = (uint2 *)take((T > 0 ? T : 1) * sizeof(uint2));
-    v.final_T = (float *)take((HW > 0 ? HW : 1) * sizeof(float));
-    v.n_contrib = (uint32_t *)take((HW > 0 ? HW : 1) * sizeof(uint32_t));
+    Bump w = {(char *)base, 0};
+    v.ranges = w.take<uint2>(T > 0 ? T : 1); v.final_T = w.take<float>(HW > 0 ? HW : 1); v.n_contrib = w.take<uint32_t>(HW > 0 ? HW : 1);
     const size_t units = 2 * (T > 0 ? T : 1);
-    v.seg.units = (uint32_t)units;
-    v.seg.band_units = (uint32_t)((units + GSR_SEG_BANDS - 1) / GSR_SEG_BANDS);
+    v.seg.units = (uint32_t)units; v.seg.band_units = (uint32_t)((units + GSR_SEG_BANDS - 1) / GSR_SEG_BANDS);
     v.seg.pool_cap = (uint32_t)((units * GSR_SEG_POOL_PER_UNIT + GSR_SEG_BANDS - 1) / GSR_SEG_BANDS * GSR_SEG_BANDS);
-    v.seg.hdr = (uint32_t *)take(GSR_SEG_HDR_WORDS * sizeof(uint32_t));
-    v.seg.info = (uint2 *)take(units * sizeof(uint2));
-    v.seg.ck_slot = (uint32_t *)take(units * 8 * sizeof(uint32_t));
+    v.seg.hdr = w.take<uint32_t>(GSR_SEG_HDR_WORDS); v.seg.info = w.take<uint2>(units); v.seg.ck_slot = w.take<uint32_t>(units * 8);
     v.seg.list_cap = (uint32_t)((size_t)v.seg.band_units * (1 + GSR_SEG_MAXCK) + GSR_SEG_FILL_CAP);
-    v.seg.bq = (uint4 *)take((size_t)GSR_SEG_BANDS * v.seg.list_cap * sizeof(uint4));
-    v.seg.pool = (float4 *)take((size_t)v.seg.pool_cap * 128 * sizeof(float4));
-    v.total_bytes = off;
+    v.seg.bq = w.take<uint4>((size_t)GSR_SEG_BANDS * v.seg.list_cap); v.seg.pool = w.take<float4>((size_t)v.seg.pool_cap * 128);
+    v.total_bytes = w.off;
     return v;
 }
 
 BinningView carve_binning(void *base, int64_t N, size_t sort_tb) {
     BinningView b;
     const size_t n = (size_t)(N > 0 ? N : 1);
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += align_up(bytes); return r; };
-    b.point_list = (uint32_t *)take(n * sizeof(uint32_t));
-    b.contrib = (uint8_t *)take(4 * n);
-    b.list_bytes = off;
-    b.keys_sorted = (uint64_t *)take(n * sizeof(uint64_t));
-    b.keys_unsorted = (uint64_t *)take(n * sizeof(uint64_t));
-    b.point_list_unsorted = (uint32_t *)take(n * sizeof(uint32_t));
+    Bump w = {(char *)base, 0};
+    b.point_list = w.take<uint32_t>(n); b.contrib = w.take<uint8_t>(4 * n);
+    b.list_bytes = w.off;
+    b.keys_sorted = w.take<uint64_t>(n); b.keys_unsorted = w.take<uint64_t>(n); b.point_list_unsorted = w.take<uint32_t>(n);
     b.tkeys_unsorted = (uint32_t *)b.keys_sorted; b.ids_sorted = b.point_list; b.ids_unsorted = (uint32_t *)b.keys_unsorted;
     b.tkeys_sorted = b.point_list_unsorted;
-    b.sort_temp = take(sort_tb);
-    b.sort_temp_bytes = sort_tb;
-    b.total_bytes = off;
+    b.sort_temp = w.take<char>(sort_tb); b.sort_temp_bytes = sort_tb;
+    b.total_bytes = w.off;
     return b;
 }
 
 TileListView carve_tile_lists(void *base, const TileListPlan &pl, int64_t E) {
     TileListView v;
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += align_up(bytes); return r; };
+    Bump w = {(char *)base, 0};
     const size_t S = (size_t)pl.S, e = (size_t)(E > 0 ? E : 1), nseg = (size_t)(pl.nseg_max > 0 ? pl.nseg_max : 1);
-    v.binstart = (uint32_t *)take((S + 1) * sizeof(uint32_t));
-    v.segbase = (uint32_t *)take((S + 1) * sizeof(uint32_t));
-    v.seg_super = (uint32_t *)take(nseg * sizeof(uint32_t));
-    v.entries = (uint4 *)take(e * sizeof(uint4));
-    v.segcnt = (uint32_t *)take(nseg * 64 * sizeof(uint32_t));
-    v.tile_off = (uint32_t *)take(S * 64 * sizeof(uint32_t));
-    v.tile_tot = (uint32_t *)take(S * 64 * sizeof(uint32_t));
-    v.st_pairs = (uint32_t *)take(S * sizeof(uint32_t));
-    v.total_bytes = off;
+    v.binstart = w.take<uint32_t>(S + 1); v.segbase = w.take<uint32_t>(S + 1);
+    v.seg_super = w.take<uint32_t>(nseg); v.entries = w.take<uint4>(e); v.segcnt = w.take<uint32_t>(nseg * 64);
+    v.tile_off = w.take<uint32_t>(S * 64); v.tile_tot = w.take<uint32_t>(S * 64); v.st_pairs = w.take<uint32_t>(S);
+    v.total_bytes = w.off;
     return v;
 }
 
-static inline int grid_dim(int px) { return (px + GSR_TILE_HOST - 1) / GSR_TILE_HOST; }
-static SegPlan seg_plan(int W, int H) {
-    SegPlan p = {0, false, false};
-    const long long T = (long long)grid_dim(W) * grid_dim(H);
-    const int pk = g_persistent_bwd.load();
-    const bool small = T <= GSR_PERSISTENT_MAX_TILES;
-    p.persistent_bwd = (pk == 1 || (pk == 2 && small)) && g_bwd_npx.load() == 2 && T <= (1 << 28);
-    const bool fwd_seg = (pk == 1 || (pk == 2 && small)) && g_fwd_npx.load() == 2 && T <= (1 << 28);
-    // not under deterministic_bwd: which half tiles get checkpoints once the pool runs out is a race between the forward waves, and a
-    // segment that starts from a stored transmittance differs in the last bits from the same entries reached by dividing back
-    p.seg_len = fwd_seg && !g_deterministic_bwd.load() ? g_seg_len.load() : 0;
-    p.small_image = small;
-    return p;
-}
 static inline int tile_bits(int W, int H) { return ceil_log2_u32((uint32_t)(grid_dim(W) * grid_dim(H))); }
 static inline int key_bits(int W, int H) { return 32 + tile_bits(W, H); }
 // temp storage that serves either sort flavour
@@ -316,7 +352,8 @@ struct StageTimer {   // hipEvent pairs on the caller's stream; active only unde
     int idx[GSR_NUM_STAGES + 1];
     float ms_out[GSR_NUM_STAGES];
     int n = 0;
-    StageTimer(hipStream_t s_, bool on_) : s(s_), on(on_) { for (float &m : ms_out) m = -1.f; }
+    DeviceState &ds;           // where finish() files the times
+    StageTimer(hipStream_t s_, bool on_, DeviceState &ds_) : s(s_), on(on_), ds(ds_) { for (float &m : ms_out) m = -1.f; }
     void zero(int stage) { ms_out[stage] = 0.f; }
     void mark(int stage_about_to_start) {
         if (!on || n > GSR_NUM_STAGES) return;
@@ -337,7 +374,6 @@ struct StageTimer {   // hipEvent pairs on the caller's stream; active only unde
         (void)hipEventElapsedTime(&tot, ev[0], ev[n - 1]);
         ms_out[total_slot] = tot;
         {
-            DeviceState &ds = dev_state();
             std::lock_guard<std::mutex> lk(ds.mu);
             for (int i = 0; i < GSR_NUM_STAGES; i++) if (ms_out[i] >= 0.f) ds.stage_ms[i] = ms_out[i];
         }
@@ -345,6 +381,328 @@ struct StageTimer {   // hipEvent pairs on the caller's stream; active only unde
         n = 0;
     }
 };
+
+// One gsr_forward or gsr_backward call: what its stages share.  The device state is looked up, the options are read and the plan is
+// made once, here; the views are carved by carve_views() once the arguments have passed their checks.
+struct Call {
+    hipStream_t s;
+    int P, W, H, debug;
+    DeviceState &ds;
+    const Options o;
+    const Plan pl;
+    StageTimer tm;
+    GeomView g; ImageView im;                // carve_views
+    // gsr_forward only: the caller's allocator for the binning workspace with its argument, and where it wants N (may be NULL)
+    gsr_alloc_fn alloc = nullptr; void *alloc_user = nullptr; int64_t *num_rendered = nullptr;
+    DeviceState::Prefill pre;                // the announcement this render fills (prefill_take)
+    uint32_t touch_mark = 0;                 // this frame's mark for GeomView::touched
+    bool lists_done = false, tile_lists = false;   // the super-tile builder has made the lists; else: tile_lists.hip makes them (fwd_depth_order)
+    BinningView b;                           // the lists, once a builder has allocated them
+    int P_list = 0;                          // entries of the depth-ordered list (perm / offsets)
+    int64_t N = 0, E = 0;                    // (Gaussian, tile) pairs and (Gaussian, super-tile) entries of this frame
+    Call(gsr_stream_t stream, int P_, int W_, int H_, int debug_)
+        : s((hipStream_t)stream), P(P_), W(W_), H(H_), debug(debug_), ds(dev_state()), pl(make_plan(o, P_, W_, H_)),
+          tm(s, o.profiling != 0, ds) {}
+};
+static int32_t carve_views(Call &c, const void *geom_ws, size_t geom_bytes, const void *img_ws, size_t img_bytes) {
+    GSR_TRY(geom_view(geom_ws, c.P, &c.g));
+    c.im = carve_image(const_cast<void *>(img_ws), c.W, c.H);
+    if (geom_bytes < c.g.total_bytes) return fail(GSR_ERR_WORKSPACE, "geom workspace %zu < %zu", geom_bytes, c.g.total_bytes);
+    if (img_bytes < c.im.total_bytes) return fail(GSR_ERR_WORKSPACE, "image workspace %zu < %zu", img_bytes, c.im.total_bytes);
+    return GSR_OK;
+}
+
+// Reads back the four totals {overflow, Pv or largest bin, N, E} of the kernels `launch(host_out, seq)` queues: they store them into a
+// pinned slot and the host polls its sequence word, so that neither a copy nor a barrier sits between those kernels and the ones queued
+// behind them.  Without a slot (none free, or debug mode) or when the poll times out, the words are copied from the workspace header (the first
+// from [DO_OVERFLOW], the other three from `rest`; NULL: they follow the first) and the stream is synchronised.  Every path releases the slot.
+template <class Launch>
+static int32_t read_totals(Call &c, const char *what, Launch launch, const uint32_t *rest, uint32_t h[4]) {
+    ReadbackSlot *sl = c.debug ? nullptr : acquire_slot();
+    const uint32_t seq = sl ? (g_seq.fetch_add(1) | 0x80000000u) : 0u;
+    if (sl) sl->host[4] = 0u;
+    const hipError_t e = launch(sl ? sl->host : nullptr, seq);
+    if (e != hipSuccess) { release_slot(sl); return fail(GSR_ERR_HIP, "%s: %s (%d)", what, hipGetErrorString(e), (int)e); }
+    if (c.debug) HIP_TRY(hipStreamSynchronize(c.s), what);
+    c.tm.mark(2);
+    if (sl && wait_seq(sl, seq)) { h[0] = sl->host[0]; h[1] = sl->host[1]; h[2] = sl->host[2]; h[3] = sl->host[3]; release_slot(sl); return GSR_OK; }
+    hipError_t ce = hipMemcpyAsync(h, c.g.dord.hdr + DO_OVERFLOW, (rest ? 1 : 4) * sizeof(uint32_t), hipMemcpyDeviceToHost, c.s);
+    if (ce == hipSuccess && rest) ce = hipMemcpyAsync(h + 1, rest, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, c.s);
+    if (ce == hipSuccess) ce = hipStreamSynchronize(c.s);
+    if (sl) { c.ds.poll_timeouts.fetch_add(1); release_slot(sl); }      // the stream has drained: the kernel that writes the slot has finished, so it is free again
+    return ce == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "read N: %s (%d)", hipGetErrorString(ce), (int)ce);
+}
+
+// ---- gsr_forward's stages (the checks let P == 0 pass after the first two: gsr_forward then only clears the image) ----
+static int32_t fwd_check(const PreprocessArgs &a, const float *bg, const float *out_color, const void *geom_ws, const void *img_ws, gsr_alloc_fn alloc) {
+    if (a.P < 0 || a.W <= 0 || a.H <= 0 || !out_color || !bg || !a.viewmatrix || !a.projmatrix) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: bad sizes or missing bg/matrices/out_color");
+    if (a.W > 65535 * GSR_TILE_HOST || a.H > 65535 * GSR_TILE_HOST) return fail(GSR_ERR_INVALID_ARGUMENT, "image too large");
+    if (a.P == 0) return GSR_OK;
+    if (!a.means3D || !a.opacities || !a.radii || !geom_ws || !img_ws || !alloc) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: missing means3D/opacities/radii/workspaces/allocator");
+    if ((a.shs != nullptr) == (a.colors_precomp != nullptr)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: exactly one of shs / colors_precomp must be given");
+    if (((a.scales != nullptr) && (a.rotations != nullptr)) == (a.cov3D_precomp != nullptr) || ((a.scales != nullptr) != (a.rotations != nullptr)))
+        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: exactly one of (scales, rotations) / cov3D_precomp must be given");
+    if (a.shs_rest && (!a.shs || a.M < 2)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: shs_rest needs shs (= features_dc) and M >= 2");
+    if (a.raw_params && a.cov3D_precomp) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: raw_params needs scales/rotations, not cov3D_precomp");
+    if (a.shs && (a.D < 0 || a.D > 3)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: SH degree %d not in 0..3", a.D);
+    if (a.shs && a.M < (a.D + 1) * (a.D + 1)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: M=%d < (D+1)^2=%d", a.M, (a.D + 1) * (a.D + 1));
+    if (a.shs && !a.campos) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: campos required with shs");
+    return GSR_OK;
+}
+static int32_t fwd_preprocess(Call &c, PreprocessArgs &pa) {
+    pa.gridx = c.pl.gridx; pa.gridy = c.pl.gridy; pa.exact_cull = c.o.exact_cull; pa.g = c.g; pa.seg_hdr = c.im.seg.hdr;
+    pa.touch_mark = c.touch_mark = 1u + c.ds.frame_seq.fetch_add(1u) % 255u;
+    HIP_TRY(launch_preprocess_fwd(pa, c.s), "preprocess launch");
+    return c.debug ? hip_rc(hipStreamSynchronize(c.s), "preprocess") : GSR_OK;
+}
+static void fwd_totals(Call &c, uint32_t n32, uint32_t e32) { c.N = (int64_t)n32; c.E = (int64_t)e32; if (c.num_rendered) *c.num_rendered = c.N; }
+static int32_t fwd_alloc_lists(Call &c, size_t extra, char **behind) {      // point_list + contrib, and `extra` bytes behind them (*behind)
+    const size_t pl_bytes = carve_binning(nullptr, c.N, 0).list_bytes;
+    char *ptr = (char *)c.alloc(c.alloc_user, pl_bytes + extra);
+    if (!ptr) return fail(GSR_ERR_ALLOC, "binning allocator returned NULL for %zu bytes (N=%lld)", pl_bytes + extra, (long long)c.N);
+    c.b = carve_binning(ptr, c.N, 0);
+    if (behind) *behind = ptr + pl_bytes;
+    return GSR_OK;
+}
+// default: entries binned per super-tile, every bin ordered in LDS (supertile_sort.hip).  lists_done stays false where that is not
+// applicable, or a bin exceeds the LDS capacity / the entries the workspace: the frame then takes round 1's path (depth order + tile lists)
+static int32_t fwd_lists_supertile(Call &c, const float *shs) {
+    const SuperSortPlan ssp = super_sort_plan(c.P, c.W, c.H);
+    if (c.o.tile_lists != 2 || !c.o.two_level_sort || c.debug || ssp.S > GSR_SS_MAXS || ssp.chunk > GSR_SS_MAX_CHUNK ||
+        (size_t)ssp.S * ssp.nblk > (size_t)GSR_SS_WGCNT_WORDS) return GSR_OK;
+    uint32_t h[4] = {1u, 0u, 0u, 0u};
+    GSR_TRY(read_totals(c, "super-tile lists", [&](uint32_t *host_out, uint32_t seq) {
+        hipError_t e = launch_super_sort_count(c.g, c.P, c.W, c.H, c.o.exact_cull, host_out, seq, c.s);
+        if (e == hipSuccess) e = launch_super_sort_scatter(c.g, c.P, c.W, c.H, c.o.exact_cull, c.s);     // runs while the host waits for the totals
+        return e;
+    }, c.g.dord.hdr + SS_HDR_MAXBIN, h));
+    if (h[0]) {      // round 1's path shares the (now dirty) counter region
+        HIP_TRY(hipMemsetAsync(c.g.dord.hdr, 0, GSR_DO_ZERO_WORDS * sizeof(uint32_t), c.s), "reset counters");
+        c.tm.mark(1); return GSR_OK;
+    }
+    fwd_totals(c, h[2], h[3]);
+    GSR_TRY(fwd_alloc_lists(c, 0, nullptr));
+    c.tm.zero(3); c.tm.zero(5); c.tm.mark(4);
+    if (c.o.prefill_at == 2) GSR_TRY(prefill_fork(c.ds, c.s, shs, &c.pre));
+    HIP_TRY(launch_super_sort_expand(c.g, c.im, c.b.point_list, c.P, c.W, c.H, h[1], c.s), "super-tile lists: order + expand");
+    c.tm.mark(7);
+    c.lists_done = true;
+    return GSR_OK;
+}
+static int32_t fwd_depth_order_bucketed(Call &c, bool *ok) {      // depth_order.hip; !*ok: a bucket exceeds the LDS capacity -- general sort for this frame, log map next time
+    uint32_t h[4] = {1u, 0u, 0u, 0u};
+    const int log_map = c.ds.depth_log_map.load();
+    GSR_TRY(read_totals(c, "depth order", [&](uint32_t *host_out, uint32_t seq) {
+        hipError_t e = launch_depth_order_count(c.g, c.P, log_map, host_out, seq, c.s);
+        if (e == hipSuccess) e = launch_depth_order_place(c.g, c.P, log_map, c.tile_lists ? 0 : 1, c.s);   // runs while the host waits for the totals
+        if (e == hipSuccess && c.tile_lists) e = launch_tile_lists_count(c.g, c.P, c.g.dord.hdr, c.W, c.H, c.s);
+        return e;
+    }, nullptr, h));
+    *ok = !h[0];
+    if (*ok) { c.P_list = (int)h[1]; fwd_totals(c, h[2], h[3]); return GSR_OK; }
+    int cur = c.ds.bucket_fail_p.load();          // under the robust map already: stop paying for the attempt at this size
+    while (log_map && c.P < cur && !c.ds.bucket_fail_p.compare_exchange_weak(cur, c.P)) {}
+    c.ds.depth_log_map.store(1);
+    return GSR_OK;
+}
+static int32_t fwd_depth_order_general(Call &c) {      // rocPRIM's sort + scan; the totals come back by copy
+    uint32_t n32 = 0, e32 = 0;
+    HIP_TRY(launch_depth_sort(c.g, c.P, c.s), "depth sort");
+    HIP_TRY(launch_ordered_scan(c.g, c.P, c.s), "ordered scan");
+    HIP_TRY(launch_entry_total(c.g, c.P, c.s), "entry total");
+    if (c.tile_lists) HIP_TRY(launch_tile_lists_count(c.g, c.P, nullptr, c.W, c.H, c.s), "tile lists: count");
+    if (c.debug) HIP_TRY(hipStreamSynchronize(c.s), "depth order + scan");
+    c.tm.mark(2);
+    HIP_TRY(hipMemcpyAsync(&n32, c.g.offsets + (c.P - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c.s), "read N");
+    HIP_TRY(hipMemcpyAsync(&e32, c.g.dord.hdr + DO_ETOT, sizeof(uint32_t), hipMemcpyDeviceToHost, c.s), "read E");
+    HIP_TRY(hipStreamSynchronize(c.s), "read N sync");
+    c.P_list = c.P; fwd_totals(c, n32, e32);
+    return GSR_OK;
+}
+// yields P_list, N and E.  Whether tile_lists.hip will build the per-tile lists is known up front (image size, options): its level-1
+// counting is queued before the host waits for N, and the depth order then skips the scan only key emission needs
+static int32_t fwd_depth_order(Call &c) {
+    c.tile_lists = c.o.tile_lists != 0 && c.o.two_level_sort && tile_list_plan(c.P, 0, c.W, c.H).S <= GSR_TL_MAX_S;
+    bool bucketed = c.o.depth_buckets == 2 || (c.o.depth_buckets == 1 && c.P >= GSR_DEPTH_BUCKETS_MIN_P && c.P < c.ds.bucket_fail_p.load());
+    if (bucketed) GSR_TRY(fwd_depth_order_bucketed(c, &bucketed));
+    return bucketed ? GSR_OK : fwd_depth_order_general(c);
+}
+static int32_t fwd_lists_tile(Call &c) {      // per-tile lists from the depth order through (Gaussian, super-tile) entries (tile_lists.hip)
+    const TileListPlan tlp = tile_list_plan(c.P, c.E, c.W, c.H);
+    char *behind = nullptr;      // point_list first (what backward and the debug reader expect), then the entry workspace
+    GSR_TRY(fwd_alloc_lists(c, carve_tile_lists(nullptr, tlp, c.E).total_bytes, &behind));
+    const TileListView tv = carve_tile_lists(behind, tlp, c.E);
+    c.tm.zero(3); c.tm.zero(5); c.tm.mark(4);           // no key emission / range detection on this path
+    HIP_TRY(launch_tile_lists(c.g, tv, c.im, c.b.point_list, c.P, c.P_list, c.E, c.W, c.H, c.o.exact_cull, c.s), "tile lists");
+    if (c.debug) HIP_TRY(hipStreamSynchronize(c.s), "tile lists");
+    c.tm.mark(7);
+    return GSR_OK;
+}
+static int32_t fwd_lists_sorted(Call &c) {      // key emission + rocPRIM sort + range detection
+    size_t sort_tb = 0;
+    const int tbits = tile_bits(c.W, c.H) > 0 ? tile_bits(c.W, c.H) : 1;
+    HIP_TRY(any_sort_temp_bytes(c.N, c.W, c.H, &sort_tb), "sort temp query");
+    c.b = carve_binning(nullptr, c.N, sort_tb);
+    void *bin_ptr = c.alloc(c.alloc_user, c.b.total_bytes);
+    if (!bin_ptr) return fail(GSR_ERR_ALLOC, "binning allocator returned NULL for %zu bytes (N=%lld)", c.b.total_bytes, (long long)c.N);
+    c.b = carve_binning(bin_ptr, c.N, sort_tb);
+    c.tm.mark(3);
+    if (c.N > 0) {
+        HIP_TRY(launch_emit_keys(c.g, c.b, c.P_list, c.W, c.H, c.o.exact_cull, c.o.two_level_sort, c.s), "emit keys launch");
+        if (c.debug) HIP_TRY(hipStreamSynchronize(c.s), "emit keys");
+        c.tm.mark(4);
+        if (c.o.two_level_sort) HIP_TRY(launch_sort2_by_tile(c.b, c.N, tbits, c.s), "radix sort by tile");
+        else HIP_TRY(launch_sort(c.b, c.N, key_bits(c.W, c.H), c.s), "radix sort");
+        if (c.debug) HIP_TRY(hipStreamSynchronize(c.s), "radix sort");
+    }
+    c.tm.mark(5);
+    HIP_TRY(launch_ranges(c.b, c.im, c.N, c.pl.T, c.o.two_level_sort, c.s), "tile ranges");
+    if (c.debug) HIP_TRY(hipStreamSynchronize(c.s), "tile ranges");
+    c.tm.mark(7);
+    return GSR_OK;
+}
+static int32_t fwd_composite(Call &c, const float *bg, float *out_color) {
+    CompositeArgs ca;
+    ca.W = c.W; ca.H = c.H; ca.gridx = c.pl.gridx; ca.gridy = c.pl.gridy; ca.ranges = c.im.ranges; ca.point_list = c.b.point_list;
+    ca.contrib = c.b.contrib; ca.contrib_stride = (size_t)(c.N > 0 ? c.N : 1);
+    ca.rec = c.g.rec; ca.bg = bg; ca.final_T = c.im.final_T; ca.n_contrib = c.im.n_contrib; ca.out_color = out_color; ca.touched = c.g.touched; ca.touch_mark = c.touch_mark;
+    ca.counters = lane_counters(c.ds, c.o.count_lanes, 0); ca.count_mode = c.o.count_lanes;
+    // checkpoints + per-half-tile lengths for the segmented or the length-ordered reverse pass: only where gsr_backward will use them (Plan)
+    ca.seg = c.im.seg; ca.seg_len = c.pl.seg_len; ca.asm_walk = c.o.asm_walk; ca.pair_long_n = c.pl.pair_long_n;
+    ca.lpt_span = c.pl.seg_len == 0 && c.pl.T <= (1 << 28) ? c.pl.lpt_span : 0;
+    HIP_TRY(launch_composite_fwd(ca, c.o.fwd_npx, c.o.exact_cull, c.o.wpb, c.s), "composite launch");
+    return c.debug ? hip_rc(hipStreamSynchronize(c.s), "composite") : GSR_OK;
+}
+
+// ---- gsr_backward's stages, and its half of the decisions: what it adds to the shared Plan from R, the backward workspace, the lane counters and the pointers ----
+struct Reverse {
+    PergaussBwdArgs pa;            // inputs and gradient outputs as the per-Gaussian stage takes them: the checks and every stage read them here
+    int64_t R;                     // pairs the forward pass rendered
+    void *ws;                      // backward workspace: accumulator rows (acc_bytes) | deterministic mode's slots (det_bytes) | dense stage's list and records
+    size_t ws_bytes, acc_bytes, det_bytes;
+    BinningView b; CompositeCounters *counters;   // the forward pass's lists; the instrumented reverse kernel's counters, or NULL
+    bool det, persistent, lpt, dense, prefilled;
+    int bwd_asm, pk_grid, fill_chunk;
+};
+static int32_t bwd_check(const Reverse &r, const float *bg, const float *dL_dpix, const void *geom_ws, const void *img_ws, const void *binning_ws) {
+    const PergaussBwdArgs &a = r.pa;
+    if (a.P < 0 || a.W <= 0 || a.H <= 0 || r.R < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: bad sizes");
+    if (a.P == 0) return GSR_OK;      // gsr_backward then has nothing to do
+    if (!bg || !a.means3D || !a.radii || !a.viewmatrix || !a.projmatrix || !dL_dpix || !geom_ws || !img_ws || !r.ws ||
+        !a.dL_dmeans2D || !a.dL_dopacity || !a.dL_dmeans3D)
+        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: missing input, workspace or gradient buffer");
+    if ((a.colors_precomp && !a.dL_dcolors) || (a.cov3D_precomp && !a.dL_dcov3D)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: dL_dcolors / dL_dcov3D required with colors_precomp / cov3D_precomp");
+    if ((a.shs != nullptr) == (a.colors_precomp != nullptr)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: exactly one of shs / colors_precomp must be given");
+    if (((a.scales != nullptr) && (a.rotations != nullptr)) == (a.cov3D_precomp != nullptr) || ((a.scales != nullptr) != (a.rotations != nullptr)))
+        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: exactly one of (scales, rotations) / cov3D_precomp must be given");
+    if (a.shs && (!a.dL_dsh || !a.campos || a.D < 0 || a.D > 3 || a.M < (a.D + 1) * (a.D + 1))) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: SH inputs inconsistent");
+    if (a.scales && (!a.dL_dscales || !a.dL_drots)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: dL_dscales/dL_drots required");
+    if (a.shs_rest && (!a.shs || !a.dL_dsh_rest || a.M < 2)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: shs_rest needs shs, dL_dsh_rest and M >= 2");
+    if (a.raw_params && a.cov3D_precomp) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: raw_params needs scales/rotations");
+    if (r.R > 0 && !binning_ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: binning workspace missing");
+    return GSR_OK;
+}
+static int32_t bwd_workspaces(const Call &c, Reverse &r, const void *binning_ws, size_t binning_bytes) {
+    r.b = carve_binning(const_cast<void *>(binning_ws), r.R, 0);
+    if (r.R > 0 && binning_bytes < r.b.list_bytes) return fail(GSR_ERR_WORKSPACE, "binning workspace too small for R=%lld (%zu < %zu)", (long long)r.R, binning_bytes, r.b.list_bytes);
+    if (acc_rows(c.P) >= (1u << 28)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: P too large for the 28-bit accumulator row index");
+    r.acc_bytes = acc_rows(c.P) * GSR_ACC_FLOATS * sizeof(float);
+    if (r.ws_bytes < r.acc_bytes) return fail(GSR_ERR_WORKSPACE, "backward workspace %zu < %zu", r.ws_bytes, r.acc_bytes);
+    r.det = c.o.deterministic_bwd != 0 && r.R > 0;
+    r.det_bytes = r.det ? (size_t)r.R * (size_t)(4 / c.o.bwd_npx) * GSR_ACC_FLOATS * sizeof(float) : 0;
+    if (r.det && r.ws_bytes < align_up(r.acc_bytes) + r.det_bytes)
+        return fail(GSR_ERR_WORKSPACE, "deterministic_bwd: backward workspace %zu < %zu (size it with gsr_backward_workspace_bytes)", r.ws_bytes, align_up(r.acc_bytes) + r.det_bytes);
+    return GSR_OK;
+}
+static void bwd_plan(Call &c, Reverse &r) {      // which of the three reverse compositing kernels runs, and with what; the per-Gaussian stage's view of the workspaces
+    r.counters = lane_counters(c.ds, c.o.count_lanes, 1);
+    r.persistent = c.pl.persistent_bwd && r.R > 0;
+    // the written-out reverse walk addresses the accumulator rows with a 32-bit byte offset: rows < 2^26
+    r.bwd_asm = c.o.asm_walk && !r.det && (!r.counters || c.o.count_lanes == 2) && acc_rows(c.P) < (1u << 26) ? 1 : 0;
+    r.pk_grid = r.persistent ? composite_bwd_persistent_grid(c.pl.T, r.det ? 1 : 0, r.counters ? c.o.count_lanes : 0, r.bwd_asm) : 0;
+    // large images: half tiles in order of decreasing length (the forward pass filed the lengths when it ran with the same options)
+    r.lpt = c.pl.lpt_span && !r.persistent && r.bwd_asm && !r.counters && r.R > 0 && c.o.wpb == 1;
+    r.fill_chunk = r.persistent && c.o.fill_in_tail ? seg_fill_chunk(c.P) : 0;       // zero-fill units in the persistent kernel's lists
+    r.pa.rec = c.g.rec; r.pa.clamped = c.g.clamped; r.pa.opac = c.g.opac; r.pa.hot = c.g.hot; r.pa.touched = c.g.touched; r.pa.touch_mark = c.g.touch_mark;
+    r.pa.skip_unmarked = r.fill_chunk > 0 && r.R > 0 ? 1 : 0; r.pa.dense = 0;
+    r.pa.vis_count = nullptr; r.pa.vis_list = nullptr; r.pa.vis_rec = nullptr; r.pa.vis_cap = 0;
+}
+// Dense per-Gaussian stage: the zeros of every gradient output are written by a kernel of their own on the device's second stream,
+// forked by bwd_fork and joined in front of pergauss_bwd: it runs beside the compositing kernel (FP32-issue-bound, the memory system idle).
+static void bwd_dense_setup(Call &c, Reverse &r) {
+    const size_t vis_off = align_up(r.acc_bytes) + align_up(r.det_bytes);
+    r.dense = r.R > 0 && r.fill_chunk == 0 && c.pl.dense_wanted && pergauss_dense_eligible(r.pa) &&
+              r.ws_bytes >= vis_off + pergauss_vis_bytes(c.P);            // (a workspace sized before this stage existed: the streaming kernel)
+    if (!r.dense) return;
+    char *vis = (char *)r.ws + vis_off;
+    r.pa.vis_count = (uint32_t *)vis; r.pa.vis_list = (uint32_t *)(vis + 256);
+    r.pa.vis_rec = (float4 *)(vis + 256 + (((size_t)c.P * 4 + 255) / 256 * 256)); r.pa.vis_cap = pergauss_vis_cap(c.P);
+    std::lock_guard<std::mutex> lk(c.ds.mu);
+    if (!side_stream(c.ds)) r.dense = false;
+}
+// outputs the matching forward pass has zero-filled already (gsr_backward_prefill): no fill here, and the second stream's order
+// (that fill, then this call's gathering kernel, then the join event) covers it.  Any other outstanding fill is joined first.
+static int32_t bwd_take_prefill(Call &c, Reverse &r) {
+    const PergaussBwdArgs &a = r.pa;
+    r.prefilled = false;
+    std::lock_guard<std::mutex> lk(c.ds.mu);
+    if (!c.ds.prefill.done) return GSR_OK;
+    c.ds.prefill.done = false;
+    float *const outs[9] = {a.dL_dmeans2D, a.dL_dopacity, a.dL_dcolors, a.dL_dmeans3D, a.dL_dcov3D, a.dL_dsh, a.dL_dsh_rest, a.dL_dscales, a.dL_drots};
+    r.prefilled = r.dense && c.ds.prefill.P == c.P && c.ds.prefill.M == a.M && !memcmp(outs, c.ds.prefill.p, sizeof outs);
+    return r.prefilled ? GSR_OK : hip_rc(hipStreamWaitEvent(c.s, c.ds.ev_prefill, 0), "prefill join");
+}
+static int32_t bwd_fork(Call &c, const Reverse &r) {      // the second stream's work: gathering the Gaussians with a gradient, and the zeros unless the forward pass wrote them
+    std::lock_guard<std::mutex> lk(c.ds.mu);
+    HIP_TRY(hipEventRecord(c.ds.ev_fork, c.s), "fork event");
+    HIP_TRY(hipStreamWaitEvent(c.ds.side, c.ds.ev_fork, 0), "fork wait");
+    HIP_TRY(hipMemsetAsync(r.pa.vis_count, 0, 256, c.ds.side), "visible counter");
+    HIP_TRY(launch_gather_visible(r.pa, c.ds.side), "gather launch");
+    if (!r.prefilled) HIP_TRY(launch_fill_zero(r.pa, c.ds.side), "gradient zero-fill launch");
+    return hip_rc(hipEventRecord(c.ds.ev_join, c.ds.side), "join event");
+}
+// Clears the accumulator rows (and builds the unit lists of the persistent or the length-ordered kernel), with the fork before or after:
+// after, the clearing kernel has the chip to itself (7 us; 18 with the gathering kernel starting beside it) and the second stream's work
+// starts with the compositing kernel -- config 3: 4 us better; at 5 M Gaussians the second stream's work (1.2 GB of zeros, 450 k records)
+// outlasts the compositing kernel's shadow and every microsecond of head start counts: fork first (config 5: 2.37 against 2.42 ms)
+static int32_t bwd_fork_and_clear(Call &c, const Reverse &r) {
+    const int fork_late = c.o.dense_fork == 2 ? (c.P < GSR_DENSE_FORK_EARLY_P ? 1 : 0) : c.o.dense_fork;
+    if (r.dense && !fork_late) GSR_TRY(bwd_fork(c, r));
+    if (r.det) {
+        HIP_TRY(hipMemsetAsync(r.ws, 0, align_up(r.acc_bytes) + r.det_bytes, c.s), "zero accumulators");
+        if (r.persistent) HIP_TRY(launch_zero_marked_rows(c.P, c.g.touched, c.g.touch_mark, (float *)r.ws, 0, c.im.seg, r.pk_grid, r.fill_chunk, c.s), "unit lists");
+    } else HIP_TRY(launch_zero_marked_rows(c.P, c.g.touched, c.g.touch_mark, (float *)r.ws, acc_rows(c.P), c.im.seg, r.persistent ? r.pk_grid : (r.lpt ? 1 : 0), r.fill_chunk, c.s), "zero accumulators");
+    return r.dense && fork_late ? bwd_fork(c, r) : GSR_OK;
+}
+static int32_t bwd_composite(Call &c, const Reverse &r, const float *bg, const float *dL_dpix) {
+    if (r.R <= 0) return GSR_OK;
+    const PergaussBwdArgs &a = r.pa;
+    CompositeBwdArgs ca;
+    ca.W = c.W; ca.H = c.H; ca.gridx = c.pl.gridx; ca.gridy = c.pl.gridy; ca.ranges = c.im.ranges; ca.point_list = r.b.point_list;
+    ca.contrib = r.b.contrib; ca.contrib_stride = (size_t)r.R;
+    ca.rec = c.g.rec; ca.bg = bg; ca.final_T = c.im.final_T; ca.n_contrib = c.im.n_contrib; ca.dL_dpix = dL_dpix;
+    ca.acc = (float *)r.ws; ca.counters = r.counters; ca.count_mode = c.o.count_lanes;
+    ca.det = r.det ? (float *)((char *)r.ws + align_up(r.acc_bytes)) : nullptr;
+    ca.P = c.P; ca.rect = c.g.rect; ca.tiles = c.g.tiles; ca.depth_bits = reinterpret_cast<const uint32_t *>(c.g.depth);
+    ca.seg = c.im.seg; ca.asm_walk = r.bwd_asm;
+    ca.fill.P = c.P; ca.fill.M = a.M; ca.fill.chunk = r.fill_chunk; ca.fill.radii = a.radii; ca.fill.touched = c.g.touched; ca.fill.mark = c.g.touch_mark;
+    ca.fill.means2D = a.dL_dmeans2D; ca.fill.opacity = a.dL_dopacity; ca.fill.colors = a.dL_dcolors; ca.fill.means3D = a.dL_dmeans3D;
+    ca.fill.cov3D = a.dL_dcov3D; ca.fill.sh = a.shs ? a.dL_dsh : nullptr; ca.fill.sh_rest = a.shs_rest ? a.dL_dsh_rest : nullptr;
+    ca.fill.scales = a.scales ? a.dL_dscales : nullptr; ca.fill.rots = a.scales ? a.dL_drots : nullptr;
+    if (r.persistent) HIP_TRY(launch_composite_bwd_persistent(ca, r.pk_grid, c.s), "composite backward launch");
+    else if (r.lpt) HIP_TRY(launch_composite_bwd_lpt(ca, c.s), "composite backward launch");
+    else HIP_TRY(launch_composite_bwd(ca, c.o.bwd_npx, c.o.exact_cull, c.o.wpb, c.s), "composite backward launch");
+    return c.debug ? hip_rc(hipStreamSynchronize(c.s), "composite backward") : GSR_OK;
+}
+static int32_t bwd_pergauss(Call &c, Reverse &r) {      // joins the second stream in front of the per-Gaussian stage
+    if (r.dense) {
+        std::lock_guard<std::mutex> lk(c.ds.mu);
+        HIP_TRY(hipStreamWaitEvent(c.s, c.ds.ev_join, 0), "join wait");
+        r.pa.skip_unmarked = 1; r.pa.dense = 1;
+    }
+    HIP_TRY(launch_pergauss_bwd(r.pa, c.s), "per-Gaussian backward launch");
+    return c.debug ? hip_rc(hipStreamSynchronize(c.s), "per-Gaussian backward") : GSR_OK;
+}
 
 }  // namespace gsr
 
@@ -425,10 +783,9 @@ int32_t gsr_get_stage_times(const char **names, float *ms) {
 int32_t gsr_workspace_sizes(int32_t P, int32_t W, int32_t H, size_t *geom_bytes, size_t *img_bytes, size_t *bwd_bytes) {
     if (P < 0 || W <= 0 || H <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_workspace_sizes: P=%d W=%d H=%d", P, W, H);
     if (W > 65535 * GSR_TILE_HOST || H > 65535 * GSR_TILE_HOST) return fail(GSR_ERR_INVALID_ARGUMENT, "image too large");
-    size_t stb = 0, dtb = 0;
-    HIP_TRY(scan_temp_bytes(P, &stb), "scan temp query");
-    HIP_TRY(depth_sort_temp_bytes(P, &dtb), "depth sort temp query");
-    if (geom_bytes) *geom_bytes = carve_geom(nullptr, P, stb, dtb).total_bytes;
+    GeomView g;
+    GSR_TRY(geom_view(nullptr, P, &g));
+    if (geom_bytes) *geom_bytes = g.total_bytes;
     if (img_bytes) *img_bytes = carve_image(nullptr, W, H).total_bytes;
     if (bwd_bytes) *bwd_bytes = align_up(acc_rows(P) * GSR_ACC_FLOATS * sizeof(float));
     return GSR_OK;
@@ -436,8 +793,9 @@ int32_t gsr_workspace_sizes(int32_t P, int32_t W, int32_t H, size_t *geom_bytes,
 
 int32_t gsr_backward_workspace_bytes(int32_t P, int64_t R, size_t *bytes) {
     if (P < 0 || R < 0 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_workspace_bytes: bad argument");
+    const Options o{};
     const size_t acc_bytes = align_up(acc_rows(P) * GSR_ACC_FLOATS * sizeof(float));
-    const size_t det_bytes = g_deterministic_bwd.load() ? (size_t)R * (size_t)(4 / g_bwd_npx.load()) * GSR_ACC_FLOATS * sizeof(float) : 0;
+    const size_t det_bytes = o.deterministic_bwd ? (size_t)R * (size_t)(4 / o.bwd_npx) * GSR_ACC_FLOATS * sizeof(float) : 0;
     // + the dense per-Gaussian stage's list and record buffer (pergauss_bwd.hip), behind the accumulators
     *bytes = acc_bytes + align_up(det_bytes) + pergauss_vis_bytes(P);
     return GSR_OK;
@@ -459,261 +817,32 @@ int32_t gsr_forward(gsr_stream_t stream, int32_t P, int32_t D, int32_t M, int32_
                     size_t geom_bytes, gsr_alloc_fn binning_alloc, void *binning_user, void *img_ws, size_t img_bytes,
                     int64_t *num_rendered, const float *shs_rest, int32_t raw_params) {
     (void)prefiltered;   // culled Gaussians are always skipped, as with prefiltered=False (the only value the reference passes)
-    hipStream_t s = (hipStream_t)stream;
-    if (num_rendered) *num_rendered = 0;
-    // Gradient outputs announced for this render's backward call (gsr_backward_prefill): their zeros are written on the device's second
-    // stream beside this pass's last kernels (half of the CUs idle under the list-ordering kernel, most of them in the compositing
-    // kernel's tail) instead of beside the reverse compositing kernel, whose waves leave no slot free until it drains.  Only where
-    // gsr_backward will take the dense per-Gaussian stage (same rule as there), which is what needs the zeros.
-    DeviceState::Prefill pre;
-    bool prefill = false, prefilled = false;
-    {
-        DeviceState &d0 = dev_state();
-        std::lock_guard<std::mutex> lk(d0.mu);
-        if (d0.prefill.done) {       // an earlier render's fill that no gsr_backward took over: ordered before everything this call writes
-            d0.prefill.done = false;
-            if (hipStreamWaitEvent(s, d0.ev_prefill, 0) != hipSuccess) return fail(GSR_ERR_HIP, "prefill join");
-        }
-        if (d0.prefill.pending) {
-            d0.prefill.pending = false;
-            const int dopt = g_dense_pergauss.load();
-            pre = d0.prefill;
-            prefill = g_prefill_at.load() != 0 && P > 0 && pre.P == P && pre.M == M && !debug && (dopt == 1 || (dopt == 2 && P >= GSR_DENSE_MIN_P)) &&
-                      shs && !shs_rest && M == 16 && scales && rotations && pre.p[5] && !pre.p[6] && side_stream(d0);
-        }
-    }
-    if (P < 0 || W <= 0 || H <= 0 || !out_color || !bg || !viewmatrix || !projmatrix)
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: bad sizes or missing bg/matrices/out_color");
-    if (W > 65535 * GSR_TILE_HOST || H > 65535 * GSR_TILE_HOST) return fail(GSR_ERR_INVALID_ARGUMENT, "image too large");
-    const size_t HW = (size_t)W * H;
-    if (P == 0) {   // upstream returns a zero image, not the background, when there is nothing to draw
-        HIP_TRY(hipMemsetAsync(out_color, 0, 3 * HW * sizeof(float), s), "memset out_color");
-        return GSR_OK;
-    }
-    if (!means3D || !opacities || !radii || !geom_ws || !img_ws || !binning_alloc)
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: missing means3D/opacities/radii/workspaces/allocator");
-    if ((shs != nullptr) == (colors_precomp != nullptr))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: exactly one of shs / colors_precomp must be given");
-    if (((scales != nullptr) && (rotations != nullptr)) == (cov3D_precomp != nullptr) || ((scales != nullptr) != (rotations != nullptr)))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: exactly one of (scales, rotations) / cov3D_precomp must be given");
-    if (shs_rest && (!shs || M < 2)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: shs_rest needs shs (= features_dc) and M >= 2");
-    if (raw_params && cov3D_precomp) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: raw_params needs scales/rotations, not cov3D_precomp");
-    if (shs) {
-        if (D < 0 || D > 3) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: SH degree %d not in 0..3", D);
-        if (M < (D + 1) * (D + 1)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: M=%d < (D+1)^2=%d", M, (D + 1) * (D + 1));
-        if (!campos) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward: campos required with shs");
-    }
-    size_t stb = 0, dtb = 0;
-    HIP_TRY(scan_temp_bytes(P, &stb), "scan temp query");
-    HIP_TRY(depth_sort_temp_bytes(P, &dtb), "depth sort temp query");
-    GeomView g = carve_geom(geom_ws, P, stb, dtb);
-    ImageView im = carve_image(img_ws, W, H);
-    if (geom_bytes < g.total_bytes) return fail(GSR_ERR_WORKSPACE, "geom workspace %zu < %zu", geom_bytes, g.total_bytes);
-    if (img_bytes < im.total_bytes) return fail(GSR_ERR_WORKSPACE, "image workspace %zu < %zu", img_bytes, im.total_bytes);
-    const int gridx = grid_dim(W), gridy = grid_dim(H), T = gridx * gridy;
-
-    auto prefill_now = [&]() -> int32_t {
-        if (!prefill) return GSR_OK;
-        prefill = false;
-        DeviceState &d0 = dev_state();
-        std::lock_guard<std::mutex> lk(d0.mu);
-        PergaussBwdArgs fa{};
-        fa.P = P; fa.M = M; fa.shs = shs;
-        fa.dL_dmeans2D = pre.p[0]; fa.dL_dopacity = pre.p[1]; fa.dL_dcolors = pre.p[2]; fa.dL_dmeans3D = pre.p[3]; fa.dL_dcov3D = pre.p[4];
-        fa.dL_dsh = pre.p[5]; fa.dL_dscales = pre.p[7]; fa.dL_drots = pre.p[8];
-        HIP_TRY(hipEventRecord(d0.ev_fork, s), "prefill fork event");
-        HIP_TRY(hipStreamWaitEvent(d0.side, d0.ev_fork, 0), "prefill fork wait");
-        HIP_TRY(launch_fill_zero(fa, d0.side), "gradient zero-fill launch");
-        HIP_TRY(hipEventRecord(d0.ev_prefill, d0.side), "prefill event");
-        prefilled = true;
-        return GSR_OK;
-    };
-
-    StageTimer tm(s, g_profiling.load() != 0);
-    tm.mark(0);
+    Call c(stream, P, W, H, debug);
+    c.alloc = binning_alloc; c.alloc_user = binning_user; c.num_rendered = num_rendered;
+    fwd_totals(c, 0u, 0u);
     PreprocessArgs pa;
-    pa.P = P; pa.D = D; pa.M = M; pa.W = W; pa.H = H; pa.gridx = gridx; pa.gridy = gridy;
-    pa.raw_params = raw_params ? 1 : 0; pa.shs_rest = shs_rest;
-    pa.means3D = means3D; pa.shs = shs; pa.colors_precomp = colors_precomp; pa.opacities = opacities;
-    pa.scales = scales; pa.rotations = rotations; pa.cov3D_precomp = cov3D_precomp;
-    pa.viewmatrix = viewmatrix; pa.projmatrix = projmatrix; pa.campos = campos;
-    pa.scale_modifier = scale_modifier; pa.tanfovx = tanfovx; pa.tanfovy = tanfovy; pa.radii = radii; pa.exact_cull = g_exact_cull.load(); pa.g = g;
-    pa.touch_mark = 1u + dev_state().frame_seq.fetch_add(1u) % 255u;
-    pa.seg_hdr = im.seg.hdr;
-    HIP_TRY(launch_preprocess_fwd(pa, s), "preprocess launch");
-    if (debug) HIP_TRY(hipStreamSynchronize(s), "preprocess");
-    tm.mark(1);
-    uint32_t n32 = 0, e32 = 0;
-    const int two_level = g_two_level_sort.load();
-    const int tl_mode = g_tile_lists.load();
-    DeviceState &ds = dev_state();
-    BinningView b;
-    bool lists_done = false;
-    // ---- default: entries binned per super-tile, every bin ordered in LDS (supertile_sort.hip) ----
-    const SuperSortPlan ssp = super_sort_plan(P, W, H);
-    if (tl_mode == 2 && two_level && !debug && ssp.S <= GSR_SS_MAXS && ssp.chunk <= GSR_SS_MAX_CHUNK &&
-        (size_t)ssp.S * ssp.nblk <= (size_t)GSR_SS_WGCNT_WORDS) {
-        uint32_t h[4] = {1u, 0u, 0u, 0u};
-        ReadbackSlot *sl = acquire_slot();
-        const uint32_t seq = sl ? (g_seq.fetch_add(1) | 0x80000000u) : 0u;
-        if (sl) sl->host[4] = 0u;
-        hipError_t e = launch_super_sort_count(g, P, W, H, pa.exact_cull, sl ? sl->host : nullptr, seq, s);
-        if (e == hipSuccess) e = launch_super_sort_scatter(g, P, W, H, pa.exact_cull, s);     // runs while the host waits for the totals
-        if (e != hipSuccess) { release_slot(sl); return fail(GSR_ERR_HIP, "super-tile lists: %s (%d)", hipGetErrorString(e), (int)e); }
-        tm.mark(2);
-        if (sl && wait_seq(sl, seq)) {
-            h[0] = sl->host[0]; h[1] = sl->host[1]; h[2] = sl->host[2]; h[3] = sl->host[3];
-            release_slot(sl);
-        } else {
-            uint32_t w4[4] = {0u, 0u, 0u, 0u};
-            hipError_t ce = hipMemcpyAsync(w4, g.dord.hdr + DO_OVERFLOW, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-            if (ce == hipSuccess) ce = hipMemcpyAsync(w4 + 1, g.dord.hdr + SS_HDR_MAXBIN, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-            if (ce == hipSuccess) ce = hipStreamSynchronize(s);
-            if (sl) { ds.poll_timeouts.fetch_add(1); release_slot(sl); }
-            if (ce != hipSuccess) return fail(GSR_ERR_HIP, "read N: %s (%d)", hipGetErrorString(ce), (int)ce);
-            h[0] = w4[0]; h[1] = w4[1]; h[2] = w4[2]; h[3] = w4[3];
-        }
-        if (!h[0]) {
-            n32 = h[2]; e32 = h[3];
-            const int64_t N = (int64_t)n32;
-            if (num_rendered) *num_rendered = N;
-            const size_t pl_bytes = carve_binning(nullptr, N, 0).list_bytes;   // point_list + contrib
-            char *bin_ptr = (char *)binning_alloc(binning_user, pl_bytes);
-            if (!bin_ptr) return fail(GSR_ERR_ALLOC, "binning allocator returned NULL for %zu bytes (N=%lld)", pl_bytes, (long long)N);
-            b = carve_binning(bin_ptr, N, 0);
-            tm.zero(3); tm.zero(5);
-            tm.mark(4);
-            if (g_prefill_at.load() == 2) { const int32_t rc = prefill_now(); if (rc != GSR_OK) return rc; }
-            HIP_TRY(launch_super_sort_expand(g, im, b.point_list, P, W, H, h[1], s), "super-tile lists: order + expand");
-            tm.mark(7);
-            lists_done = true;
-        } else {
-            // a bin beyond the LDS capacity or more entries than the workspace holds: this frame takes round 1's path, which
-            // shares the (now dirty) counter region
-            HIP_TRY(hipMemsetAsync(g.dord.hdr, 0, GSR_DO_ZERO_WORDS * sizeof(uint32_t), s), "reset counters");
-            tm.mark(1);
-        }
+    pa.P = P; pa.D = D; pa.M = M; pa.W = W; pa.H = H; pa.raw_params = raw_params ? 1 : 0; pa.shs_rest = shs_rest; pa.radii = radii;
+    pa.means3D = means3D; pa.shs = shs; pa.colors_precomp = colors_precomp; pa.opacities = opacities; pa.scales = scales; pa.rotations = rotations;
+    pa.cov3D_precomp = cov3D_precomp; pa.viewmatrix = viewmatrix; pa.projmatrix = projmatrix; pa.campos = campos;
+    pa.scale_modifier = scale_modifier; pa.tanfovx = tanfovx; pa.tanfovy = tanfovy;
+    // an announcement is consumed whatever becomes of this call, and filled only where gsr_backward will take the dense per-Gaussian stage
+    const bool fill = c.o.prefill_at != 0 && P > 0 && !debug && c.pl.dense_wanted && shs && !shs_rest && M == 16 && scales && rotations;
+    GSR_TRY(prefill_take(c.ds, c.s, fill, P, M, &c.pre));
+    GSR_TRY(fwd_check(pa, bg, out_color, geom_ws, img_ws, binning_alloc));
+    if (P == 0) return hip_rc(hipMemsetAsync(out_color, 0, 3 * (size_t)W * H * sizeof(float), c.s), "memset out_color");   // as upstream: a zero image, not the background
+    GSR_TRY(carve_views(c, geom_ws, geom_bytes, img_ws, img_bytes));
+    c.tm.mark(0);                                    // (the stages set the marks that fall between their own launches: 2, 3, 4, 5, 7)
+    GSR_TRY(fwd_preprocess(c, pa));
+    c.tm.mark(1);
+    GSR_TRY(fwd_lists_supertile(c, shs));
+    if (!c.lists_done) {
+        GSR_TRY(fwd_depth_order(c));
+        GSR_TRY(c.tile_lists && c.N > 0 ? fwd_lists_tile(c) : fwd_lists_sorted(c));
     }
-    if (!lists_done) {
-    // whether tile_lists.hip builds the per-tile lists is known up front (image size, options): its level-1 counting
-    // is queued before the host waits for N, and the depth order then skips the scan only key emission needs
-    const bool want_tile_lists = g_tile_lists.load() != 0 && two_level && tile_list_plan(P, 0, W, H).S <= GSR_TL_MAX_S;
-    int P_list = P;                                   // entries of the depth-ordered list (perm / offsets)
-    const int dbopt = g_depth_buckets.load();
-    bool bucketed = dbopt == 2 || (dbopt == 1 && P >= GSR_DEPTH_BUCKETS_MIN_P && P < ds.bucket_fail_p.load());
-    if (bucketed) {
-        uint32_t h[4] = {1u, 0u, 0u, 0u};
-        ReadbackSlot *sl = debug ? nullptr : acquire_slot();
-        const uint32_t seq = sl ? (g_seq.fetch_add(1) | 0x80000000u) : 0u;
-        if (sl) sl->host[4] = 0u;
-        const int log_map = ds.depth_log_map.load();
-        hipError_t e = launch_depth_order_count(g, P, log_map, sl ? sl->host : nullptr, seq, s);
-        if (e == hipSuccess) e = launch_depth_order_place(g, P, log_map, want_tile_lists ? 0 : 1, s);   // runs while the host waits for the totals
-        if (e == hipSuccess && want_tile_lists) e = launch_tile_lists_count(g, P, g.dord.hdr, W, H, s);
-        if (e != hipSuccess) { release_slot(sl); return fail(GSR_ERR_HIP, "depth order: %s (%d)", hipGetErrorString(e), (int)e); }
-        if (debug) HIP_TRY(hipStreamSynchronize(s), "depth order");
-        tm.mark(2);
-        if (sl && wait_seq(sl, seq)) {
-            h[0] = sl->host[0]; h[1] = sl->host[1]; h[2] = sl->host[2]; h[3] = sl->host[3];
-            release_slot(sl);
-        } else {                                      // no slot, debug mode, or the poll timed out
-            hipError_t ce = hipMemcpyAsync(h, g.dord.hdr + DO_OVERFLOW, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-            if (ce == hipSuccess) ce = hipStreamSynchronize(s);
-            // the stream has drained: the kernel that writes the slot has finished, so the slot is free again
-            if (sl) { ds.poll_timeouts.fetch_add(1); release_slot(sl); }
-            if (ce != hipSuccess) return fail(GSR_ERR_HIP, "read N: %s (%d)", hipGetErrorString(ce), (int)ce);
-        }
-        e32 = h[3];
-        if (h[0]) {               // a bucket exceeds the LDS capacity: general sort below, log map next time
-            bucketed = false;
-            if (log_map) {        // already the robust map: stop paying for the attempt at this size
-                int cur = ds.bucket_fail_p.load();
-                while (P < cur && !ds.bucket_fail_p.compare_exchange_weak(cur, P)) {}
-            }
-            ds.depth_log_map.store(1);
-        }
-        else { P_list = (int)h[1]; n32 = h[2]; }
-    }
-    if (!bucketed) {
-        HIP_TRY(launch_depth_sort(g, P, s), "depth sort");
-        HIP_TRY(launch_ordered_scan(g, P, s), "ordered scan");
-        HIP_TRY(launch_entry_total(g, P, s), "entry total");
-        if (want_tile_lists) HIP_TRY(launch_tile_lists_count(g, P, nullptr, W, H, s), "tile lists: count");
-        if (debug) HIP_TRY(hipStreamSynchronize(s), "depth order + scan");
-        tm.mark(2);
-        HIP_TRY(hipMemcpyAsync(&n32, g.offsets + (P - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s), "read N");
-        HIP_TRY(hipMemcpyAsync(&e32, g.dord.hdr + DO_ETOT, sizeof(uint32_t), hipMemcpyDeviceToHost, s), "read E");
-        HIP_TRY(hipStreamSynchronize(s), "read N sync");
-    }
-    const int64_t N = (int64_t)n32;
-    if (num_rendered) *num_rendered = N;
-
-    size_t sort_tb = 0;
-    const int bits = key_bits(W, H);
-    const int64_t E = (int64_t)e32;
-    const TileListPlan tlp = tile_list_plan(P, E, W, H);
-    const bool tile_lists = want_tile_lists && N > 0;
-    TileListView tv;
-    if (tile_lists) {             // point_list first (what backward and the debug reader expect), then the entry workspace
-        const size_t pl_bytes = carve_binning(nullptr, N, 0).list_bytes;   // point_list + contrib
-        tv = carve_tile_lists(nullptr, tlp, E);
-        const size_t total = pl_bytes + tv.total_bytes;
-        char *bin_ptr = (char *)binning_alloc(binning_user, total);
-        if (!bin_ptr) return fail(GSR_ERR_ALLOC, "binning allocator returned NULL for %zu bytes (N=%lld)", total, (long long)N);
-        b = carve_binning(bin_ptr, N, 0);
-        tv = carve_tile_lists(bin_ptr + pl_bytes, tlp, E);
-        tm.zero(3); tm.zero(5);                         // no key emission / range detection on this path
-        tm.mark(4);
-        HIP_TRY(launch_tile_lists(g, tv, im, b.point_list, P, P_list, E, W, H, pa.exact_cull, s), "tile lists");
-        if (debug) HIP_TRY(hipStreamSynchronize(s), "tile lists");
-        tm.mark(7);
-    } else {
-        HIP_TRY(any_sort_temp_bytes(N, W, H, &sort_tb), "sort temp query");
-        b = carve_binning(nullptr, N, sort_tb);
-        void *bin_ptr = binning_alloc(binning_user, b.total_bytes);
-        if (!bin_ptr) return fail(GSR_ERR_ALLOC, "binning allocator returned NULL for %zu bytes (N=%lld)", b.total_bytes, (long long)N);
-        b = carve_binning(bin_ptr, N, sort_tb);
-        tm.mark(3);
-        if (N > 0) {
-            HIP_TRY(launch_emit_keys(g, b, P_list, W, H, pa.exact_cull, two_level, s), "emit keys launch");
-            if (debug) HIP_TRY(hipStreamSynchronize(s), "emit keys");
-            tm.mark(4);
-            if (two_level) HIP_TRY(launch_sort2_by_tile(b, N, tile_bits(W, H) > 0 ? tile_bits(W, H) : 1, s), "radix sort by tile");
-            else HIP_TRY(launch_sort(b, N, bits, s), "radix sort");
-            if (debug) HIP_TRY(hipStreamSynchronize(s), "radix sort");
-        }
-        tm.mark(5);
-        HIP_TRY(launch_ranges(b, im, N, T, two_level, s), "tile ranges");
-        if (debug) HIP_TRY(hipStreamSynchronize(s), "tile ranges");
-        tm.mark(7);
-    }
-    }
-    CompositeArgs ca;
-    ca.W = W; ca.H = H; ca.gridx = gridx; ca.gridy = gridy; ca.ranges = im.ranges; ca.point_list = b.point_list;
-    ca.contrib = b.contrib; ca.contrib_stride = (size_t)(n32 > 0 ? n32 : 1);
-    ca.rec = g.rec; ca.bg = bg; ca.final_T = im.final_T; ca.n_contrib = im.n_contrib; ca.out_color = out_color; ca.touched = g.touched; ca.touch_mark = pa.touch_mark;
-    ca.counters = lane_counters(0); ca.count_mode = g_count_lanes.load();
-    ca.seg = im.seg;
-    // checkpoints + per-half-tile lengths for the segmented reverse pass: only where gsr_backward will use them (same rule as there)
-    const SegPlan sp = seg_plan(W, H);
-    ca.seg_len = sp.seg_len;
-    ca.asm_walk = g_asm_walk.load();
-    {   // long lists by pairs of block waves: only where the longest list sets the kernel's time (the images the persistent reverse kernel serves)
-        const int pl = g_fwd_pair_long.load();
-        ca.pair_long_n = sp.small_image && g_fwd_npx.load() == 2 ? (pl < 0 ? GSR_PAIR_LONG_DEFAULT : pl) : 0;
-    }
-    ca.lpt_span = (!sp.small_image && sp.seg_len == 0 && g_bwd_lpt.load() && g_fwd_npx.load() == 2 && g_bwd_npx.load() == 2 && T <= (1 << 28)) ? GSR_LPT_SPAN : 0;
-    { const int32_t rc = prefill_now(); if (rc != GSR_OK) return rc; }
-    HIP_TRY(launch_composite_fwd(ca, g_fwd_npx.load(), pa.exact_cull, g_wpb.load(), s), "composite launch");
-    if (debug) HIP_TRY(hipStreamSynchronize(s), "composite");
-    if (prefilled) {        // joined by the gsr_backward that takes the buffers over, or by the next call on the device (no wait here: the
-                            // fill's tail runs on beside the kernels between the two passes)
-        DeviceState &d0 = dev_state();
-        std::lock_guard<std::mutex> lk(d0.mu);
-        d0.prefill = pre; d0.prefill.pending = false; d0.prefill.done = true;
-    }
-    tm.mark(-1);
-    tm.finish(11);
+    GSR_TRY(prefill_fork(c.ds, c.s, shs, &c.pre));
+    GSR_TRY(fwd_composite(c, bg, out_color));
+    prefill_publish(c.ds, c.pre);
+    c.tm.mark(-1); c.tm.finish(11);
     return GSR_OK;
 }
 
@@ -740,150 +869,29 @@ int32_t gsr_backward(gsr_stream_t stream, int32_t P, int32_t D, int32_t M, int64
                      size_t bwd_bytes, float *dL_dmeans2D, float *dL_dopacity, float *dL_dcolors, float *dL_dmeans3D,
                      float *dL_dcov3D, float *dL_dsh, float *dL_dscales, float *dL_drots, int32_t debug,
                      const float *shs_rest, int32_t raw_params, float *dL_dsh_rest) {
-    hipStream_t s = (hipStream_t)stream;
-    if (P < 0 || W <= 0 || H <= 0 || R < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: bad sizes");
-    if (P == 0) return GSR_OK;
-    if (!bg || !means3D || !radii || !viewmatrix || !projmatrix || !dL_dpix || !geom_ws || !img_ws || !bwd_ws ||
-        !dL_dmeans2D || !dL_dopacity || !dL_dmeans3D)
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: missing input, workspace or gradient buffer");
-    if ((colors_precomp && !dL_dcolors) || (cov3D_precomp && !dL_dcov3D))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: dL_dcolors / dL_dcov3D required with colors_precomp / cov3D_precomp");
-    if ((shs != nullptr) == (colors_precomp != nullptr))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: exactly one of shs / colors_precomp must be given");
-    if (((scales != nullptr) && (rotations != nullptr)) == (cov3D_precomp != nullptr) || ((scales != nullptr) != (rotations != nullptr)))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: exactly one of (scales, rotations) / cov3D_precomp must be given");
-    if (shs && (!dL_dsh || !campos || D < 0 || D > 3 || M < (D + 1) * (D + 1)))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: SH inputs inconsistent");
-    if (scales && (!dL_dscales || !dL_drots)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: dL_dscales/dL_drots required");
-    if (shs_rest && (!shs || !dL_dsh_rest || M < 2)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: shs_rest needs shs, dL_dsh_rest and M >= 2");
-    if (raw_params && cov3D_precomp) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: raw_params needs scales/rotations");
-    if (R > 0 && !binning_ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: binning workspace missing");
-    size_t stb = 0, dtb = 0;
-    HIP_TRY(scan_temp_bytes(P, &stb), "scan temp query");
-    HIP_TRY(depth_sort_temp_bytes(P, &dtb), "depth sort temp query");
-    GeomView g = carve_geom(const_cast<void *>(geom_ws), P, stb, dtb);
-    ImageView im = carve_image(const_cast<void *>(img_ws), W, H);
-    if (geom_bytes < g.total_bytes) return fail(GSR_ERR_WORKSPACE, "geom workspace %zu < %zu", geom_bytes, g.total_bytes);
-    if (img_bytes < im.total_bytes) return fail(GSR_ERR_WORKSPACE, "image workspace %zu < %zu", img_bytes, im.total_bytes);
-    const SegPlan sp = seg_plan(W, H);
-    BinningView b = carve_binning(const_cast<void *>(binning_ws), R, 0);
-    if (R > 0 && binning_bytes < b.list_bytes)
-        return fail(GSR_ERR_WORKSPACE, "binning workspace too small for R=%lld (%zu < %zu)", (long long)R, binning_bytes, b.list_bytes);
-    if (acc_rows(P) >= (1u << 28)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: P too large for the 28-bit accumulator row index");
-    const size_t acc_bytes = acc_rows(P) * GSR_ACC_FLOATS * sizeof(float);
-    if (bwd_bytes < acc_bytes) return fail(GSR_ERR_WORKSPACE, "backward workspace %zu < %zu", bwd_bytes, acc_bytes);
-    const bool det = g_deterministic_bwd.load() != 0 && R > 0;
-    const int bwd_npx = g_bwd_npx.load();
-    const size_t det_bytes = det ? (size_t)R * (size_t)(4 / bwd_npx) * GSR_ACC_FLOATS * sizeof(float) : 0;
-    if (det && bwd_bytes < align_up(acc_bytes) + det_bytes)
-        return fail(GSR_ERR_WORKSPACE, "deterministic_bwd: backward workspace %zu < %zu (size it with gsr_backward_workspace_bytes)", bwd_bytes,
-                    align_up(acc_bytes) + det_bytes);
-    const int gridx = grid_dim(W), gridy = grid_dim(H);
-    const bool persistent = sp.persistent_bwd && R > 0;
-    const SegView &segv = im.seg;
-    // the written-out reverse walk addresses the accumulator rows with a 32-bit byte offset: rows < 2^26
-    const int bwd_asm = g_asm_walk.load() && !det && (!lane_counters(1) || g_count_lanes.load() == 2) && acc_rows(P) < (1u << 26) ? 1 : 0;
-    const int pk_grid = persistent ? composite_bwd_persistent_grid(gridx * gridy, det ? 1 : 0, lane_counters(1) ? g_count_lanes.load() : 0, bwd_asm) : 0;
-    // large images: half tiles in order of decreasing length (the forward pass filed the lengths when it ran with the same options)
-    const bool lpt = !persistent && bwd_asm && !lane_counters(1) && g_bwd_lpt.load() && !sp.small_image && bwd_npx == 2 && g_fwd_npx.load() == 2 && R > 0 && g_wpb.load() == 1;
-    const int fill_chunk = persistent && g_fill_in_tail.load() ? seg_fill_chunk(P) : 0;       // zero-fill units in the persistent kernel's lists
-
-    PergaussBwdArgs pa;
-    pa.raw_params = raw_params ? 1 : 0; pa.shs_rest = shs_rest; pa.rec = g.rec; pa.dL_dsh_rest = dL_dsh_rest;
-    pa.P = P; pa.D = D; pa.M = M; pa.W = W; pa.H = H; pa.means3D = means3D; pa.shs = shs; pa.colors_precomp = colors_precomp;
-    pa.scales = scales; pa.rotations = rotations; pa.cov3D_precomp = cov3D_precomp; pa.viewmatrix = viewmatrix;
-    pa.projmatrix = projmatrix; pa.campos = campos; pa.scale_modifier = scale_modifier; pa.tanfovx = tanfovx;
-    pa.tanfovy = tanfovy; pa.radii = radii; pa.clamped = g.clamped; pa.opac = g.opac; pa.acc = (const float *)bwd_ws; pa.hot = g.hot; pa.touched = g.touched; pa.touch_mark = g.touch_mark;
-    pa.skip_unmarked = fill_chunk > 0 && R > 0 ? 1 : 0;
-    pa.dense = 0; pa.vis_count = nullptr; pa.vis_list = nullptr; pa.vis_rec = nullptr; pa.vis_cap = 0;
+    Reverse r; PergaussBwdArgs &pa = r.pa;
+    r.R = R; r.ws = bwd_ws; r.ws_bytes = bwd_bytes; pa.acc = (const float *)bwd_ws;
+    pa.raw_params = raw_params ? 1 : 0; pa.shs_rest = shs_rest; pa.dL_dsh_rest = dL_dsh_rest;
+    pa.P = P; pa.D = D; pa.M = M; pa.W = W; pa.H = H; pa.means3D = means3D; pa.shs = shs; pa.colors_precomp = colors_precomp; pa.radii = radii;
+    pa.scales = scales; pa.rotations = rotations; pa.cov3D_precomp = cov3D_precomp; pa.viewmatrix = viewmatrix; pa.projmatrix = projmatrix;
+    pa.campos = campos; pa.scale_modifier = scale_modifier; pa.tanfovx = tanfovx; pa.tanfovy = tanfovy;
     pa.dL_dmeans2D = dL_dmeans2D; pa.dL_dopacity = dL_dopacity; pa.dL_dcolors = dL_dcolors; pa.dL_dmeans3D = dL_dmeans3D;
     pa.dL_dcov3D = dL_dcov3D; pa.dL_dsh = dL_dsh; pa.dL_dscales = dL_dscales; pa.dL_drots = dL_drots;
-
-    StageTimer tm(s, g_profiling.load() != 0);
-    tm.mark(8);
-    // Dense per-Gaussian stage: the zeros of every gradient output are written by a kernel of their own on the device's second stream,
-    // forked here and joined in front of pergauss_bwd: it runs beside the compositing kernel (FP32-issue-bound, the memory system idle).
-    const int dense_opt = g_dense_pergauss.load();
-    const size_t vis_off = align_up(acc_bytes) + align_up(det_bytes);
-    bool dense = R > 0 && fill_chunk == 0 && (dense_opt == 1 || (dense_opt == 2 && P >= GSR_DENSE_MIN_P)) && pergauss_dense_eligible(pa) &&
-                 bwd_bytes >= vis_off + pergauss_vis_bytes(P);            // (a workspace sized before this stage existed: the streaming kernel)
-    if (dense) {
-        char *vis = (char *)bwd_ws + vis_off;
-        pa.vis_count = (uint32_t *)vis;
-        pa.vis_list = (uint32_t *)(vis + 256);
-        pa.vis_rec = (float4 *)(vis + 256 + (((size_t)P * 4 + 255) / 256 * 256));
-        pa.vis_cap = pergauss_vis_cap(P);
-        DeviceState &ds = dev_state();
-        std::lock_guard<std::mutex> lk(ds.mu);
-        if (!side_stream(ds)) dense = false;
-    }
-    // outputs the matching forward pass has zero-filled already (gsr_backward_prefill): no fill here, and the second stream's order
-    // (that fill, then this call's gathering kernel, then the join event) covers it.  Any other outstanding fill is joined first.
-    bool prefilled = false;
-    {
-        DeviceState &ds = dev_state();
-        std::lock_guard<std::mutex> lk(ds.mu);
-        if (ds.prefill.done) {
-            ds.prefill.done = false;
-            float *const outs[9] = {dL_dmeans2D, dL_dopacity, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscales, dL_drots};
-            prefilled = dense && ds.prefill.P == P && ds.prefill.M == M && !memcmp(outs, ds.prefill.p, sizeof outs);
-            if (!prefilled) HIP_TRY(hipStreamWaitEvent(s, ds.ev_prefill, 0), "prefill join");
-        }
-    }
-    // the fork: after the accumulator rows are cleared, the clearing kernel has the chip to itself (7 us; 18 with the gathering kernel
-    // starting beside it) and the second stream's work starts with the compositing kernel -- config 3: 4 us better; at 5 M Gaussians
-    // the second stream's work (1.2 GB of zeros, 450 k records) outlasts the compositing kernel's shadow and every microsecond of
-    // head start counts: fork first (config 5: 2.37 against 2.42 ms)
-    auto fork = [&]() -> int32_t {
-        DeviceState &ds = dev_state();
-        std::lock_guard<std::mutex> lk(ds.mu);
-        HIP_TRY(hipEventRecord(ds.ev_fork, s), "fork event");
-        HIP_TRY(hipStreamWaitEvent(ds.side, ds.ev_fork, 0), "fork wait");
-        HIP_TRY(hipMemsetAsync(pa.vis_count, 0, 256, ds.side), "visible counter");
-        HIP_TRY(launch_gather_visible(pa, ds.side), "gather launch");
-        if (!prefilled) HIP_TRY(launch_fill_zero(pa, ds.side), "gradient zero-fill launch");
-        HIP_TRY(hipEventRecord(ds.ev_join, ds.side), "join event");
-        return GSR_OK;
-    };
-    const int fork_late = g_dense_fork.load() == 2 ? (P < GSR_DENSE_FORK_EARLY_P ? 1 : 0) : g_dense_fork.load();
-    if (dense && !fork_late) { const int32_t rc = fork(); if (rc != GSR_OK) return rc; }
-    if (det) {
-        HIP_TRY(hipMemsetAsync(bwd_ws, 0, align_up(acc_bytes) + det_bytes, s), "zero accumulators");
-        if (persistent) HIP_TRY(launch_zero_marked_rows(P, g.touched, g.touch_mark, (float *)bwd_ws, 0, segv, pk_grid, fill_chunk, s), "unit lists");
-    } else HIP_TRY(launch_zero_marked_rows(P, g.touched, g.touch_mark, (float *)bwd_ws, acc_rows(P), segv, persistent ? pk_grid : (lpt ? 1 : 0), fill_chunk, s), "zero accumulators");
-    if (dense && fork_late) { const int32_t rc = fork(); if (rc != GSR_OK) return rc; }
-    tm.mark(9);
-    if (R > 0) {
-        CompositeBwdArgs ca;
-        ca.W = W; ca.H = H; ca.gridx = gridx; ca.gridy = gridy; ca.ranges = im.ranges; ca.point_list = b.point_list;
-        ca.contrib = b.contrib; ca.contrib_stride = (size_t)R;
-        ca.rec = g.rec; ca.bg = bg; ca.final_T = im.final_T; ca.n_contrib = im.n_contrib; ca.dL_dpix = dL_dpix;
-        ca.acc = (float *)bwd_ws;
-        ca.counters = lane_counters(1); ca.count_mode = g_count_lanes.load();
-        ca.det = det ? (float *)((char *)bwd_ws + align_up(acc_bytes)) : nullptr;
-        ca.P = P; ca.rect = g.rect; ca.tiles = g.tiles; ca.depth_bits = reinterpret_cast<const uint32_t *>(g.depth);
-        ca.seg = segv;
-        ca.asm_walk = bwd_asm;
-        ca.fill.P = P; ca.fill.M = M; ca.fill.chunk = fill_chunk; ca.fill.radii = radii; ca.fill.touched = g.touched; ca.fill.mark = g.touch_mark;
-        ca.fill.means2D = dL_dmeans2D; ca.fill.opacity = dL_dopacity; ca.fill.colors = dL_dcolors; ca.fill.means3D = dL_dmeans3D;
-        ca.fill.cov3D = dL_dcov3D; ca.fill.sh = shs ? dL_dsh : nullptr; ca.fill.sh_rest = shs_rest ? dL_dsh_rest : nullptr;
-        ca.fill.scales = scales ? dL_dscales : nullptr; ca.fill.rots = scales ? dL_drots : nullptr;
-        if (persistent) HIP_TRY(launch_composite_bwd_persistent(ca, pk_grid, s), "composite backward launch");
-        else if (lpt) HIP_TRY(launch_composite_bwd_lpt(ca, s), "composite backward launch");
-        else HIP_TRY(launch_composite_bwd(ca, bwd_npx, g_exact_cull.load(), g_wpb.load(), s), "composite backward launch");
-        if (debug) HIP_TRY(hipStreamSynchronize(s), "composite backward");
-    }
-    tm.mark(10);
-    if (dense) {
-        DeviceState &ds = dev_state();
-        std::lock_guard<std::mutex> lk(ds.mu);
-        HIP_TRY(hipStreamWaitEvent(s, ds.ev_join, 0), "join wait");
-        pa.skip_unmarked = 1; pa.dense = 1;
-    }
-    HIP_TRY(launch_pergauss_bwd(pa, s), "per-Gaussian backward launch");
-    if (debug) HIP_TRY(hipStreamSynchronize(s), "per-Gaussian backward");
-    tm.mark(-1);
-    tm.finish(12);
+    GSR_TRY(bwd_check(r, bg, dL_dpix, geom_ws, img_ws, binning_ws));
+    if (P == 0) return GSR_OK;
+    Call c(stream, P, W, H, debug);
+    GSR_TRY(carve_views(c, geom_ws, geom_bytes, img_ws, img_bytes));
+    GSR_TRY(bwd_workspaces(c, r, binning_ws, binning_bytes));
+    bwd_plan(c, r);
+    c.tm.mark(8);
+    bwd_dense_setup(c, r);
+    GSR_TRY(bwd_take_prefill(c, r));
+    GSR_TRY(bwd_fork_and_clear(c, r));
+    c.tm.mark(9);
+    GSR_TRY(bwd_composite(c, r, bg, dL_dpix));
+    c.tm.mark(10);
+    GSR_TRY(bwd_pergauss(c, r));
+    c.tm.mark(-1); c.tm.finish(12);
     return GSR_OK;
 }
 
@@ -891,30 +899,24 @@ int32_t gsr_mark_visible(gsr_stream_t stream, int32_t P, const float *means3D, c
                          const float *projmatrix, uint8_t *present) {
     (void)projmatrix;
     if (P < 0 || (P > 0 && (!means3D || !viewmatrix || !present))) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_mark_visible: bad argument");
-    HIP_TRY(launch_mark_visible(P, means3D, viewmatrix, present, (hipStream_t)stream), "mark_visible launch");
-    return GSR_OK;
+    return hip_rc(launch_mark_visible(P, means3D, viewmatrix, present, (hipStream_t)stream), "mark_visible launch");
 }
 
 int32_t gsr_composited_mask(gsr_stream_t stream, int32_t P, const void *geom_ws, size_t geom_bytes, uint8_t *out) {
     if (P < 0 || (P > 0 && (!geom_ws || !out))) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_composited_mask: bad argument");
     if (P == 0) return GSR_OK;
-    size_t stb = 0, dtb = 0;
-    HIP_TRY(scan_temp_bytes(P, &stb), "scan temp query");
-    HIP_TRY(depth_sort_temp_bytes(P, &dtb), "depth sort temp query");
-    const GeomView g = carve_geom(const_cast<void *>(geom_ws), P, stb, dtb);
+    GeomView g;
+    GSR_TRY(geom_view(geom_ws, P, &g));
     if (geom_bytes < g.total_bytes) return fail(GSR_ERR_WORKSPACE, "geom workspace %zu < %zu", geom_bytes, g.total_bytes);
-    HIP_TRY(launch_composited_mask(P, g.touched, g.touch_mark, out, (hipStream_t)stream), "composited mask launch");
-    return GSR_OK;
+    return hip_rc(launch_composited_mask(P, g.touched, g.touch_mark, out, (hipStream_t)stream), "composited mask launch");
 }
 
 int32_t gsr_debug_read_geom(gsr_stream_t stream, int32_t P, const void *geom_ws, float *depth, float *xy,
                             float *conic_opacity, float *rgb, uint32_t *tiles_touched, uint8_t *clamped) {
     hipStream_t s = (hipStream_t)stream;
     if (P <= 0) return GSR_OK;
-    size_t stb = 0, dtb = 0;
-    HIP_TRY(scan_temp_bytes(P, &stb), "scan temp query");
-    HIP_TRY(depth_sort_temp_bytes(P, &dtb), "depth sort temp query");
-    GeomView g = carve_geom(const_cast<void *>(geom_ws), P, stb, dtb);
+    GeomView g;
+    GSR_TRY(geom_view(geom_ws, P, &g));
     HIP_TRY(hipStreamSynchronize(s), "sync");
     float *rec = (float *)malloc((size_t)P * GSR_REC_FLOATS * sizeof(float));
     uint8_t *cl = (uint8_t *)malloc((size_t)P);
@@ -1014,10 +1016,8 @@ int32_t gsr_debug_read_bound_errors(gsr_stream_t stream, int32_t P, const void *
 #endif
     HIP_TRY(hipStreamSynchronize(s), "sync");
     if (geom_ws && P > 0) {
-        size_t stb = 0, dtb = 0;
-        HIP_TRY(scan_temp_bytes(P, &stb), "scan temp query");
-        HIP_TRY(depth_sort_temp_bytes(P, &dtb), "depth sort temp query");
-        const GeomView g = carve_geom(const_cast<void *>(geom_ws), P, stb, dtb);
+        GeomView g;
+        GSR_TRY(geom_view(geom_ws, P, &g));
         HIP_TRY(hipMemcpy(out, g.dord.hdr + GSR_DBG_GEOM_WORD, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost), "copy bound words");
     }
     if (img_ws && W > 0 && H > 0) {

@@ -1,13 +1,23 @@
-"""What the C entry points of the auxiliary headers refuse, and what they accept without launching, pinned to the letter: return code
-and the exact text of gsr_last_error().  No device is needed and none is used: every device pointer below is a made-up address that is
-only compared, never followed, and every call returns before its first HIP call (a refusal, or an accepted case with nothing to do).
+"""What the C entry points refuse, and what they accept without launching, pinned to the letter: return code and the exact text of
+gsr_last_error().  No device is needed and none is used: every device pointer below is a made-up address that is only compared, never
+followed, and every call returns before it asks the HIP runtime for any work (a refusal, or an accepted case with nothing to do).  The
+one exception is harmless: gsr_forward and gsr_backward_prefill look the current device up before their checks, and without a device
+that lookup fails quietly (device 0 is assumed) and leaves the message alone.  With a device every case ends the same way.
 
-One case per `fail(...)` site that can be reached that way, in gsr_loss.h (gsr_l1_ssim_*, gsr_views_loss_*), gsr_optim.h (gsr_adam_step,
-gsr_adam_step_masked), gsr_density.h, gsr_knn.h, gsr_chamfer.h, gsr_sequence.h and gsr_rows.h, among them the two-step refusals where a
-nested check leaves the text and the caller returns the bare code.  Before every call the message buffer holds a sentinel, so an
-accepted call is also seen to leave it alone.
+One case per `fail(...)` site that can be reached that way, in gsr.h (the rasterizer: gsr_forward, gsr_backward, gsr_backward_prefill,
+the size queries, gsr_mark_visible, gsr_composited_mask and the debug readers), gsr_loss.h (gsr_l1_ssim_*, gsr_views_loss_*), gsr_optim.h
+(gsr_adam_step, gsr_adam_step_masked), gsr_density.h, gsr_knn.h, gsr_chamfer.h, gsr_sequence.h and gsr_rows.h, among them the two-step
+refusals where a nested check leaves the text and the caller returns the bare code, and for gsr.h a handful of calls that break two
+checks at once, to pin which refusal wins.  Before every call the message buffer holds a sentinel, so an accepted call is also seen to
+leave it alone.
 
 NOT covered, because they lie behind a call into the HIP runtime (a workspace size asked of rocPRIM, a memset or a launch):
+  - gsr_forward with P = 0 (a memset of out_color), and everything from its workspace checks on ("scan temp query", "geom workspace %zu
+    < %zu", "image workspace %zu < %zu", the allocator's refusal, every launch); gsr_backward likewise from "scan temp query" on
+    ("binning workspace too small", "P too large for the 28-bit accumulator row index", "backward workspace %zu < %zu", "deterministic_bwd: ...")
+  - gsr_workspace_sizes beyond its argument checks and gsr_binning_bytes for large N (rocPRIM's size queries want a device; the sizes
+    themselves are pinned by tests/test_gpu_cabi.py), gsr_composited_mask's "geom workspace %zu < %zu", gsr_mark_visible's launch
+  - gsr_debug_read_wave_trace: its argument check comes after a device synchronisation, which fails first without a device
   - gsr_densify_plan_workspace, gsr_knn_workspace, gsr_box_sort_workspace: the size itself ("densify workspace size", "knn temp query",
     "box sort workspace size")
   - gsr_densify_plan: "densify workspace %zu < %zu", "densify plan launch"
@@ -115,6 +125,54 @@ def unpack(P, D, rows=A, xyz=2 * A, dc=3 * A, rest=4 * A, op=5 * A, sc=6 * A, ro
 def gpack(P, D, B, arenas=ARENAS, grad=8 * A):
     return lambda L: L.gsr_rows_grad_pack(None, P, D, B, arenas, grad)
 
+
+ALLOC = _lib.ALLOC_FN(lambda user, n: None)        # never called: every case returns before the allocator is needed
+
+
+def fwd(**kw):
+    """gsr_forward with arguments that pass every check, except the ones given; num_rendered must come back zeroed."""
+    a = dict(P=10, D=1, M=4, W=32, H=32, bg=A, means3D=2 * A, shs=3 * A, colors=None, opac=4 * A, scales=5 * A, rots=6 * A, cov=None,
+             view=7 * A, proj=8 * A, campos=9 * A, debug=0, out=10 * A, radii=11 * A, geom=12 * A, alloc=ALLOC, img=13 * A, rest=None, raw=0)
+    a.update(kw)
+
+    def call(L):
+        n = C.c_int64(77)
+        rc = L.gsr_forward(None, a["P"], a["D"], a["M"], a["W"], a["H"], a["bg"], a["means3D"], a["shs"], a["colors"], a["opac"],
+                           a["scales"], 1.0, a["rots"], a["cov"], a["view"], a["proj"], a["campos"], 0.5, 0.5, 0, a["debug"], a["out"],
+                           a["radii"], a["geom"], BIG, a["alloc"], None, a["img"], BIG, C.byref(n), a["rest"], a["raw"])
+        assert n.value == 0
+        return rc
+    return call
+
+
+def bwd(**kw):
+    """gsr_backward likewise (the eight gradient outputs are g0 .. g7 in the order of the signature, g8 is dL_dsh_rest)."""
+    a = dict(P=10, D=1, M=4, R=100, W=32, H=32, bg=A, means3D=2 * A, radii=3 * A, shs=4 * A, colors=None, scales=5 * A, rots=6 * A,
+             cov=None, view=7 * A, proj=8 * A, campos=9 * A, dpix=10 * A, geom=11 * A, binning=12 * A, img=13 * A, ws=14 * A,
+             g0=15 * A, g1=16 * A, g2=None, g3=17 * A, g4=None, g5=18 * A, g6=19 * A, g7=20 * A, debug=0, rest=None, raw=0, g8=None)
+    a.update(kw)
+    return lambda L: L.gsr_backward(None, a["P"], a["D"], a["M"], a["R"], a["W"], a["H"], a["bg"], a["means3D"], a["radii"], a["shs"],
+                                    a["colors"], a["scales"], 1.0, a["rots"], a["cov"], a["view"], a["proj"], a["campos"], 0.5, 0.5,
+                                    a["dpix"], a["geom"], BIG, a["binning"], BIG, a["img"], BIG, a["ws"], BIG, a["g0"], a["g1"], a["g2"],
+                                    a["g3"], a["g4"], a["g5"], a["g6"], a["g7"], a["debug"], a["rest"], a["raw"], a["g8"])
+
+
+def prefill(P, M):
+    return lambda L: L.gsr_backward_prefill(P, M, A, 2 * A, None, 3 * A, None, 4 * A, 5 * A, 6 * A, None)
+
+
+FWD, BWD = "gsr_forward: ", "gsr_backward: "
+F_SIZES = FWD + "bad sizes or missing bg/matrices/out_color"
+F_MISSING = FWD + "missing means3D/opacities/radii/workspaces/allocator"
+F_COLOUR, B_COLOUR = FWD + "exactly one of shs / colors_precomp must be given", BWD + "exactly one of shs / colors_precomp must be given"
+F_COV = FWD + "exactly one of (scales, rotations) / cov3D_precomp must be given"
+B_COV = BWD + "exactly one of (scales, rotations) / cov3D_precomp must be given"
+F_REST = FWD + "shs_rest needs shs (= features_dc) and M >= 2"
+B_MISSING = BWD + "missing input, workspace or gradient buffer"
+B_PRECOMP = BWD + "dL_dcolors / dL_dcov3D required with colors_precomp / cov3D_precomp"
+B_SH, B_REST = BWD + "SH inputs inconsistent", BWD + "shs_rest needs shs, dL_dsh_rest and M >= 2"
+PRECOLOUR = dict(shs=None, colors=3 * A)           # colours instead of SH coefficients
+TOO_WIDE = 65535 * 16 + 1
 
 VF, VB = "gsr_views_loss_forward", "gsr_views_loss_backward"
 MA = "gsr_adam_step_masked"
@@ -299,6 +357,121 @@ CASES = [
     (gpack(10, 26, 1, arenas=ptrs(A + 2)), INVALID, "gsr_rows_grad_pack: arenas[0] is not 4-byte aligned"),
     (gpack(10, 26, 3, grad=16 * A + 2 * 4096 + 4 * 229), INVALID, "gsr_rows_grad_pack: grad_rows overlaps arenas[2]"),
     (gpack(10, 26, 3, grad=16 * A + 4096 - 4 * 259), INVALID, "gsr_rows_grad_pack: grad_rows overlaps arenas[1]"),
+    # (the cases above keep their numbers: new ones are added below)
+    # ---- gsr.h: gsr_forward, in the order of its checks ----
+    (fwd(P=-1), INVALID, F_SIZES),
+    (fwd(W=0), INVALID, F_SIZES),
+    (fwd(H=-5), INVALID, F_SIZES),
+    (fwd(out=None), INVALID, F_SIZES),
+    (fwd(bg=None), INVALID, F_SIZES),
+    (fwd(view=None), INVALID, F_SIZES),
+    (fwd(proj=None), INVALID, F_SIZES),
+    (fwd(W=TOO_WIDE), INVALID, "image too large"),
+    (fwd(H=TOO_WIDE), INVALID, "image too large"),
+    (fwd(means3D=None), INVALID, F_MISSING),
+    (fwd(opac=None), INVALID, F_MISSING),
+    (fwd(radii=None), INVALID, F_MISSING),
+    (fwd(geom=None), INVALID, F_MISSING),
+    (fwd(img=None), INVALID, F_MISSING),
+    (fwd(alloc=_lib.ALLOC_FN(0)), INVALID, F_MISSING),                                       # a NULL function pointer
+    (fwd(colors=14 * A), INVALID, F_COLOUR),
+    (fwd(shs=None), INVALID, F_COLOUR),
+    (fwd(cov=14 * A), INVALID, F_COV),
+    (fwd(scales=None, rots=None), INVALID, F_COV),
+    (fwd(rots=None), INVALID, F_COV),
+    (fwd(scales=None, cov=14 * A), INVALID, F_COV),
+    (fwd(rest=14 * A, M=1, D=0), INVALID, F_REST),
+    (fwd(rest=14 * A, **PRECOLOUR), INVALID, F_REST),
+    (fwd(raw=1, scales=None, rots=None, cov=14 * A), INVALID, FWD + "raw_params needs scales/rotations, not cov3D_precomp"),
+    (fwd(D=-1), INVALID, FWD + "SH degree -1 not in 0..3"),
+    (fwd(D=4, M=25), INVALID, FWD + "SH degree 4 not in 0..3"),
+    (fwd(D=2, M=8), INVALID, FWD + "M=8 < (D+1)^2=9"),
+    (fwd(campos=None), INVALID, FWD + "campos required with shs"),
+    # two checks broken at once: the earlier one answers
+    (fwd(P=-1, W=TOO_WIDE), INVALID, F_SIZES),
+    (fwd(W=TOO_WIDE, means3D=None), INVALID, "image too large"),
+    (fwd(means3D=None, colors=14 * A), INVALID, F_MISSING),
+    (fwd(colors=14 * A, cov=14 * A), INVALID, F_COLOUR),
+    (fwd(rots=None, rest=14 * A, M=1, D=0), INVALID, F_COV),
+    (fwd(rest=14 * A, M=1, D=4), INVALID, F_REST),
+    (fwd(D=4, M=25, campos=None), INVALID, FWD + "SH degree 4 not in 0..3"),
+    (fwd(D=3, M=4, campos=None), INVALID, FWD + "M=4 < (D+1)^2=16"),
+    # ---- gsr.h: gsr_backward, in the order of its checks ----
+    (bwd(P=-1), INVALID, BWD + "bad sizes"),
+    (bwd(W=0), INVALID, BWD + "bad sizes"),
+    (bwd(H=0), INVALID, BWD + "bad sizes"),
+    (bwd(R=-1), INVALID, BWD + "bad sizes"),
+    (bwd(P=0, bg=None, means3D=None, geom=None, ws=None, g0=None), OK, SENTINEL),          # P = 0: nothing else is looked at
+    (bwd(bg=None), INVALID, B_MISSING),
+    (bwd(means3D=None), INVALID, B_MISSING),
+    (bwd(radii=None), INVALID, B_MISSING),
+    (bwd(view=None), INVALID, B_MISSING),
+    (bwd(proj=None), INVALID, B_MISSING),
+    (bwd(dpix=None), INVALID, B_MISSING),
+    (bwd(geom=None), INVALID, B_MISSING),
+    (bwd(img=None), INVALID, B_MISSING),
+    (bwd(ws=None), INVALID, B_MISSING),
+    (bwd(g0=None), INVALID, B_MISSING),
+    (bwd(g1=None), INVALID, B_MISSING),
+    (bwd(g3=None), INVALID, B_MISSING),
+    (bwd(shs=None, colors=21 * A), INVALID, B_PRECOMP),
+    (bwd(scales=None, rots=None, cov=21 * A), INVALID, B_PRECOMP),
+    (bwd(colors=21 * A, g2=22 * A), INVALID, B_COLOUR),
+    (bwd(shs=None), INVALID, B_COLOUR),
+    (bwd(cov=21 * A, g4=22 * A), INVALID, B_COV),
+    (bwd(scales=None, rots=None), INVALID, B_COV),
+    (bwd(scales=None), INVALID, B_COV),
+    (bwd(g5=None), INVALID, B_SH),
+    (bwd(campos=None), INVALID, B_SH),
+    (bwd(D=-1), INVALID, B_SH),
+    (bwd(D=4, M=25), INVALID, B_SH),
+    (bwd(D=1, M=3), INVALID, B_SH),
+    (bwd(g6=None), INVALID, BWD + "dL_dscales/dL_drots required"),
+    (bwd(g7=None), INVALID, BWD + "dL_dscales/dL_drots required"),
+    (bwd(rest=21 * A), INVALID, B_REST),                                                   # no dL_dsh_rest
+    (bwd(rest=21 * A, g8=22 * A, M=1, D=0), INVALID, B_REST),
+    (bwd(raw=1, scales=None, rots=None, cov=21 * A, g4=22 * A), INVALID, BWD + "raw_params needs scales/rotations"),
+    (bwd(binning=None), INVALID, BWD + "binning workspace missing"),
+    # two checks broken at once
+    (bwd(P=0, W=0), INVALID, BWD + "bad sizes"),
+    (bwd(R=-1, bg=None), INVALID, BWD + "bad sizes"),
+    (bwd(bg=None, shs=None), INVALID, B_MISSING),
+    (bwd(shs=None, colors=21 * A, cov=21 * A, g4=22 * A), INVALID, B_PRECOMP),
+    (bwd(shs=None, cov=21 * A, g4=22 * A), INVALID, B_COLOUR),
+    (bwd(cov=21 * A, g4=22 * A, g5=None), INVALID, B_COV),
+    (bwd(g5=None, g6=None), INVALID, B_SH),
+    (bwd(g6=None, rest=21 * A), INVALID, BWD + "dL_dscales/dL_drots required"),
+    (bwd(rest=21 * A, binning=None), INVALID, B_REST),
+    # ---- gsr.h: announcements, size queries, visibility, debug readers ----
+    (prefill(10, -1), INVALID, "gsr_backward_prefill: M < 0"),
+    (prefill(0, -1), OK, SENTINEL),                                                        # P <= 0 withdraws: M is not looked at
+    (prefill(-3, 16), OK, SENTINEL),
+    (lambda L: L.gsr_workspace_sizes(-1, 32, 32, size(), size(), size()), INVALID, "gsr_workspace_sizes: P=-1 W=32 H=32"),
+    (lambda L: L.gsr_workspace_sizes(10, 0, 32, size(), size(), size()), INVALID, "gsr_workspace_sizes: P=10 W=0 H=32"),
+    (lambda L: L.gsr_workspace_sizes(10, 32, -2, None, None, None), INVALID, "gsr_workspace_sizes: P=10 W=32 H=-2"),
+    (lambda L: L.gsr_workspace_sizes(10, TOO_WIDE, 32, size(), size(), size()), INVALID, "image too large"),
+    (lambda L: L.gsr_workspace_sizes(10, 32, TOO_WIDE, size(), size(), size()), INVALID, "image too large"),
+    (lambda L: L.gsr_workspace_sizes(-1, TOO_WIDE, 32, size(), size(), size()), INVALID, "gsr_workspace_sizes: P=-1 W=1048561 H=32"),
+    (lambda L: L.gsr_backward_workspace_bytes(-1, 5, size()), INVALID, "gsr_backward_workspace_bytes: bad argument"),
+    (lambda L: L.gsr_backward_workspace_bytes(10, -5, size()), INVALID, "gsr_backward_workspace_bytes: bad argument"),
+    (lambda L: L.gsr_backward_workspace_bytes(10, 5, None), INVALID, "gsr_backward_workspace_bytes: bad argument"),
+    (lambda L: L.gsr_binning_bytes(-1, 32, 32, size()), INVALID, "gsr_binning_bytes: bad argument"),
+    (lambda L: L.gsr_binning_bytes(10, 0, 32, size()), INVALID, "gsr_binning_bytes: bad argument"),
+    (lambda L: L.gsr_binning_bytes(10, 32, -1, size()), INVALID, "gsr_binning_bytes: bad argument"),
+    (lambda L: L.gsr_binning_bytes(10, 32, 32, None), INVALID, "gsr_binning_bytes: bad argument"),
+    (lambda L: L.gsr_mark_visible(None, -1, A, 2 * A, 3 * A, 4 * A), INVALID, "gsr_mark_visible: bad argument"),
+    (lambda L: L.gsr_mark_visible(None, 10, None, 2 * A, 3 * A, 4 * A), INVALID, "gsr_mark_visible: bad argument"),
+    (lambda L: L.gsr_mark_visible(None, 10, A, None, 3 * A, 4 * A), INVALID, "gsr_mark_visible: bad argument"),
+    (lambda L: L.gsr_mark_visible(None, 10, A, 2 * A, 3 * A, None), INVALID, "gsr_mark_visible: bad argument"),
+    (lambda L: L.gsr_composited_mask(None, -1, A, BIG, 2 * A), INVALID, "gsr_composited_mask: bad argument"),
+    (lambda L: L.gsr_composited_mask(None, 10, None, BIG, 2 * A), INVALID, "gsr_composited_mask: bad argument"),
+    (lambda L: L.gsr_composited_mask(None, 10, A, BIG, None), INVALID, "gsr_composited_mask: bad argument"),
+    (lambda L: L.gsr_composited_mask(None, 0, None, 0, None), OK, SENTINEL),               # P = 0: nothing to do
+    (lambda L: L.gsr_debug_read_segments(None, 32, 32, None, A), INVALID, "gsr_debug_read_segments: bad argument"),
+    (lambda L: L.gsr_debug_read_segments(None, 32, 32, A, None), INVALID, "gsr_debug_read_segments: bad argument"),
+    (lambda L: L.gsr_debug_read_segments(None, 0, 32, A, 2 * A), INVALID, "gsr_debug_read_segments: bad argument"),
+    (lambda L: L.gsr_debug_read_segments(None, 32, -1, A, 2 * A), INVALID, "gsr_debug_read_segments: bad argument"),
+    (lambda L: L.gsr_debug_read_bound_errors(None, 10, A, 32, 32, 2 * A, None), INVALID, "gsr_debug_read_bound_errors: bad argument"),
 ]
 
 
@@ -319,6 +492,27 @@ def test_sizes_that_need_no_runtime_are_what_they_were():
     assert lib.gsr_views_loss_workspace(1, 1048560, 174752, C.byref(n)) == OK         # the largest image: 3 * 65535 * 10922 blocks < 2^31
     assert lib.gsr_chamfer_workspace(2, 3, 5, C.byref(n)) == OK and n.value == 128
     assert lib.gsr_chamfer_workspace(0, 3, 5, C.byref(n)) == OK and n.value == 0
+
+
+def test_backward_workspace_bytes_are_what_they_were():
+    """gsr_backward_workspace_bytes needs no device: accumulator rows + the deterministic mode's slots (2 * 64 bytes per rendered pair at the
+    default two blocks per wave, only under deterministic_bwd) + the dense per-Gaussian stage's list and records.  The numbers were
+    recorded from the library before gsr_api.hip was restructured around a per-call options snapshot."""
+    lib = _lib.load()
+    sizes, pairs = (0, 1, 1023, 1024, 500000), (0, 1, 1023, 1024, 500000)
+    plain = {0: 66048, 1: 81664, 1023: 383232, 1024: 383232, 500000: 66523392}
+    slots = {0: 0, 1: 256, 1023: 131072, 1024: 131072, 500000: 64000000}
+    n = C.c_size_t(0)
+    assert _lib.get_option("deterministic_bwd") == 0 and _lib.get_option("bwd_blocks_per_wave") == 2
+    try:
+        for det in (0, 1):
+            _lib.set_option("deterministic_bwd", det)
+            for P in sizes:
+                for R in pairs:
+                    assert lib.gsr_backward_workspace_bytes(P, R, C.byref(n)) == OK
+                    assert n.value == plain[P] + det * slots[R], (det, P, R)
+    finally:
+        _lib.set_option("deterministic_bwd", 0)
 
 
 def test_densify_plan_of_nothing_writes_four_zeros_and_launches_nothing():
