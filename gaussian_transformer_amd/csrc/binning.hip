@@ -150,15 +150,6 @@ hipError_t launch_sort2_by_tile(const BinningView &b, int64_t N, int tile_bits, 
                                      (unsigned)tile_bits, s, false);
 }
 
-// wave-wide inclusive scan (all 64 lanes active)
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
 // number of lanes whose inclusive-scan value is <= j  (== index of the lane that owns slot j)
 __device__ __forceinline__ int owner_lane(uint32_t incl, uint32_t j) {
     int lo = 0;
@@ -196,7 +187,7 @@ __global__ __launch_bounds__(256) void emit_keys_kernel(int P, int W, int H, int
     const uint32_t rh = (rc.y >> 16) - (rc.y & 0xffffu);
     // level-1 items = tile rows of the 3-sigma rectangle; splats that emit nothing are not walked at all
     const uint32_t nrows = (g < P && tiles[gc] > 0u) ? rh : 0u;
-    const uint32_t rincl = wave_inclusive_scan(nrows, lane);
+    const uint32_t rincl = wave_incl_scan_u32(nrows, lane);
     const uint32_t rexcl = rincl - nrows;
     const uint32_t rtotal = __shfl(rincl, 63);
     const float4 r0 = reinterpret_cast<const float4 *>(rec)[3 * (size_t)gc];
@@ -223,7 +214,7 @@ __global__ __launch_bounds__(256) void emit_keys_kernel(int P, int W, int H, int
             tile_row_span(c, px, py, A, B, (int)row, W, H, (int)x0, (int)x1, c0, c1);
         }
         const uint32_t cnt = j < rtotal ? (uint32_t)(c1 - c0) : 0u;
-        const uint32_t cincl = wave_inclusive_scan(cnt, lane);
+        const uint32_t cincl = wave_incl_scan_u32(cnt, lane);
         const uint32_t cexcl = cincl - cnt;
         const uint32_t ctotal = __shfl(cincl, 63);
         const uint32_t tile0 = row * (uint32_t)gridx + (uint32_t)c0;      // first tile of this item's span

@@ -32,11 +32,6 @@ extern int g_composite_lds_pad;
 // kernel needs 53 VGPRs and is latency-sensitive: 48-byte records, 29 waves/CU, cost 4 %; 22 waves/CU cost another 9 %)
 #define BWD_LDS_F4 (64 * 2 + 32 + (9 * RED_STRIDE + 3) / 4)
 
-__device__ __forceinline__ int xcd_band_unit(int b, int nblocks_padded) {
-    const int chunk = nblocks_padded >> 3;
-    return (b & 7) * chunk + (b >> 3);
-}
-
 template <int CTRL>
 __device__ __forceinline__ float dpp_add(float v) {
     const int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true);
@@ -713,9 +708,7 @@ __device__ void plan_units(const SegView &v, const int band, const int fillP, co
         cls = top > seg ? 0 : (top == seg ? 1 : 2 + (int)min((uint32_t)(GSR_SEG_LEN_CLASSES - 3), ((seg - top) * (GSR_SEG_LEN_CLASSES - 2)) / seg));
     };
     auto count_round = [&](uint32_t ml, uint32_t kt, int cls) {
-        uint32_t ks = kt;
-#pragma unroll
-        for (int sft = 32; sft > 0; sft >>= 1) ks += __shfl_xor(ks, sft);
+        const uint32_t ks = wave_sum_u32(kt);
         if (lane == 0 && ks) atomicAdd(&hist[1], ks);
         unsigned long long todo = __ballot(ml != 0u);
         while (todo) {                                // wave-uniform: one round per class present in the wave
@@ -728,9 +721,7 @@ __device__ void plan_units(const SegView &v, const int band, const int fillP, co
     };
     auto place_round = [&](uint32_t u, uint32_t ml, uint32_t kt, int cls, const uint4 ca, const uint4 cb) {
         // full segments: the wave reserves the sum of its kt with one atomic, every lane takes its prefix
-        uint32_t incl = kt;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+        const uint32_t incl = wave_incl_scan_u32(kt, lane);
         const uint32_t wsum = __shfl(incl, 63);
         uint32_t wbase = 0u;
         if (lane == 0 && wsum) wbase = atomicAdd(&cur[1], wsum);

@@ -22,11 +22,6 @@ extern int g_composite_lds_pad;
 
 #define LOG2E 1.4426950408889634f
 
-__device__ __forceinline__ int xcd_band_unit_f(int b, int nblocks_padded) {
-    const int chunk = nblocks_padded >> 3;
-    return (b & 7) * chunk + (b >> 3);
-}
-
 // ---- the splat walk of one staged batch, 2 blocks per wave, written out (round 3) ----
 // What the compiler makes of the C++ walk below is bound by the SCALAR unit as much as by the vector one: 31 scalar instructions per
 // splat visit (mask algebra for the per-pair decisions, the set-bit walk, structured-control-flow bookkeeping) against 39 vector
@@ -564,7 +559,7 @@ __device__ __forceinline__ void fwd_kernel_body(const CompositeArgs &a, int nblo
     extern __shared__ __align__(16) float4 stage_dyn[];     // [waves per block][64 * 3]
     const int T = a.gridx * a.gridy;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
-    const int unit = xcd_band_unit_f(blockIdx.x, nblocks_padded) * wpb + wave;
+    const int unit = xcd_band_unit(blockIdx.x, nblocks_padded) * wpb + wave;
     const int tile = unit / UNITS_PER_TILE, sub = unit % UNITS_PER_TILE;
     if (tile >= T) return;                            // wave-uniform
     fwd_unit<NPX, COUNT, ASMW>(a, stage_dyn + wave * (64 * 3), lane, tile, sub, unit, exact_cull);
@@ -588,7 +583,7 @@ __global__ __launch_bounds__(128, 8) void composite_fwd_pair_kernel(CompositeArg
     __shared__ PairShared ps;
     const int T = a.gridx * a.gridy;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int unit = xcd_band_unit_f(blockIdx.x, nblocks_padded);
+    const int unit = xcd_band_unit(blockIdx.x, nblocks_padded);
     const int tile = unit >> 1, sub = unit & 1;
     if (tile >= T) return;                            // workgroup-uniform
     if (threadIdx.x < sizeof(PairShared) / 4) reinterpret_cast<uint32_t *>(&ps)[threadIdx.x] = 0u;

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gsr_device.h"
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -73,25 +74,6 @@ __device__ __forceinline__ DoMap do_map(uint32_t kmin, uint32_t kmax, uint32_t n
     return m;
 }
 
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, m));
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m));
-    return v;
-}
-
 // depth range of the emitting Gaussians from the per-workgroup extrema preprocess left (every workgroup
 // reduces the whole list: npre words x 2 out of L2, one round trip)
 __device__ __forceinline__ void do_key_range(int npre, const uint32_t *__restrict__ blkmin, const uint32_t *__restrict__ blkmax,
@@ -112,8 +94,7 @@ __global__ __launch_bounds__(1024) void do_entry_total_kernel(int npre, const ui
     __shared__ uint32_t s_sum[16];
     uint32_t e = 0;
     for (int j = threadIdx.x; j < npre; j += 1024) e += blkent[j];
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) e += (uint32_t)__shfl_xor((int)e, m);
+    e = wave_sum_u32(e);
     if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = e;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -150,8 +131,7 @@ __global__ __launch_bounds__(DO_CNT_THREADS) void do_hist_kernel(int P, int chun
     if (blockIdx.x == 0) {                                             // workgroup 0 also totals the super-tile entries
         uint32_t e = 0;
         for (int j = threadIdx.x; j < npre; j += DO_CNT_THREADS) e += blkent[j];
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) e += (uint32_t)__shfl_xor((int)e, m);
+        e = wave_sum_u32(e);
         if ((threadIdx.x & 63) == 0) s_ent[threadIdx.x >> 6] = e;
     }
     uint32_t *h = sm, *ts = sm + nb;

@@ -39,6 +39,48 @@
 
 namespace gsr {
 
+// ---- wave-wide (64 lanes, all active) integer reductions and the inclusive scan ----
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, m));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(v, d);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+
+// Compositing launches remap blockIdx so that each XCD (blocks b, b + 8, ... share one) walks a contiguous band of units
+__device__ __forceinline__ int xcd_band_unit(int b, int nblocks_padded) {
+    const int chunk = nblocks_padded >> 3;
+    return (b & 7) * chunk + (b >> 3);
+}
+
+// A packed tile rectangle (x0 | x1 << 16, y0 | y1 << 16) and the super-tiles of EDGE x EDGE tiles under it (EDGE a power of two)
+struct SuperRect { int x0, x1, y0, y1, sx0, sx1, sy0, sy1; };
+template <int EDGE>
+__device__ __forceinline__ SuperRect super_rect(uint4 rc, int SX, int SY) {
+    SuperRect r;
+    r.x0 = (int)(rc.x & 0xffffu); r.x1 = (int)(rc.x >> 16); r.y0 = (int)(rc.y & 0xffffu); r.y1 = (int)(rc.y >> 16);
+    // tile rectangles lie inside the grid; the clamp only bounds the loops should a record ever be garbage
+    r.sx0 = r.x0 / EDGE; r.sx1 = min((r.x1 + EDGE - 1) / EDGE, SX); r.sy0 = r.y0 / EDGE; r.sy1 = min((r.y1 + EDGE - 1) / EDGE, SY);
+    return r;
+}
+
 // x' = m[0]x + m[4]y + m[8]z + m[12]  (scene/cameras.py:54-57 memory layout)
 __device__ __forceinline__ void xform4x3(const float *__restrict__ m, const float p[3], float o[3]) {
     o[0] = m[0] * p[0] + m[4] * p[1] + m[8] * p[2] + m[12];

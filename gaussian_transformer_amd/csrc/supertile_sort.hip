@@ -50,39 +50,6 @@ SuperSortPlan super_sort_plan(int P, int W, int H) {
     return p;
 }
 
-__device__ __forceinline__ uint32_t ss_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m);
-    return v;
-}
-__device__ __forceinline__ uint32_t ss_wave_max(uint32_t v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m));
-    return v;
-}
-__device__ __forceinline__ uint32_t ss_wave_min(uint32_t v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, m));
-    return v;
-}
-__device__ __forceinline__ uint32_t ss_wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-struct SsRect { int x0, x1, y0, y1, sx0, sx1, sy0, sy1; };
-__device__ __forceinline__ SsRect ss_rect(uint4 rc, int SX, int SY) {
-    SsRect r;
-    r.x0 = (int)(rc.x & 0xffffu); r.x1 = (int)(rc.x >> 16); r.y0 = (int)(rc.y & 0xffffu); r.y1 = (int)(rc.y >> 16);
-    r.sx0 = r.x0 / GSR_SS_TILES; r.sx1 = min((r.x1 + GSR_SS_TILES - 1) / GSR_SS_TILES, SX);
-    r.sy0 = r.y0 / GSR_SS_TILES; r.sy1 = min((r.y1 + GSR_SS_TILES - 1) / GSR_SS_TILES, SY);
-    return r;
-}
-
 struct SsBinArgs {
     int P, chunk, SX, SY, W, H, exact_cull;
     const uint4 *ss_rec;             // per Gaussian: what preprocess prepared for this path (GeomView::ss_rec)
@@ -230,7 +197,7 @@ __device__ __forceinline__ void ss_for_chunk_entries(const SsBinArgs &a, const S
 #define SS_BC(x) __builtin_amdgcn_readlane((int)(x), j)
 #define SS_BCF(x) __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j))
             const int i = SS_BC(iv);
-            const SsRect q = ss_rect(make_uint4((uint32_t)SS_BC(rcv.x), (uint32_t)SS_BC(rcv.y), 0u, 0u), a.SX, a.SY);
+            const SuperRect q = super_rect<GSR_SS_TILES>(make_uint4((uint32_t)SS_BC(rcv.x), (uint32_t)SS_BC(rcv.y), 0u, 0u), a.SX, a.SY);
             const uint32_t d = (uint32_t)SS_BC(dv);
             const float4 r0 = make_float4(SS_BCF(r0v.x), SS_BCF(r0v.y), SS_BCF(r0v.z), SS_BCF(r0v.w));
             const CullParams cp = make_cull(r0.z, r0.w, SS_BCF(conCv), SS_BCF(tauv));
@@ -280,7 +247,7 @@ __global__ __launch_bounds__(SS_BIN_THREADS) void ss_count_kernel(SsBinArgs a) {
     ss_for_chunk_entries<true>(a, l, [&](int bin, uint32_t m, uint32_t, uint32_t) {
         atomicAdd(&h[bin], 1u); pairs += (uint32_t)__popc(m); ents++;
     });
-    pairs = ss_wave_sum(pairs); ents = ss_wave_sum(ents);
+    pairs = wave_sum_u32(pairs); ents = wave_sum_u32(ents);
     if ((threadIdx.x & 63) == 0) { s_sum[0][threadIdx.x >> 6] = pairs; s_sum[1][threadIdx.x >> 6] = ents; }
     __syncthreads();
     uint32_t *row = a.wg_cnt + (size_t)blockIdx.x * S;
@@ -311,8 +278,8 @@ __global__ __launch_bounds__(SS_THREADS) void ss_scan_kernel(int S, uint32_t eca
         c[q] = (q < per && b0 + q < S) ? bin_cnt[b0 + q] : 0u;
         sum += c[q]; mx = max(mx, c[q]);
     }
-    const uint32_t incl = ss_wave_incl_scan(sum, lane);
-    mx = ss_wave_max(mx);
+    const uint32_t incl = wave_incl_scan_u32(sum, lane);
+    mx = wave_max_u32(mx);
     if (lane == 63) { wtot[w] = incl; wmax[w] = mx; }
     __syncthreads();
     uint32_t ex = incl - sum;
@@ -379,37 +346,23 @@ struct SsSortArgs {
                              // kernel, read by the big-buffer launch, which then takes only those); lives in the counting scratch (wg_cnt)
     int flagged_only;        // big-buffer launch: 1 = only bins with unsplit[s] != 0
 };
-template <int CAP>
-__global__ __launch_bounds__(SS_THREADS, CAP <= GSR_SS_CAP ? 8 : 4) void ss_sort_expand_kernel(SsSortArgs a) {
-    constexpr int ITEMS = CAP / SS_THREADS;
-    extern __shared__ uint64_t buf[];                              // [CAP] keys; later: sorted ids (u32) | sorted masks (u16)
-    uint16_t *mbuf = reinterpret_cast<uint16_t *>(buf + CAP);      // [CAP] masks travelling with the keys
-    __shared__ uint32_t start[SS_NSUB + 1], cur[SS_NSUB];
-    __shared__ uint32_t wred[3][SS_THREADS / 64];
-    __shared__ uint32_t s_kmin, s_kmax, s_before;
-    __shared__ uint32_t tile_start[16];
-    __shared__ uint64_t split[SS_NSPLIT];                          // third map: splitters drawn from the bin itself (split[0] unused); 256 of them:
-                                                                   // with 512 the static LDS would push two workgroups past a CU's 160 KB
-    if (a.hdr[DO_OVERFLOW]) return;                                // grid-uniform
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const uint32_t e0 = a.bin_start[s];
-    int n = (int)a.bin_cur[s];                                     // entries actually written (empty masks were dropped)
-    if (a.n_lo == 0 && tid == 0 && a.unsplit) a.unsplit[s] = 0u;   // first launch of the frame: clear the flag of every bin
-    if (n < a.n_lo || n > a.n_hi) return;                          // workgroup-uniform: another launch's bin
-    if (a.flagged_only && a.unsplit[s] == 0u) return;              // the split kernel took it
 
-    if (!GSR_IDX_OK(n, CAP + 1, a.hdr + GSR_DBG_GEOM_WORD, GSR_BOUND_SS_BIN_SIZE)) n = CAP;      // debug build: a bin beyond the LDS buffer
-    // pairs of the super-tiles before this one = where its region of point_list starts
-    {
-        uint32_t before = 0;
-        for (int k = tid; k < s; k += SS_THREADS) before += a.bin_pairs[k];
-        before = ss_wave_sum(before);
-        if (lane == 0) wred[0][w] = before;
-    }
-    if (tid <= SS_NSUB) start[tid] = 0u;
-    // ---- keys into registers, their depth range ----
-    uint64_t key[ITEMS];
-    uint32_t msk[ITEMS];
+// The phases the two sort-expand kernels below share.  Every __shared__ array is declared in the kernels (static LDS is tight, see
+// split[] of ss_sort_expand_kernel) and handed to the phase that uses it; the register arrays stay the kernels' own.
+typedef uint32_t SsWaveWords[SS_THREADS / 64];        // one word per wave of the workgroup
+
+// pairs of the super-tiles before this one = where its region of point_list starts: per-wave partial sums (ss_load_keys folds them)
+__device__ __forceinline__ void ss_pairs_before(const SsSortArgs &a, int s, SsWaveWords &wsum) {
+    uint32_t before = 0;
+    for (int k = threadIdx.x; k < s; k += SS_THREADS) before += a.bin_pairs[k];
+    before = wave_sum_u32(before);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = before;
+}
+// ---- keys into registers, their depth range -> s_kmin, s_kmax; s_before ----
+template <int ITEMS>
+__device__ __forceinline__ void ss_load_keys(const SsSortArgs &a, uint32_t e0, int n, uint64_t (&key)[ITEMS], uint32_t (&msk)[ITEMS],
+                                             SsWaveWords (&wred)[3], uint32_t &s_before, uint32_t &s_kmin, uint32_t &s_kmax) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     uint32_t kmin = 0xffffffffu, kmax = 0u;
 #pragma unroll
     for (int q = 0; q < ITEMS; q++) {
@@ -421,7 +374,7 @@ __global__ __launch_bounds__(SS_THREADS, CAP <= GSR_SS_CAP ? 8 : 4) void ss_sort
             kmin = min(kmin, e.x); kmax = max(kmax, e.x);
         }
     }
-    kmin = ss_wave_min(kmin); kmax = ss_wave_max(kmax);
+    kmin = wave_min_u32(kmin); kmax = wave_max_u32(kmax);
     if (lane == 0) { wred[1][w] = kmin; wred[2][w] = kmax; }
     __syncthreads();
     if (tid == 0) {
@@ -430,17 +383,205 @@ __global__ __launch_bounds__(SS_THREADS, CAP <= GSR_SS_CAP ? 8 : 4) void ss_sort
         s_before = b; s_kmin = mn; s_kmax = mx;
     }
     __syncthreads();
-    // Monotone map of the depth bits onto the sub-buckets, over the bin's own range.  First choice: linear in DEPTH, which
-    // spreads a typical bin evenly (rank-by-counting then compares a key with ~10 others).  A few splats right in front of
-    // the camera stretch such a map until the bulk of the bin shares a handful of sub-buckets; when the largest sub-bucket
-    // exceeds SS_RANK_MAX the histogram is redone with a map linear in the depth BITS (logarithmic in depth, exact integer
-    // arithmetic), which no outlier can stretch that way.  Either map is monotone, so the order is the same.
-    const uint32_t kmin0 = s_kmin;
-    const uint64_t kspan = (uint64_t)(s_kmax >= s_kmin ? s_kmax - s_kmin : 0u) + 1ull;
-    const float dmin = __uint_as_float(s_kmin);
-    const float fspan = __uint_as_float(s_kmax) - dmin;
-    const float fscale = (s_kmax > s_kmin && fspan > 0.f) ? (float)SS_NSUB / fspan : 0.f;
-    bool log_map = false, split_map = false;                           // workgroup-uniform
+}
+
+// Monotone map of the depth bits onto the sub-buckets, over the bin's own range.  First choice: linear in DEPTH, which
+// spreads a typical bin evenly (rank-by-counting then compares a key with ~10 others).  A few splats right in front of
+// the camera stretch such a map until the bulk of the bin shares a handful of sub-buckets; when the largest sub-bucket
+// exceeds SS_RANK_MAX the histogram is redone with a map linear in the depth BITS (logarithmic in depth, exact integer
+// arithmetic), which no outlier can stretch that way.  Either map is monotone, so the order is the same.
+struct SsDepthMap {
+    uint32_t kmin0; uint64_t kspan; float dmin, fscale;
+    bool log_map;                                                      // workgroup-uniform
+    __device__ __forceinline__ SsDepthMap(uint32_t kmin, uint32_t kmax) {
+        kmin0 = kmin;
+        kspan = (uint64_t)(kmax >= kmin ? kmax - kmin : 0u) + 1ull;
+        dmin = __uint_as_float(kmin);
+        const float fspan = __uint_as_float(kmax) - dmin;
+        fscale = (kmax > kmin && fspan > 0.f) ? (float)SS_NSUB / fspan : 0.f;
+        log_map = false;
+    }
+    __device__ __forceinline__ uint32_t sub_of(uint64_t k) const {
+        const uint32_t kb = (uint32_t)(k >> 32);
+        if (log_map) return (uint32_t)(((uint64_t)(kb - kmin0) * (uint64_t)SS_NSUB) / kspan);     // < SS_NSUB
+        const float v = (__uint_as_float(kb) - dmin) * fscale;
+        const uint32_t f = v > 0.f ? (uint32_t)v : 0u;
+        return f < SS_NSUB ? f : SS_NSUB - 1u;
+    }
+};
+
+// ---- exclusive scan of the histogram: start[b] = first position of sub-bucket b, start[SS_NSUB] = n; cur[] (the placement's cursors) = start[] ----
+__device__ __forceinline__ void ss_scan_starts(int n, uint32_t (&start)[SS_NSUB + 1], uint32_t (&cur)[SS_NSUB], SsWaveWords &wtot) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const uint32_t v = tid < SS_NSUB ? start[tid] : 0u;
+    const uint32_t incl = wave_incl_scan_u32(v, lane);
+    if (lane == 63) wtot[w] = incl;
+    __syncthreads();
+    uint32_t ex = incl - v;
+    for (int k = 0; k < w; k++) ex += wtot[k];
+    if (tid < SS_NSUB) { start[tid] = ex; cur[tid] = ex; }
+    if (tid == SS_NSUB) start[SS_NSUB] = (uint32_t)n;
+}
+
+// buf[0..n) holds keys grouped by sub-bucket, mbuf their masks; start[] are the sub-buckets' first positions + base0 (the split kernel's
+// part begins at base0 of its bin).  Leaves the ids in key order in sid = buf (aliasing it once it has been consumed) and the masks in
+// smask behind them (6 * CAP <= 8 * CAP bytes).
+// The thread that holds position j counts the smaller keys of j's sub-bucket (keys are unique: depth bits | id).  Correct for any
+// distribution; a bin whose depths all coincide costs n comparisons per item (slow, never wrong) -- there is no power-of-two network
+// to overflow the LDS.
+template <int ITEMS, int CAP, class SubOf>
+__device__ __forceinline__ void ss_rank(int n, uint32_t base0, SubOf sub_of, const uint32_t (&start)[SS_NSUB + 1], uint64_t *buf) {
+    const int tid = threadIdx.x;
+    const uint16_t *mbuf = reinterpret_cast<const uint16_t *>(buf + CAP);
+    uint32_t *sid = reinterpret_cast<uint32_t *>(buf);
+    uint16_t *smask = reinterpret_cast<uint16_t *>(sid + CAP);
+    uint32_t rk[ITEMS], id[ITEMS], mm[ITEMS];
+#pragma unroll
+    for (int q = 0; q < ITEMS; q++) {
+        const int j = tid + q * SS_THREADS;
+        rk[q] = 0u; id[q] = 0u; mm[q] = 0u;
+        if (j < n) {
+            const uint64_t me = buf[j];
+            const uint32_t sb = sub_of(me);
+            const uint32_t a0 = start[sb] - base0, a1 = start[sb + 1] - base0;
+            // (eight reads in flight: one LDS round trip per comparison made this loop the whole kernel on scenes whose depths
+            //  crowd a few sub-buckets -- config 4: 170 of 216 us)
+            uint32_t r = a0, k = a0;
+            for (; k + 8 <= a1; k += 8) {
+                uint64_t v[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) v[u] = buf[k + u];
+#pragma unroll
+                for (int u = 0; u < 8; u++) r += v[u] < me ? 1u : 0u;
+            }
+            for (; k < a1; k++) r += buf[k] < me ? 1u : 0u;
+            rk[q] = r; id[q] = (uint32_t)me; mm[q] = mbuf[j];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < ITEMS; q++)
+        if (tid + q * SS_THREADS < n) { sid[rk[q]] = id[q]; smask[rk[q]] = (uint16_t)mm[q]; }
+}
+
+// Per-thread tile counts, packed.  bit k of a byte -> nibble k of a word; the per-thread counts (<= ITEMS <= 14 < 16) add up nibble-wise ...
+__device__ __forceinline__ uint32_t ss_spread8(uint32_t x) {
+    x = (x | (x << 12)) & 0x000f000fu; x = (x | (x << 6)) & 0x03030303u; x = (x | (x << 3)) & 0x11111111u;
+    return x;
+}
+// ... and the nibble counters of tiles 0-7 (nlo) and 8-15 (nhi) become 8 words, two tiles to a word (word k: tile 2k | tile 2k + 1 << 16)
+__device__ __forceinline__ void ss_packed_counts(uint32_t nlo, uint32_t nhi, uint32_t (&c)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const uint32_t src = k < 4 ? nlo : nhi;
+        const int sh = 8 * (k & 3);
+        c[k] = ((src >> sh) & 0xfu) | (((src >> (sh + 4)) & 0xfu) << 16);
+    }
+}
+__device__ __forceinline__ uint32_t ss_packed_get(const uint32_t *c, int t) { return (c[t >> 1] >> (16 * (t & 1))) & 0xffffu; }      // component t
+
+// ---- expansion: the sorted entries -> the 16 per-tile lists.  Every thread takes ITEMS consecutive sorted entries and needs,
+// for each of the 16 tiles, how many earlier entries carry that tile's bit: a 16-component prefix sum.  The components are
+// packed two to a word (16 bits each, n <= 14 336), so that one workgroup scan of 8 words does all tiles at once; a wave
+// sweeping all n entries for one tile (the first version) spent 26 of this kernel's 42 us on ballots.
+// This thread's ITEMS entries (m: masks, idv: ids) and their exclusive packed prefix ex[]; wtab is left holding the waves' inclusive totals.
+template <int ITEMS, int CAP>
+__device__ __forceinline__ void ss_expand_scan(int n, const uint64_t *buf, uint32_t (&m)[ITEMS], uint32_t (&idv)[ITEMS], uint32_t (&ex)[8],
+                                               uint32_t (&wtab)[SS_THREADS / 64][8]) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const uint32_t *sid = reinterpret_cast<const uint32_t *>(buf);
+    const uint16_t *smask = reinterpret_cast<const uint16_t *>(sid + CAP);
+    const int jb = tid * ITEMS;
+    uint32_t nlo = 0u, nhi = 0u;
+#pragma unroll
+    for (int q = 0; q < ITEMS; q++) {
+        const int j = jb + q;
+        m[q] = j < n ? (uint32_t)smask[j] : 0u;
+        idv[q] = j < n ? sid[j] : 0u;
+        nlo += ss_spread8(m[q] & 0xffu); nhi += ss_spread8(m[q] >> 8);
+    }
+    uint32_t c[8];
+    ss_packed_counts(nlo, nhi, c);
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const uint32_t incl = wave_incl_scan_u32(c[k], lane);
+        ex[k] = incl - c[k];
+        if (lane == 63) wtab[w][k] = incl;
+    }
+    __syncthreads();
+    for (int k = 0; k < w; k++) {
+#pragma unroll
+        for (int u = 0; u < 8; u++) ex[u] += wtab[k][u];
+    }
+}
+// threads 0..15: tile totals out of the waves' packed totals, their exclusive scan, the ranges
+__device__ __forceinline__ void ss_tile_totals(const SsSortArgs &a, int s, uint32_t before, const uint32_t (&wtot)[SS_THREADS / 64][8],
+                                               uint32_t (&tile_start)[16], bool write_ranges) {
+    const int tid = threadIdx.x;
+    if (tid < 16) {
+        uint32_t tot = 0u;
+        for (int k = 0; k < SS_THREADS / 64; k++) tot += ss_packed_get(wtot[k], tid);
+        uint32_t incl = tot;
+#pragma unroll
+        for (int d = 1; d < 16; d <<= 1) {
+            const uint32_t t = __shfl_up(incl, d);
+            if (tid >= d) incl += t;
+        }
+        const uint32_t st = before + incl - tot;
+        tile_start[tid] = st;
+        if (write_ranges) {
+            const int tx = (s % a.SX) * GSR_SS_TILES + (tid & 3), ty = (s / a.SX) * GSR_SS_TILES + (tid >> 2);
+            if (tx < a.gridx && ty < a.gridy) a.ranges[ty * a.gridx + tx] = make_uint2(st, st + tot);
+        }
+    }
+}
+// 16 * ITEMS predicated 4-byte stores per thread, tile t's from first[t] on; consecutive lanes hold consecutive entries, so the lanes that do store for
+// a tile hit neighbouring addresses.  (Staging the super-tile's lists in LDS and copying them out densely was measured: slower.)
+template <int ITEMS, class First>
+__device__ __forceinline__ void ss_expand_stores(const SsSortArgs &a, const uint32_t (&m)[ITEMS], const uint32_t (&idv)[ITEMS], const uint32_t (&ex)[8],
+                                                 First first) {
+    uint32_t pos[16];
+#pragma unroll
+    for (int t = 0; t < 16; t++) pos[t] = first(t) + ss_packed_get(ex, t);
+#pragma unroll
+    for (int q = 0; q < ITEMS; q++) {
+#pragma unroll
+        for (int t = 0; t < 16; t++) {
+            const uint32_t bitv = (m[q] >> t) & 1u;
+            if (bitv && GSR_IDX_OK(pos[t], a.hdr[SS_HDR_N], a.hdr + GSR_DBG_GEOM_WORD, GSR_BOUND_POINT_LIST)) a.point_list[pos[t]] = idv[q];
+            pos[t] += bitv;
+        }
+    }
+}
+
+template <int CAP>
+__global__ __launch_bounds__(SS_THREADS, CAP <= GSR_SS_CAP ? 8 : 4) void ss_sort_expand_kernel(SsSortArgs a) {
+    constexpr int ITEMS = CAP / SS_THREADS;
+    extern __shared__ uint64_t buf[];                              // [CAP] keys; later: sorted ids (u32) | sorted masks (u16)
+    uint16_t *mbuf = reinterpret_cast<uint16_t *>(buf + CAP);      // [CAP] masks travelling with the keys
+    __shared__ uint32_t start[SS_NSUB + 1], cur[SS_NSUB];
+    __shared__ SsWaveWords wred[3];
+    __shared__ uint32_t s_kmin, s_kmax, s_before;
+    __shared__ uint32_t tile_start[16];
+    __shared__ uint64_t split[SS_NSPLIT];                          // third map: splitters drawn from the bin itself (split[0] unused); 256 of them:
+                                                                   // with 512 the static LDS would push two workgroups past a CU's 160 KB
+    __shared__ uint32_t wtab[SS_THREADS / 64][8];
+    if (a.hdr[DO_OVERFLOW]) return;                                // grid-uniform
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const uint32_t e0 = a.bin_start[s];
+    int n = (int)a.bin_cur[s];                                     // entries actually written (empty masks were dropped)
+    if (a.n_lo == 0 && tid == 0 && a.unsplit) a.unsplit[s] = 0u;   // first launch of the frame: clear the flag of every bin
+    if (n < a.n_lo || n > a.n_hi) return;                          // workgroup-uniform: another launch's bin
+    if (a.flagged_only && a.unsplit[s] == 0u) return;              // the split kernel took it
+
+    if (!GSR_IDX_OK(n, CAP + 1, a.hdr + GSR_DBG_GEOM_WORD, GSR_BOUND_SS_BIN_SIZE)) n = CAP;      // debug build: a bin beyond the LDS buffer
+    ss_pairs_before(a, s, wred[0]);
+    if (tid <= SS_NSUB) start[tid] = 0u;
+    uint64_t key[ITEMS];
+    uint32_t msk[ITEMS];
+    ss_load_keys<ITEMS>(a, e0, n, key, msk, wred, s_before, s_kmin, s_kmax);
+    SsDepthMap map(s_kmin, s_kmax);
+    bool split_map = false;                                            // workgroup-uniform
     auto sub_of = [&](uint64_t k) -> uint32_t {
         if (split_map) {                                               // number of splitters <= k: binary search over split[1..SS_NSPLIT)
             uint32_t lo = 0u, hi = SS_NSPLIT - 1u;                     // answer in [lo, hi]
@@ -451,11 +592,7 @@ __global__ __launch_bounds__(SS_THREADS, CAP <= GSR_SS_CAP ? 8 : 4) void ss_sort
             }
             return lo;
         }
-        const uint32_t kb = (uint32_t)(k >> 32);
-        if (log_map) return (uint32_t)(((uint64_t)(kb - kmin0) * (uint64_t)SS_NSUB) / kspan);     // < SS_NSUB
-        const float v = (__uint_as_float(kb) - dmin) * fscale;
-        const uint32_t f = v > 0.f ? (uint32_t)v : 0u;
-        return f < SS_NSUB ? f : SS_NSUB - 1u;
+        return map.sub_of(k);
     };
     if (n > 0) {
         // ---- sub-bucket histogram (again if the map turns out lopsided: linear in depth, then linear in the depth bits, then splitters
@@ -466,13 +603,13 @@ __global__ __launch_bounds__(SS_THREADS, CAP <= GSR_SS_CAP ? 8 : 4) void ss_sort
                 if (tid + q * SS_THREADS < n) atomicAdd(&start[sub_of(key[q])], 1u);
             __syncthreads();
             if (attempt == 2) break;
-            const uint32_t mx = ss_wave_max(tid < SS_NSUB ? start[tid] : 0u);
+            const uint32_t mx = wave_max_u32(tid < SS_NSUB ? start[tid] : 0u);
             if (lane == 0) wred[1][w] = mx;
             __syncthreads();
             uint32_t m = 0;
             for (int k = 0; k < SS_THREADS / 64; k++) m = max(m, wred[1][k]);
             if (m <= (attempt == 0 ? SS_RANK_MAX : SS_RANK_MAX_LOG)) break;      // workgroup-uniform
-            if (attempt == 0) log_map = true;
+            if (attempt == 0) map.log_map = true;
             else {
                 // Both analytic maps leave a sub-bucket of hundreds (a scene seen from inside: a few splats at the lens stretch the range and
                 // the object sits in a sliver of it; config 4: 590 of a bin's 1781 entries in one sub-bucket, the ranking below is quadratic in
@@ -492,22 +629,13 @@ __global__ __launch_bounds__(SS_THREADS, CAP <= GSR_SS_CAP ? 8 : 4) void ss_sort
                 }
                 __syncthreads();
                 if (tid >= 1 && tid < SS_NSPLIT) split[tid] = sorted[min(ns - 1, (tid * ns) / SS_NSPLIT)];
-                split_map = true; log_map = false;
+                split_map = true; map.log_map = false;
             }
             __syncthreads();
             if (tid <= SS_NSUB) start[tid] = 0u;
             __syncthreads();
         }
-        {
-            const uint32_t v = tid < SS_NSUB ? start[tid] : 0u;
-            const uint32_t incl = ss_wave_incl_scan(v, lane);
-            if (lane == 63) wred[0][w] = incl;
-            __syncthreads();
-            uint32_t ex = incl - v;
-            for (int k = 0; k < w; k++) ex += wred[0][k];
-            if (tid < SS_NSUB) { start[tid] = ex; cur[tid] = ex; }
-            if (tid == SS_NSUB) start[SS_NSUB] = (uint32_t)n;
-        }
+        ss_scan_starts(n, start, cur, wred[0]);
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < ITEMS; q++)
@@ -516,116 +644,14 @@ __global__ __launch_bounds__(SS_THREADS, CAP <= GSR_SS_CAP ? 8 : 4) void ss_sort
                 if (GSR_IDX_OK(pos, CAP, a.hdr + GSR_DBG_GEOM_WORD, GSR_BOUND_SS_LDS_POS)) { buf[pos] = key[q]; mbuf[pos] = (uint16_t)msk[q]; }
             }
         __syncthreads();
-    }
-    uint32_t *sid = reinterpret_cast<uint32_t *>(buf);                 // sorted ids, aliasing buf once it has been consumed
-    uint16_t *smask = reinterpret_cast<uint16_t *>(sid + CAP);         // sorted masks behind them (6 * CAP <= 8 * CAP bytes)
-    if (n > 0) {
-        // The items are grouped by sub-bucket now: the thread that holds position j counts the smaller keys of j's
-        // sub-bucket (keys are unique: depth bits | id).  Correct for any distribution; a bin whose depths all coincide
-        // costs n comparisons per item (slow, never wrong) -- there is no power-of-two network to overflow the LDS.
-        uint32_t rk[ITEMS], id[ITEMS], mm[ITEMS];
-#pragma unroll
-        for (int q = 0; q < ITEMS; q++) {
-            const int j = tid + q * SS_THREADS;
-            rk[q] = 0u; id[q] = 0u; mm[q] = 0u;
-            if (j < n) {
-                const uint64_t me = buf[j];
-                const uint32_t sb = sub_of(me);
-                const uint32_t a0 = start[sb], a1 = start[sb + 1];
-                // (eight reads in flight: one LDS round trip per comparison made this loop the whole kernel on scenes whose depths
-                //  crowd a few sub-buckets -- config 4: 170 of 216 us)
-                uint32_t r = a0, k = a0;
-                for (; k + 8 <= a1; k += 8) {
-                    uint64_t v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; u++) v[u] = buf[k + u];
-#pragma unroll
-                    for (int u = 0; u < 8; u++) r += v[u] < me ? 1u : 0u;
-                }
-                for (; k < a1; k++) r += buf[k] < me ? 1u : 0u;
-                rk[q] = r; id[q] = (uint32_t)me; mm[q] = mbuf[j];
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < ITEMS; q++)
-            if (tid + q * SS_THREADS < n) { sid[rk[q]] = id[q]; smask[rk[q]] = (uint16_t)mm[q]; }
+        ss_rank<ITEMS, CAP>(n, 0u, sub_of, start, buf);
     }
     __syncthreads();
-    // ---- expansion: the sorted entries -> the 16 per-tile lists.  Every thread takes ITEMS consecutive sorted entries and needs,
-    // for each of the 16 tiles, how many earlier entries carry that tile's bit: a 16-component prefix sum.  The components are
-    // packed two to a word (16 bits each, n <= 14 336), so that one workgroup scan of 8 words does all tiles at once; a wave
-    // sweeping all n entries for one tile (the first version) spent 26 of this kernel's 42 us on ballots.
-    uint32_t m[ITEMS], idv[ITEMS];
-    const int jb = tid * ITEMS;
-#pragma unroll
-    for (int q = 0; q < ITEMS; q++) {
-        const int j = jb + q;
-        m[q] = j < n ? (uint32_t)smask[j] : 0u;
-        idv[q] = j < n ? sid[j] : 0u;
-    }
-    // this thread's entries per tile, two tiles to a word (word k: tile 2k | tile 2k + 1 << 16)
-    auto local_counts = [&](uint32_t c[8]) {
-        // bit k of a byte -> nibble k of a word; the per-thread counts (<= ITEMS <= 14 < 16) add up nibble-wise
-        auto spread8 = [](uint32_t x) {
-            x = (x | (x << 12)) & 0x000f000fu; x = (x | (x << 6)) & 0x03030303u; x = (x | (x << 3)) & 0x11111111u;
-            return x;
-        };
-        uint32_t nlo = 0u, nhi = 0u;
-#pragma unroll
-        for (int q = 0; q < ITEMS; q++) { nlo += spread8(m[q] & 0xffu); nhi += spread8(m[q] >> 8); }
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint32_t src = k < 4 ? nlo : nhi;
-            const int sh = 8 * (k & 3);
-            c[k] = ((src >> sh) & 0xfu) | (((src >> (sh + 4)) & 0xfu) << 16);
-        }
-    };
-    uint32_t c[8];
-    local_counts(c);
-    __shared__ uint32_t wtab[SS_THREADS / 64][8];
-    uint32_t ex[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        const uint32_t incl = ss_wave_incl_scan(c[k], lane);
-        ex[k] = incl - c[k];
-        if (lane == 63) wtab[w][k] = incl;
-    }
+    uint32_t m[ITEMS], idv[ITEMS], ex[8];
+    ss_expand_scan<ITEMS, CAP>(n, buf, m, idv, ex, wtab);
+    ss_tile_totals(a, s, s_before, wtab, tile_start, true);
     __syncthreads();
-    for (int k = 0; k < w; k++) {
-#pragma unroll
-        for (int u = 0; u < 8; u++) ex[u] += wtab[k][u];
-    }
-    if (tid < 16) {                                                    // tile totals, their exclusive scan, the ranges
-        uint32_t tot = 0u;
-        for (int k = 0; k < SS_THREADS / 64; k++) tot += (wtab[k][tid >> 1] >> (16 * (tid & 1))) & 0xffffu;
-        uint32_t incl = tot;
-#pragma unroll
-        for (int d = 1; d < 16; d <<= 1) {
-            const uint32_t t = __shfl_up(incl, d);
-            if (tid >= d) incl += t;
-        }
-        const uint32_t st = s_before + incl - tot;
-        tile_start[tid] = st;
-
-        const int tx = (s % a.SX) * GSR_SS_TILES + (tid & 3), ty = (s / a.SX) * GSR_SS_TILES + (tid >> 2);
-        if (tx < a.gridx && ty < a.gridy) a.ranges[ty * a.gridx + tx] = make_uint2(st, st + tot);
-    }
-    __syncthreads();
-    // 16 * ITEMS predicated 4-byte stores per thread; consecutive lanes hold consecutive entries, so the lanes that do store for
-    // a tile hit neighbouring addresses.  (Staging the super-tile's lists in LDS and copying them out densely was measured: slower.)
-    uint32_t pos[16];
-#pragma unroll
-    for (int t = 0; t < 16; t++) pos[t] = tile_start[t] + ((ex[t >> 1] >> (16 * (t & 1))) & 0xffffu);
-#pragma unroll
-    for (int q = 0; q < ITEMS; q++) {
-#pragma unroll
-        for (int t = 0; t < 16; t++) {
-            const uint32_t bitv = (m[q] >> t) & 1u;
-            if (bitv && GSR_IDX_OK(pos[t], a.hdr[SS_HDR_N], a.hdr + GSR_DBG_GEOM_WORD, GSR_BOUND_POINT_LIST)) a.point_list[pos[t]] = idv[q];
-            pos[t] += bitv;
-        }
-    }
+    ss_expand_stores<ITEMS>(a, m, idv, ex, [&](int t) { return tile_start[t]; });
 }
 
 // ---- 4b: a crowded super-tile (GSR_SS_CAP < n <= GSR_SS_CAP_BIG entries: a dense cloud centre) cut across SS_SPLIT_PARTS workgroups.
@@ -642,7 +668,7 @@ __global__ __launch_bounds__(SS_THREADS, 4) void ss_sort_expand_split_kernel(SsS
     extern __shared__ uint64_t buf[];                              // [CAP] keys of this part; later: sorted ids (u32) | sorted masks (u16)
     uint16_t *mbuf = reinterpret_cast<uint16_t *>(buf + CAP);
     __shared__ uint32_t start[SS_NSUB + 1], cur[SS_NSUB];
-    __shared__ uint32_t wred[3][SS_THREADS / 64];
+    __shared__ SsWaveWords wred[3];
     __shared__ uint32_t s_kmin, s_kmax, s_before;
     __shared__ uint32_t tile_start[16], tile_before[16];
     __shared__ uint32_t s_g[PARTS + 1];
@@ -652,76 +678,34 @@ __global__ __launch_bounds__(SS_THREADS, 4) void ss_sort_expand_split_kernel(SsS
     const uint32_t e0 = a.bin_start[s];
     const int n = (int)a.bin_cur[s];
     if (n <= GSR_SS_CAP || n > GSR_SS_CAP_BIG) return;             // workgroup-uniform: not a crowded bin
-    {
-        uint32_t before = 0;
-        for (int k = tid; k < s; k += SS_THREADS) before += a.bin_pairs[k];
-        before = ss_wave_sum(before);
-        if (lane == 0) wred[0][w] = before;
-    }
+    ss_pairs_before(a, s, wred[0]);
     if (tid <= SS_NSUB) start[tid] = 0u;
     if (tid <= PARTS) s_g[tid] = tid == 0 ? 0u : (uint32_t)SS_NSUB;
     uint64_t key[ITEMS];
     uint32_t msk[ITEMS];
-    uint32_t kmin = 0xffffffffu, kmax = 0u;
-#pragma unroll
-    for (int q = 0; q < ITEMS; q++) {
-        const int j = tid + q * SS_THREADS;
-        key[q] = ~0ull; msk[q] = 0u;
-        if (j < n) {
-            const uint4 e = a.entries[e0 + j];
-            key[q] = ((uint64_t)e.x << 32) | e.y; msk[q] = e.z;
-            kmin = min(kmin, e.x); kmax = max(kmax, e.x);
-        }
-    }
-    kmin = ss_wave_min(kmin); kmax = ss_wave_max(kmax);
-    if (lane == 0) { wred[1][w] = kmin; wred[2][w] = kmax; }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t b = 0, mn = 0xffffffffu, mx = 0u;
-        for (int k = 0; k < SS_THREADS / 64; k++) { b += wred[0][k]; mn = min(mn, wred[1][k]); mx = max(mx, wred[2][k]); }
-        s_before = b; s_kmin = mn; s_kmax = mx;
-    }
-    __syncthreads();
-    const uint32_t kmin0 = s_kmin;
-    const uint64_t kspan = (uint64_t)(s_kmax >= s_kmin ? s_kmax - s_kmin : 0u) + 1ull;
-    const float dmin = __uint_as_float(s_kmin);
-    const float fspan = __uint_as_float(s_kmax) - dmin;
-    const float fscale = (s_kmax > s_kmin && fspan > 0.f) ? (float)SS_NSUB / fspan : 0.f;
-    bool log_map = false;                                              // workgroup-uniform
-    auto sub_of = [&](uint64_t k) -> uint32_t {                        // the maps of ss_sort_expand_kernel
-        const uint32_t kb = (uint32_t)(k >> 32);
-        if (log_map) return (uint32_t)(((uint64_t)(kb - kmin0) * (uint64_t)SS_NSUB) / kspan);
-        const float v = (__uint_as_float(kb) - dmin) * fscale;
-        const uint32_t f = v > 0.f ? (uint32_t)v : 0u;
-        return f < SS_NSUB ? f : SS_NSUB - 1u;
-    };
-    for (int attempt = 0; attempt < 2; attempt++) {
+    ss_load_keys<ITEMS>(a, e0, n, key, msk, wred, s_before, s_kmin, s_kmax);
+    SsDepthMap map(s_kmin, s_kmax);
+    auto sub_of = [&](uint64_t k) -> uint32_t { return map.sub_of(k); };
+    // ss_sort_expand_kernel's histogram loop without the third map.  Not a shared phase: as a function taking the map it cost the kernels registers
+    // (the map behind a reference: <GSR_SS_CAP> 8 -> 76 B of scratch; by value: <GSR_SS_CAP_BIG> 17 -> 31 spilled VGPRs, this kernel 108 -> 116 VGPRs)
+    for (int attempt = 0; attempt < 2; attempt++) {                    // the two analytic maps only
 #pragma unroll
         for (int q = 0; q < ITEMS; q++)
             if (tid + q * SS_THREADS < n) atomicAdd(&start[sub_of(key[q])], 1u);
         __syncthreads();
         if (attempt == 1) break;
-        const uint32_t mx = ss_wave_max(tid < SS_NSUB ? start[tid] : 0u);
+        const uint32_t mx = wave_max_u32(tid < SS_NSUB ? start[tid] : 0u);
         if (lane == 0) wred[1][w] = mx;
         __syncthreads();
         uint32_t m = 0;
         for (int k = 0; k < SS_THREADS / 64; k++) m = max(m, wred[1][k]);
         if (m <= SS_RANK_MAX) break;                                   // workgroup-uniform
-        log_map = true;
+        map.log_map = true;
         __syncthreads();
         if (tid <= SS_NSUB) start[tid] = 0u;
         __syncthreads();
     }
-    {
-        const uint32_t v = tid < SS_NSUB ? start[tid] : 0u;
-        const uint32_t incl = ss_wave_incl_scan(v, lane);
-        if (lane == 63) wred[0][w] = incl;
-        __syncthreads();
-        uint32_t ex = incl - v;
-        for (int k = 0; k < w; k++) ex += wred[0][k];
-        if (tid < SS_NSUB) start[tid] = ex;
-        if (tid == SS_NSUB) start[SS_NSUB] = (uint32_t)n;
-    }
+    ss_scan_starts(n, start, cur, wred[0]);
     __syncthreads();
     // the cut: group p starts at the first sub-bucket whose first position is at or beyond p n / PARTS
     if (tid < SS_NSUB) {
@@ -745,16 +729,12 @@ __global__ __launch_bounds__(SS_THREADS, 4) void ss_sort_expand_split_kernel(SsS
     if (tid < SS_NSUB) cur[tid] = start[tid] - base0;                  // only [g0, g1) is used
     __syncthreads();
     // own entries into LDS; what the bin's entries of the groups before this one, and all of them, put into each tile
-    auto spread8 = [](uint32_t x) {
-        x = (x | (x << 12)) & 0x000f000fu; x = (x | (x << 6)) & 0x03030303u; x = (x | (x << 3)) & 0x11111111u;
-        return x;
-    };
     uint32_t tlo = 0u, thi = 0u, blo = 0u, bhi = 0u;                   // nibble counters (<= ITEMS < 16 per thread)
 #pragma unroll
     for (int q = 0; q < ITEMS; q++)
         if (tid + q * SS_THREADS < n) {
             const uint32_t sb = sub_of(key[q]);
-            const uint32_t lo = spread8(msk[q] & 0xffu), hi = spread8(msk[q] >> 8);
+            const uint32_t lo = ss_spread8(msk[q] & 0xffu), hi = ss_spread8(msk[q] >> 8);
             tlo += lo; thi += hi;
             if (sb < g0) { blo += lo; bhi += hi; }
             else if (sb < g1) {
@@ -762,112 +742,26 @@ __global__ __launch_bounds__(SS_THREADS, 4) void ss_sort_expand_split_kernel(SsS
                 if (GSR_IDX_OK(pos, CAP, a.hdr + GSR_DBG_GEOM_WORD, GSR_BOUND_SS_LDS_POS)) { buf[pos] = key[q]; mbuf[pos] = (uint16_t)msk[q]; }
             }
         }
-    {   // workgroup sums of the per-tile counts, two tiles to a word (<= 14 336 < 2^16 each)
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int sh = 8 * (k & 3);
-            const uint32_t ts = k < 4 ? tlo : thi, bs = k < 4 ? blo : bhi;
-            const uint32_t tw = ((ts >> sh) & 0xfu) | (((ts >> (sh + 4)) & 0xfu) << 16);
-            const uint32_t bw = ((bs >> sh) & 0xfu) | (((bs >> (sh + 4)) & 0xfu) << 16);
-            const uint32_t tsum = ss_wave_sum(tw), bsum = ss_wave_sum(bw);
-            if (lane == 0) { wsum[0][w][k] = tsum; wsum[1][w][k] = bsum; }
-        }
-    }
-    __syncthreads();
-    if (tid < 16) {
-        uint32_t tot = 0u, bef = 0u;
-        for (int k = 0; k < SS_THREADS / 64; k++) {
-            tot += (wsum[0][k][tid >> 1] >> (16 * (tid & 1))) & 0xffffu;
-            bef += (wsum[1][k][tid >> 1] >> (16 * (tid & 1))) & 0xffffu;
-        }
-        uint32_t incl = tot;
-#pragma unroll
-        for (int d = 1; d < 16; d <<= 1) {
-            const uint32_t t = __shfl_up(incl, d);
-            if (tid >= d) incl += t;
-        }
-        const uint32_t st = s_before + incl - tot;
-        tile_start[tid] = st; tile_before[tid] = bef;
-        if (part == 0) {
-            const int tx = (s % a.SX) * GSR_SS_TILES + (tid & 3), ty = (s / a.SX) * GSR_SS_TILES + (tid >> 2);
-            if (tx < a.gridx && ty < a.gridy) a.ranges[ty * a.gridx + tx] = make_uint2(st, st + tot);
-        }
-    }
-    __syncthreads();
-    uint32_t *sid = reinterpret_cast<uint32_t *>(buf);
-    uint16_t *smask = reinterpret_cast<uint16_t *>(sid + CAP);
-    {
-        uint32_t rk[ITEMS_P], id[ITEMS_P], mm[ITEMS_P];
-#pragma unroll
-        for (int q = 0; q < ITEMS_P; q++) {
-            const int j = tid + q * SS_THREADS;
-            rk[q] = 0u; id[q] = 0u; mm[q] = 0u;
-            if (j < np) {
-                const uint64_t me = buf[j];
-                const uint32_t sb = sub_of(me);
-                const uint32_t a0 = start[sb] - base0, a1 = start[sb + 1] - base0;
-                uint32_t r = a0, k = a0;
-                for (; k + 8 <= a1; k += 8) {
-                    uint64_t v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; u++) v[u] = buf[k + u];
-#pragma unroll
-                    for (int u = 0; u < 8; u++) r += v[u] < me ? 1u : 0u;
-                }
-                for (; k < a1; k++) r += buf[k] < me ? 1u : 0u;
-                rk[q] = r; id[q] = (uint32_t)me; mm[q] = mbuf[j];
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < ITEMS_P; q++)
-            if (tid + q * SS_THREADS < np) { sid[rk[q]] = id[q]; smask[rk[q]] = (uint16_t)mm[q]; }
-    }
-    __syncthreads();
-    uint32_t m[ITEMS_P], idv[ITEMS_P];
-    const int jb = tid * ITEMS_P;
-#pragma unroll
-    for (int q = 0; q < ITEMS_P; q++) {
-        const int j = jb + q;
-        m[q] = j < np ? (uint32_t)smask[j] : 0u;
-        idv[q] = j < np ? sid[j] : 0u;
-    }
-    uint32_t c[8];
-    {
-        uint32_t nlo = 0u, nhi = 0u;
-#pragma unroll
-        for (int q = 0; q < ITEMS_P; q++) { nlo += spread8(m[q] & 0xffu); nhi += spread8(m[q] >> 8); }
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint32_t src = k < 4 ? nlo : nhi;
-            const int sh = 8 * (k & 3);
-            c[k] = ((src >> sh) & 0xfu) | (((src >> (sh + 4)) & 0xfu) << 16);
-        }
-    }
-    uint32_t ex[8];
+    uint32_t tw[8], bw[8];                                             // workgroup sums of the per-tile counts, two tiles to a word (<= 14 336 < 2^16 each)
+    ss_packed_counts(tlo, thi, tw); ss_packed_counts(blo, bhi, bw);
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-        const uint32_t incl = ss_wave_incl_scan(c[k], lane);
-        ex[k] = incl - c[k];
-        if (lane == 63) wsum[0][w][k] = incl;
+        const uint32_t tsum = wave_sum_u32(tw[k]), bsum = wave_sum_u32(bw[k]);
+        if (lane == 0) { wsum[0][w][k] = tsum; wsum[1][w][k] = bsum; }
     }
     __syncthreads();
-    for (int k = 0; k < w; k++) {
-#pragma unroll
-        for (int u = 0; u < 8; u++) ex[u] += wsum[0][k][u];
+    if (tid < 16) {                                                    // what the groups before this part put into tile tid
+        uint32_t bef = 0u;
+        for (int k = 0; k < SS_THREADS / 64; k++) bef += ss_packed_get(wsum[1][k], tid);
+        tile_before[tid] = bef;
     }
-    uint32_t pos[16];
-#pragma unroll
-    for (int t = 0; t < 16; t++) pos[t] = tile_start[t] + tile_before[t] + ((ex[t >> 1] >> (16 * (t & 1))) & 0xffffu);
-#pragma unroll
-    for (int q = 0; q < ITEMS_P; q++) {
-#pragma unroll
-        for (int t = 0; t < 16; t++) {
-            const uint32_t bitv = (m[q] >> t) & 1u;
-            if (bitv && GSR_IDX_OK(pos[t], a.hdr[SS_HDR_N], a.hdr + GSR_DBG_GEOM_WORD, GSR_BOUND_POINT_LIST)) a.point_list[pos[t]] = idv[q];
-            pos[t] += bitv;
-        }
-    }
+    ss_tile_totals(a, s, s_before, wsum[0], tile_start, part == 0);
+    __syncthreads();
+    ss_rank<ITEMS_P, CAP>(np, base0, sub_of, start, buf);
+    __syncthreads();
+    uint32_t m[ITEMS_P], idv[ITEMS_P], ex[8];
+    ss_expand_scan<ITEMS_P, CAP>(np, buf, m, idv, ex, wsum[0]);
+    ss_expand_stores<ITEMS_P>(a, m, idv, ex, [&](int t) { return tile_start[t] + tile_before[t]; });
 }
 
 static hipError_t ss_set_lds_attr(const void *fn, size_t bytes, std::atomic<uint64_t> &flags) {

@@ -43,34 +43,6 @@ TileListPlan tile_list_plan(int P, int64_t E, int W, int H) {
     return p;
 }
 
-__device__ __forceinline__ uint32_t tl_wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-__device__ __forceinline__ uint32_t tl_wave_max(uint32_t v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m));
-    return v;
-}
-__device__ __forceinline__ uint32_t tl_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m);
-    return v;
-}
-
-struct SuperRect { int x0, x1, y0, y1, sx0, sx1, sy0, sy1; };
-__device__ __forceinline__ SuperRect super_rect(uint4 rc, int SX, int SY) {
-    SuperRect r;
-    r.x0 = (int)(rc.x & 0xffffu); r.x1 = (int)(rc.x >> 16); r.y0 = (int)(rc.y & 0xffffu); r.y1 = (int)(rc.y >> 16);
-    // tile rectangles lie inside the grid; the clamp only bounds the loops should a record ever be garbage
-    r.sx0 = r.x0 >> 3; r.sx1 = min((r.x1 + 7) >> 3, SX); r.sy0 = r.y0 >> 3; r.sy1 = min((r.y1 + 7) >> 3, SY);
-    return r;
-}
-
 // ---- level 1a: entries per (super-tile, workgroup) ----
 __global__ __launch_bounds__(TL_L1_THREADS) void tl_count_kernel(int P, const uint32_t *__restrict__ hdr, int SX, int SY, int nblk1,
                                                                  const uint4 *__restrict__ orect, uint32_t *__restrict__ mat1) {
@@ -82,7 +54,7 @@ __global__ __launch_bounds__(TL_L1_THREADS) void tl_count_kernel(int P, const ui
     __syncthreads();
     const int r = blockIdx.x * TL_L1_THREADS + threadIdx.x;
     if (r < Pl) {
-        const SuperRect q = super_rect(orect[r], SX, SY);
+        const SuperRect q = super_rect<8>(orect[r], SX, SY);
         if (q.x1 > q.x0)
             for (int sy = q.sy0; sy < q.sy1; sy++)
                 for (int sx = q.sx0; sx < q.sx1; sx++) atomicAdd(&cnt[sy * SX + sx], 1u);
@@ -100,7 +72,7 @@ __global__ __launch_bounds__(1024) void tl_binscan_kernel(int nblk1, uint32_t *_
     for (int base = 0; base < nblk1; base += 1024) {                     // workgroup-uniform
         const int j = base + (int)threadIdx.x;
         const uint32_t v = j < nblk1 ? row[j] : 0u;
-        const uint32_t incl = tl_wave_incl_scan(v, lane);
+        const uint32_t incl = wave_incl_scan_u32(v, lane);
         if (lane == 63) wsum[w] = incl;
         __syncthreads();
         uint32_t ex = incl - v, tot = 0;
@@ -142,7 +114,7 @@ __global__ __launch_bounds__(TL_L1_THREADS) void tl_scatter_kernel(TlScatterArgs
     {   // list start of every super-tile and its first segment (S <= TL_L1_THREADS: one per thread)
         const uint32_t v = my_total;
         const uint32_t sg = tid < S ? max(1u, (v + TL_SEG - 1) / TL_SEG) : 0u;
-        const uint32_t iv = tl_wave_incl_scan(v, lane), is = tl_wave_incl_scan(sg, lane);
+        const uint32_t iv = wave_incl_scan_u32(v, lane), is = wave_incl_scan_u32(sg, lane);
         if (lane == 63) { wsum[0][w] = iv; wsum[1][w] = is; }
         __syncthreads();
         uint32_t ev = iv - v, es = is - sg;
@@ -156,7 +128,7 @@ __global__ __launch_bounds__(TL_L1_THREADS) void tl_scatter_kernel(TlScatterArgs
         }
     }
     __syncthreads();
-    const SuperRect q = super_rect(rc, a.SX, a.SY);
+    const SuperRect q = super_rect<8>(rc, a.SX, a.SY);
     const bool emits = q.x1 > q.x0;
     if (emits)
         for (int sy = q.sy0; sy < q.sy1; sy++)
@@ -322,7 +294,7 @@ __global__ __launch_bounds__(1024) void tl_tilescan_kernel(const uint32_t *__res
     __syncthreads();
     if (threadIdx.x < 64) {
         const uint32_t v = tot[t];
-        const uint32_t incl = tl_wave_incl_scan(v, t);
+        const uint32_t incl = wave_incl_scan_u32(v, t);
         tile_off[(size_t)s * 64 + t] = incl - v;
         if (t == 63) st_pairs[s] = incl;
     }
@@ -341,7 +313,7 @@ __global__ __launch_bounds__(256) void tl_expand_kernel(int S, int SX, int gridx
     const int s = (int)seg_super[seg];
     uint32_t before = 0;                                                 // pairs of the super-tiles before this one
     for (int k = lane; k < s; k += 64) before += st_pairs[k];
-    before = tl_wave_sum(before);
+    before = wave_sum_u32(before);
     const uint32_t off = before + tile_off[(size_t)s * 64 + lane];
     if (seg == segbase[s]) {                                             // the first segment publishes the tile ranges
         const int tx = (s % SX) * 8 + (lane & 7), ty = (s / SX) * 8 + (lane >> 3);
@@ -369,7 +341,7 @@ __global__ __launch_bounds__(256) void tl_expand_kernel(int S, int SX, int gridx
     uint32_t pc[TL_SEG / 64], cnt = 0, most = 0;
 #pragma unroll
     for (int qq = 0; qq < TL_SEG / 64; qq++) { pc[qq] = (uint32_t)__popcll(col[qq]); cnt += pc[qq]; most = max(most, pc[qq]); }
-    const uint32_t lincl = tl_wave_incl_scan(cnt, lane);
+    const uint32_t lincl = wave_incl_scan_u32(cnt, lane);
     const uint32_t lstart = lincl - cnt;                                 // this tile's run inside the slice
     const uint32_t total = (uint32_t)__shfl((int)lincl, 63);
     const bool staged = total <= TL_STAGE;                               // wave-uniform
@@ -380,7 +352,7 @@ __global__ __launch_bounds__(256) void tl_expand_kernel(int S, int SX, int gridx
 #pragma unroll
         for (int qq = 0; qq < TL_SEG / 64; qq++) { cur[qq] = run; run += pc[qq]; }
     }
-    const int iters = (int)tl_wave_max(most);
+    const int iters = (int)wave_max_u32(most);
     for (int it = 0; it < iters; it++) {                                 // wave-uniform trip count: every lane feeds the shuffles
 #pragma unroll
         for (int qq = 0; qq < TL_SEG / 64; qq++) {

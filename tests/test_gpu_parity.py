@@ -103,6 +103,17 @@ def test_stages_bit_exact_against_oracle(kw, two_level, upstream_tile_rule):
     dict(P=6000, width=64, height=64, sh_degree=0, s0=0.5, seed=41, zmin=4.0, zmax=4.0),     # one bin of 6000 entries, ONE depth
     dict(P=6500, width=64, height=64, sh_degree=0, s0=0.3, seed=42, zmin=0.21, zmax=40.0),   # one bin, depths over 7 octaves
     dict(P=13000, width=64, height=64, sh_degree=0, s0=0.3, seed=43, zmin=0.21, zmax=40.0),  # 7168 < bin <= 14336: one workgroup per CU
+    # Three more routes through supertile_sort.hip's sort-expand kernels.  The sub-bucket figures come from emulating the kernels' maps on
+    # the f32 oracle's depths (512 sub-buckets, retry thresholds 96 and 1024, the split kernel's cut); the library has no route indicator.
+    # One bin of 6500: the linear map puts 6480 in one sub-bucket (> 96), the bit-linear map's largest holds 196 (<= 1024):
+    # single kernel, second map.
+    dict(P=6500, width=64, height=64, sh_degree=0, s0=0.3, seed=46, zmin=3.0, zmax=6.0, outliers=20),
+    # One bin of 13000: linear map 12980 in one sub-bucket, bit-linear map's largest 422, cut into parts of 3294 / 3496 / 3000 / 3210
+    # (all <= 7168): split kernel, second map.
+    dict(P=13000, width=64, height=64, sh_degree=0, s0=0.3, seed=47, zmin=3.0, zmax=6.0, outliers=20),
+    # One bin of 13000 at ONE depth: every map puts them into sub-bucket 0, the cut does not fit: the split kernel flags the bin as
+    # unsplit and the big-buffer kernel (flagged bins only) orders it with the splitter map.
+    dict(P=13000, width=64, height=64, sh_degree=0, s0=0.5, seed=44, zmin=4.0, zmax=4.0),
 ])
 def test_tile_lists_bit_exact(kw, upstream_tile_rule, lists_mode):
     """Both sort-free list builders against the oracle's sorted pair list, per tile, on grids that stress the super-tile
