@@ -126,6 +126,22 @@ DENSITY_SIGNATURES = {
                                  _p, _p, _p, _p, _sz]),                                  # scaling rotation noise ws ws_bytes
 }
 
+# include/gsr_depth.h (likewise a table of its own)
+DEPTH_EXPECTED, DEPTH_INVERSE = 0, 1
+DEPTH_SIGNATURES = {
+    "gsr_depth_workspace_bytes": (_i32, [_i32, C.POINTER(_sz)]),                         # P bytes
+    "gsr_depth_forward": (_i32, [_p, _i32, _i32, _i32, C.c_int64, _i32,                  # stream P W H R mode
+                                 _p, _sz, _p, _sz, _p, _sz,                              # geom binning img (+bytes)
+                                 _p, _p]),                                               # out_depth out_alpha
+    "gsr_depth_backward": (_i32, [_p, _i32, _i32, _i32, C.c_int64, _i32,                 # stream P W H R mode
+                                  _p, _p, _p, _f, _p, _p,                                # means3D radii scales mod rotations cov3D
+                                  _p, _p, _p, _f, _f,                                    # view proj campos tanfovx tanfovy
+                                  _p, _p,                                                # dL_ddepth dL_dalpha
+                                  _p, _sz, _p, _sz, _p, _sz, _p, _sz,                    # geom binning img ws (+bytes)
+                                  _i32,                                                  # accumulate
+                                  _p, _p, _p, _p, _p, _p]),                              # dL_d{means2D opacity means3D cov3D scales rots}
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -152,7 +168,8 @@ def load() -> C.CDLL:
             lib = C.CDLL(LIB_PATH)
         except OSError as e:
             raise GsrError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES, **SEQUENCE_SIGNATURES, **ROWS_SIGNATURES, **DENSITY_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES, **SEQUENCE_SIGNATURES, **ROWS_SIGNATURES, **DENSITY_SIGNATURES,
+                                   **DEPTH_SIGNATURES}.items():
             fn = getattr(lib, name)       # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,454 @@
+// depth_maps.hip -- depth and accumulated-opacity maps of a render, with gradients (include/gsr_depth.h): kernels and entry points.
+//
+// Built beside the colour path, which it does not touch: both walks re-read what gsr_forward left on the device -- the per-tile lists,
+// the records (centre, conic, opacity, view-space depth), the reachability bytes per (entry, 8x8 block), final_T and n_contrib per
+// pixel -- so no per-Gaussian stage and no list build runs again.
+//
+// CDNA4 shape, as composite_bwd.hip's classic decomposition: a wave64 owns the two 8x8 blocks of one half tile (they lie side by side
+// and share dy, so the exponent is formed with gsr_device.h's row terms, the form the colour pass uses: same bits, same decisions);
+// lane l holds pixel l of each block.  Waves never synchronise with each other: each stages the list 64 entries at a time into its own
+// LDS slice (id -> record gather, 7 of the 12 floats: px py conic x 3, opacity, depth) and walks the set bits of the ballot of
+// reachable entries.  The walk ends at the half tile's largest last contributor; a pixel blends the entries in front of its own.
+//   forward: front to back, D += v alpha T, T = T - alpha T.  The stop test is not evaluated: no entry in front of the last contributor
+//            triggered it.  alpha map = 1 - final_T, read, not re-composited.
+//   reverse: back to front with the running suffix S = sum_{j > i} v_j alpha_j T_j and T reconstructed from final_T as bwd_unit does it:
+//            dL/dalpha = gD (v T_i - S / (1 - alpha)) + gA T_final / (1 - alpha); the 0.99 cap straight-through, 1 / (1 - alpha) by
+//            v_rcp_f32 as there.  (bwd_unit's own recurrence for the colour (v, 1, 0) is the same sum, but forms the alpha term as
+//            1 - (alpha composited behind, normalised): in a pixel that saturates that is 1 - 0.9999.., and float32 loses three digits
+//            of dL/dopacity -- measured against the float64 oracle.)  Seven sums per (wave, entry): the six moments of
+//            s = opacity G dL/dalpha (slots 3..8 of the 16-float accumulator row, gsr_internal.h) and dL/dv (spare slot 9), reduced
+//            through LDS + two DPP steps and issued as ONE 7-lane global_atomic_add_f32 into 28 contiguous bytes of the row, only when
+//            some lane blended.  A splat with replica rows adds into replica (tile mod K).
+// pergauss_bwd.hip's streaming kernel then runs unchanged on these rows (no colour input at all: shs = colors_precomp = NULL is a case
+// its launcher already takes), and depth_finish_kernel adds the dL/dv term to dL/dmeans3D -- and, with accumulate, the whole result
+// to the caller's buffers.
+// Zeroing: only the rows that can be added into (marked Gaussians + replica rows) are cleared, by composite_bwd.hip's
+// launch_zero_marked_rows: 64 B per marked row and a byte read per Gaussian instead of a 66 P byte memset.
+#include <string.h>
+
+#include "../../include/gsr_depth.h"
+#include "gsr_device.h"
+#include "gsr_host.h"
+#include "gsr_internal.h"
+
+namespace gsr {
+namespace {
+
+#define DRED_STRIDE 68                                  // as composite_bwd.hip: rows of 64 would start in one LDS bank
+#define DEPTH_NSUM 7                                    // s dx, s dy, s dx dx, s dx dy, s dy dy, s, dL/dv -> row slots 3..9
+#define DEPTH_BWD_LDS_F4 (64 * 2 + (DEPTH_NSUM * DRED_STRIDE + 3) / 4)
+
+struct DepthArgs {
+    int W, H, gridx, gridy, P, mode;
+    size_t list_len;             // R: entries of point_list, stride of contrib
+    size_t acc_rows;             // rows of acc (reverse pass)
+    const uint8_t *contrib;      // [4][list_len]
+    const uint2 *ranges;
+    const uint32_t *point_list;
+    const float *rec;
+    const float *final_T;
+    const uint32_t *n_contrib;
+    float *out_depth, *out_alpha;           // forward (either may be NULL)
+    const float *gD, *gA;                   // reverse (either may be NULL)
+    float *acc;
+};
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+    const int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true);
+    return v + __int_as_float(moved);
+}
+
+// what a wave knows of its half tile before it walks: pixel coordinates, each pixel's last contributor (0 outside the image), the
+// largest one per block and overall (clamped to the list: a garbage n_contrib cannot send the walk past the tile's range)
+struct HalfTile {
+    float fx[2], fy;
+    bool inside[2];
+    size_t pix[2];
+    int last[2], blk_last[2], hi;
+    uint2 range;
+};
+__device__ __forceinline__ HalfTile half_tile(const DepthArgs &a, const int tile, const int sub, const int lane) {
+    HalfTile h;
+    const int tx = tile % a.gridx, ty = tile / a.gridx;
+    h.range = a.ranges[tile];
+    const int y = ty * GSR_TILE + sub * 8 + (lane >> 3);
+    h.fy = (float)y;
+    int hi = 0;
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const int x = tx * GSR_TILE + q * 8 + (lane & 7);
+        h.inside[q] = x < a.W && y < a.H;
+        h.pix[q] = (size_t)(h.inside[q] ? y : 0) * a.W + (h.inside[q] ? x : 0);
+        h.fx[q] = (float)x;
+        h.last[q] = h.inside[q] ? (int)a.n_contrib[h.pix[q]] : 0;
+        int m = h.last[q];
+#pragma unroll
+        for (int sft = 32; sft > 0; sft >>= 1) m = max(m, __shfl_xor(m, sft));
+        h.blk_last[q] = __builtin_amdgcn_readfirstlane(m);
+        hi = max(hi, h.blk_last[q]);
+    }
+    const long long n = (long long)h.range.y - (long long)h.range.x;
+    h.hi = (int)min((long long)hi, max(n, 0ll));
+    return h;
+}
+
+// stages entry base + lane of the tile's list: (px, py, a, b) (c, opacity, v, bits | row << 4); returns whether the entry reaches a block
+__device__ __forceinline__ bool stage_entry(const DepthArgs &a, const HalfTile &h, float4 *my, const int tile, const int sub, const int base,
+                                            const int cnt, const int lane, const bool want_row) {
+    if (lane >= cnt) return false;
+    const size_t at = (size_t)h.range.x + base + lane;
+    if (at >= a.list_len) return false;
+    const uint32_t g = a.point_list[at];
+    if (g >= (uint32_t)a.P) return false;
+    const float4 *rec4 = reinterpret_cast<const float4 *>(a.rec) + 3 * (size_t)g;
+    const float4 r0 = rec4[0], r1 = rec4[1], r2 = rec4[2];
+    uint32_t bits = 0u;
+#pragma unroll
+    for (int q = 0; q < 2; q++) bits |= a.contrib[(size_t)(sub * 2 + q) * a.list_len + at] ? (1u << q) : 0u;
+    uint32_t row = g;
+    if (want_row) {
+        const uint32_t hot = __float_as_uint(r2.w);      // replica code (gsr_internal.h): 0 = the Gaussian's own row
+        if (hot) row = (uint32_t)a.P + (hot >> 4) + ((uint32_t)tile & ((1u << (hot & 15u)) - 1u));
+        if ((size_t)row >= a.acc_rows) return false;
+    }
+    const StagedConic sc = stage_conic(r0.z, r0.w, r1.x);        // as the colour pass stages it
+    const float v = a.mode == GSR_DEPTH_INVERSE ? 1.0f / r2.y : r2.y;
+    my[lane] = make_float4(r0.x, r0.y, sc.a, sc.b);
+    my[64 + lane] = make_float4(sc.c, r1.y, v, __uint_as_float(bits | (row << 4)));      // row < 2^28 (checked by the entry point)
+    return bits != 0u;
+}
+
+__global__ __launch_bounds__(256) void depth_fwd_kernel(DepthArgs a) {
+    __shared__ __align__(16) float4 stage[4][128];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int unit = blockIdx.x * 4 + wave, tile = unit >> 1, sub = unit & 1;
+    if (tile >= a.gridx * a.gridy) return;              // wave-uniform
+    float4 *my = stage[wave];
+    HalfTile h = half_tile(a, tile, sub, lane);
+    if (!a.out_depth) h.hi = 0;                         // the alpha map alone is a read of final_T
+    float Tr[2] = {1.f, 1.f}, D[2] = {0.f, 0.f};
+    for (int base = 0; base < h.hi; base += 64) {
+        const int cnt = min(64, h.hi - base);
+        __builtin_amdgcn_wave_barrier();
+        const bool live = stage_entry(a, h, my, tile, sub, base, cnt, lane, false);
+        uint64_t todo = __ballot(live);
+        __builtin_amdgcn_wave_barrier();
+        while (todo) {
+            const int j = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const float4 r0 = my[j], r1 = my[64 + j];
+            const uint32_t bits = __builtin_amdgcn_readfirstlane(__float_as_uint(r1.w)) & 3u;
+            const int pos = base + j;
+            const StagedConic kc = {r0.z, r0.w, r1.x};
+            const RowTerms rt = splat_row_terms(kc, r0.y - h.fy);
+#pragma unroll
+            for (int q = 0; q < 2; q++) {
+                if (!(bits & (1u << q)) || pos >= h.blk_last[q]) continue;          // scalar branch
+                float araw;                                                          // the one evaluation every pass shares (gsr_device.h)
+                const unsigned long long okm = splat_alpha(splat_power_log2_row(kc, rt, r0.x - h.fx[q]), r1.y, araw) &
+                                               __builtin_amdgcn_ballot_w64(pos < h.last[q]);
+                const float alpha = fminf(GSR_ALPHA_MAX, araw);
+                const float aT = alpha * Tr[q];
+                if (__builtin_amdgcn_inverse_ballot_w64(okm)) {
+                    D[q] += r1.z * aT;
+                    Tr[q] = Tr[q] - aT;                                              // T (1 - alpha), the colour pass's form
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        if (!h.inside[q]) continue;
+        if (a.out_depth) a.out_depth[h.pix[q]] = D[q];
+        if (a.out_alpha) a.out_alpha[h.pix[q]] = 1.f - a.final_T[h.pix[q]];
+    }
+}
+
+__global__ __launch_bounds__(256) void depth_bwd_kernel(DepthArgs a) {
+    __shared__ __align__(16) float4 stage[4][DEPTH_BWD_LDS_F4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int unit = blockIdx.x * 4 + wave, tile = unit >> 1, sub = unit & 1;
+    if (tile >= a.gridx * a.gridy) return;              // wave-uniform
+    float4 *my = stage[wave];
+    float *red = reinterpret_cast<float *>(my + 128);   // [value 0..6][lane 0..63], rows of DRED_STRIDE floats
+    const HalfTile h = half_tile(a, tile, sub, lane);
+    if (h.hi <= 0) return;
+    // per pixel: Tr = transmittance behind the splats visited so far, S = sum of v alpha T over them (the running suffix of the depth
+    // map), gAT = gA T_final
+    float Tr[2], S[2] = {0.f, 0.f}, gD[2], gAT[2];
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        Tr[q] = h.inside[q] ? a.final_T[h.pix[q]] : 1.f;
+        gD[q] = h.inside[q] && a.gD ? a.gD[h.pix[q]] : 0.f;
+        gAT[q] = h.inside[q] && a.gA ? a.gA[h.pix[q]] * Tr[q] : 0.f;
+    }
+    // lane 4 value + part adds red[value][16 part .. 16 part + 15]; two DPP steps fold the four parts; lanes 0, 4, .., 24 hold the totals
+    const int rvalue = lane >> 2, rpart = lane & 3;
+    const bool red_lane = rvalue < DEPTH_NSUM;
+    const float4 *red_rd = reinterpret_cast<const float4 *>(red + (red_lane ? rvalue : 0) * DRED_STRIDE + rpart * 16);
+    const int slot = (red_lane && rpart == 0) ? 3 + rvalue : -1;
+
+    for (int base = ((h.hi - 1) >> 6) << 6; base >= 0; base -= 64) {
+        const int cnt = min(64, h.hi - base);
+        __builtin_amdgcn_wave_barrier();
+        const bool live = stage_entry(a, h, my, tile, sub, base, cnt, lane, true);
+        uint64_t todo = __ballot(live);
+        __builtin_amdgcn_wave_barrier();
+        while (todo) {
+            const int j = 63 - __builtin_clzll(todo);   // back to front
+            todo &= ~(1ull << j);
+            const float4 r0 = my[j], r1 = my[64 + j];
+            const uint32_t code = __builtin_amdgcn_readfirstlane(__float_as_uint(r1.w));
+            const uint32_t bits = code & 3u, row = code >> 4;
+            const int pos = base + j;
+            const StagedConic kc = {r0.z, r0.w, r1.x};
+            const float dy = r0.y - h.fy;
+            const RowTerms rt = splat_row_terms(kc, dy);
+            float s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f, s5 = 0.f, s6 = 0.f, s7 = 0.f;
+            unsigned long long any_ok = 0ull;
+#pragma unroll
+            for (int q = 0; q < 2; q++) {
+                if (!(bits & (1u << q)) || pos >= h.blk_last[q]) continue;          // scalar branch
+                const float dx = r0.x - h.fx[q];
+                float araw;
+                const unsigned long long okm = splat_alpha(splat_power_log2_row(kc, rt, dx), r1.y, araw) &
+                                               __builtin_amdgcn_ballot_w64(pos < h.last[q]);
+                any_ok |= okm;
+                // lanes that do not blend carry alpha = 0 through the same arithmetic: every sum gets an exact 0 (exp2 of a skipped lane may be inf)
+                const float araw_ok = __builtin_amdgcn_inverse_ballot_w64(okm) ? araw : 0.f;
+                const float alpha = fminf(GSR_ALPHA_MAX, araw_ok);
+                const float inv = __builtin_amdgcn_rcpf(1.f - alpha);
+                const float Tk = Tr[q] * inv;                                        // transmittance in front of this splat
+                // gD (v T_i - S / (1 - alpha)) + gA T_final / (1 - alpha) with T_i = Tr / (1 - alpha): one factor 1 / (1 - alpha).  The alpha
+                // term is formed from T_final itself, not as 1 - (alpha composited behind): no cancellation where a pixel saturates
+                const float dL_dalpha = (gD[q] * (r1.z * Tr[q] - S[q]) + gAT[q]) * inv;
+                const float w = alpha * Tk;
+                S[q] += r1.z * w;
+                Tr[q] = Tk;
+                s7 += w * gD[q];                                                     // dL/dv
+                const float sg = araw_ok * dL_dalpha;                                // pre-cap alpha: the cap is straight-through
+                s6 += sg;
+                const float sx = sg * dx, sy = sg * dy;
+                s1 += sx; s2 += sy;
+                s3 += sx * dx; s4 += sx * dy; s5 += sy * dy;
+            }
+            if (any_ok == 0ull) continue;               // wave-uniform: no pixel of this wave blends the splat
+            red[0 * DRED_STRIDE + lane] = s1; red[1 * DRED_STRIDE + lane] = s2; red[2 * DRED_STRIDE + lane] = s3;
+            red[3 * DRED_STRIDE + lane] = s4; red[4 * DRED_STRIDE + lane] = s5; red[5 * DRED_STRIDE + lane] = s6;
+            red[6 * DRED_STRIDE + lane] = s7;
+            __builtin_amdgcn_wave_barrier();
+            float sel = 0.f;
+            if (red_lane) {
+                const float4 p0 = red_rd[0], p1 = red_rd[1], p2 = red_rd[2], p3 = red_rd[3];
+                sel = ((p0.x + p0.y) + (p0.z + p0.w)) + ((p1.x + p1.y) + (p1.z + p1.w)) +
+                      (((p2.x + p2.y) + (p2.z + p2.w)) + ((p3.x + p3.y) + (p3.z + p3.w)));
+            }
+            __builtin_amdgcn_wave_barrier();
+            sel = dpp_add<0xB1>(sel);   // quad_perm [1,0,3,2]
+            sel = dpp_add<0x4E>(sel);   // quad_perm [2,3,0,1]
+            if (slot >= 0) atomicAdd(a.acc + GSR_ACC_FLOATS * (size_t)row + slot, sel);
+        }
+    }
+}
+
+struct FinishArgs {
+    int P, mode, accumulate;
+    const float *means3D, *viewmatrix;
+    const int *radii;
+    const uint8_t *touched, *clamped;
+    const uint32_t *touch_mark, *hot;
+    const float *acc;
+    // accumulate: the per-Gaussian chain's result (staged in the workspace) is added to the caller's buffers
+    const float *t_means2D, *t_opacity, *t_means3D, *t_cov3D, *t_scales, *t_rots;
+    float *dL_dmeans2D, *dL_dopacity, *dL_dmeans3D, *dL_dcov3D, *dL_dscales, *dL_drots;
+};
+
+// One lane per Gaussian: dL/dmeans3D += dL/dv dv/dz (m[2], m[6], m[10]); with accumulate, out += staged result.  A Gaussian whose mark
+// differs (or that was culled) has no gradient: pergauss_bwd wrote its zeros (accumulate = 0) or nothing is added (accumulate = 1).
+__global__ __launch_bounds__(256) void depth_finish_kernel(FinishArgs f) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= f.P) return;
+    const size_t si = (size_t)i;
+    if (!(f.radii[si] > 0 && (uint32_t)f.touched[si] == *f.touch_mark)) return;
+    float dv = f.acc[GSR_ACC_FLOATS * si + 9];
+    if (f.clamped[si] & 0x80u) {                        // replica rows (gsr_internal.h): their slot 9 is folded in
+        const uint32_t hot = f.hot[si];
+        const size_t first = (size_t)f.P + (hot >> 4);
+        for (uint32_t k = 0; k < (1u << (hot & 15u)); k++) dv += f.acc[GSR_ACC_FLOATS * (first + k) + 9];
+    }
+    const float *m = f.viewmatrix;
+    const float x = f.means3D[3 * si], y = f.means3D[3 * si + 1], z = f.means3D[3 * si + 2];
+    const float zv = m[2] * x + m[6] * y + m[10] * z + m[14];
+    const float g = f.mode == GSR_DEPTH_INVERSE ? -dv / (zv * zv) : dv;
+    const float e0 = g * m[2], e1 = g * m[6], e2 = g * m[10];
+    if (!f.accumulate) {
+        f.dL_dmeans3D[3 * si] += e0; f.dL_dmeans3D[3 * si + 1] += e1; f.dL_dmeans3D[3 * si + 2] += e2;
+        return;
+    }
+    f.dL_dmeans3D[3 * si] += f.t_means3D[3 * si] + e0; f.dL_dmeans3D[3 * si + 1] += f.t_means3D[3 * si + 1] + e1;
+    f.dL_dmeans3D[3 * si + 2] += f.t_means3D[3 * si + 2] + e2;
+    f.dL_dmeans2D[3 * si] += f.t_means2D[3 * si]; f.dL_dmeans2D[3 * si + 1] += f.t_means2D[3 * si + 1];
+    f.dL_dopacity[si] += f.t_opacity[si];
+    if (f.dL_dcov3D) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) f.dL_dcov3D[6 * si + k] += f.t_cov3D[6 * si + k];
+    }
+    if (f.dL_dscales) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) f.dL_dscales[3 * si + k] += f.t_scales[3 * si + k];
+#pragma unroll
+        for (int k = 0; k < 4; k++) f.dL_drots[4 * si + k] += f.t_rots[4 * si + k];
+    }
+}
+
+// ---- host side ----
+#define GSR_TRY(expr) do { const int32_t _rc = (expr); if (_rc != GSR_OK) return _rc; } while (0)
+inline int grid_dim(int px) { return (int)(((long long)px + GSR_TILE_HOST - 1) / GSR_TILE_HOST); }
+inline size_t acc_bytes(int P) { return align_up(acc_rows(P) * GSR_ACC_FLOATS * sizeof(float)); }
+inline size_t stage_floats(int P) { return (size_t)(P > 0 ? P : 0) * 20; }      // rots 4 | means2D 3 | means3D 3 | opacity 1 | scales 3 | cov3D 6
+inline size_t workspace_bytes(int P) { return acc_bytes(P) + align_up(stage_floats(P) * sizeof(float)); }
+
+int32_t sizes_and_mode(const char *who, int P, int W, int H, long long R, int mode) {
+    if (P < 0 || W <= 0 || H <= 0 || R < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+    if (W > 65535 * GSR_TILE_HOST || H > 65535 * GSR_TILE_HOST || (long long)grid_dim(W) * grid_dim(H) > (1ll << 28)) return fail(GSR_ERR_INVALID_ARGUMENT, "image too large");
+    if (mode != GSR_DEPTH_EXPECTED && mode != GSR_DEPTH_INVERSE)
+        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: mode %d is neither 0 (expected depth) nor 1 (inverse depth)", who, mode);
+    return GSR_OK;
+}
+
+// the three workspaces of the gsr_forward before this call, as gsr_api.hip carves them
+struct Views { GeomView g; ImageView im; BinningView b; };
+int32_t carve(Views &v, int P, int W, int H, long long R, const void *geom_ws, size_t geom_bytes, const void *binning_ws, size_t binning_bytes,
+              const void *img_ws, size_t img_bytes) {
+    size_t stb = 0, dtb = 0;
+    HIP_TRY(scan_temp_bytes(P, &stb), "scan temp query");
+    HIP_TRY(depth_sort_temp_bytes(P, &dtb), "depth sort temp query");
+    v.g = carve_geom(const_cast<void *>(geom_ws), P, stb, dtb);
+    v.im = carve_image(const_cast<void *>(img_ws), W, H);
+    v.b = carve_binning(const_cast<void *>(binning_ws), R, 0);
+    if (geom_bytes < v.g.total_bytes) return fail(GSR_ERR_WORKSPACE, "geom workspace %zu < %zu", geom_bytes, v.g.total_bytes);
+    if (img_bytes < v.im.total_bytes) return fail(GSR_ERR_WORKSPACE, "image workspace %zu < %zu", img_bytes, v.im.total_bytes);
+    if (binning_bytes < v.b.list_bytes) return fail(GSR_ERR_WORKSPACE, "binning workspace too small for R=%lld (%zu < %zu)", R, binning_bytes, v.b.list_bytes);
+    return GSR_OK;
+}
+DepthArgs walk_args(const Views &v, int P, int W, int H, long long R, int mode) {
+    DepthArgs a;
+    memset(&a, 0, sizeof a);
+    a.W = W; a.H = H; a.gridx = grid_dim(W); a.gridy = grid_dim(H); a.P = P; a.mode = mode; a.list_len = (size_t)R;
+    a.contrib = v.b.contrib; a.ranges = v.im.ranges; a.point_list = v.b.point_list; a.rec = v.g.rec;
+    a.final_T = v.im.final_T; a.n_contrib = v.im.n_contrib;
+    return a;
+}
+inline unsigned walk_blocks(const DepthArgs &a) { return (unsigned)((2ll * a.gridx * a.gridy + 3) / 4); }
+
+}  // namespace
+}  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+int32_t gsr_depth_workspace_bytes(int32_t P, size_t *bytes) {
+    if (P < 0 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_depth_workspace_bytes: bad argument");
+    *bytes = workspace_bytes(P);
+    return GSR_OK;
+}
+
+int32_t gsr_depth_forward(gsr_stream_t stream, int32_t P, int32_t W, int32_t H, int64_t R, int32_t mode,
+                          const void *geom_ws, size_t geom_bytes, const void *binning_ws, size_t binning_bytes,
+                          const void *img_ws, size_t img_bytes, float *out_depth, float *out_alpha) {
+    hipStream_t s = (hipStream_t)stream;
+    GSR_TRY(sizes_and_mode("gsr_depth_forward", P, W, H, (long long)R, mode));
+    if (!out_depth && !out_alpha) return GSR_OK;
+    if (P == 0 || R == 0) {
+        const size_t n = (size_t)W * H * sizeof(float);
+        if (out_depth) HIP_TRY(hipMemsetAsync(out_depth, 0, n, s), "clear depth map");
+        if (out_alpha) HIP_TRY(hipMemsetAsync(out_alpha, 0, n, s), "clear alpha map");
+        return GSR_OK;
+    }
+    if (!geom_ws || !binning_ws || !img_ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_depth_forward: missing workspace");
+    Views v;
+    GSR_TRY(carve(v, P, W, H, (long long)R, geom_ws, geom_bytes, binning_ws, binning_bytes, img_ws, img_bytes));
+    DepthArgs a = walk_args(v, P, W, H, (long long)R, mode);
+    a.out_depth = out_depth; a.out_alpha = out_alpha;
+    hipLaunchKernelGGL(depth_fwd_kernel, dim3(walk_blocks(a)), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError(), "depth forward launch");
+    return GSR_OK;
+}
+
+int32_t gsr_depth_backward(gsr_stream_t stream, int32_t P, int32_t W, int32_t H, int64_t R, int32_t mode,
+                           const float *means3D, const int32_t *radii, const float *scales, float scale_modifier, const float *rotations,
+                           const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix, const float *campos,
+                           float tanfovx, float tanfovy, const float *dL_ddepth, const float *dL_dalpha,
+                           const void *geom_ws, size_t geom_bytes, const void *binning_ws, size_t binning_bytes,
+                           const void *img_ws, size_t img_bytes, void *ws, size_t ws_bytes, int32_t accumulate,
+                           float *dL_dmeans2D, float *dL_dopacity, float *dL_dmeans3D, float *dL_dcov3D, float *dL_dscales, float *dL_drots) {
+    const char *who = "gsr_depth_backward";
+    hipStream_t s = (hipStream_t)stream;
+    GSR_TRY(sizes_and_mode(who, P, W, H, (long long)R, mode));
+    if (!dL_ddepth && !dL_dalpha) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_ddepth and dL_dalpha are both NULL", who);
+    if (P == 0) return GSR_OK;
+    if (!means3D || !radii || !viewmatrix || !projmatrix || !geom_ws || !img_ws || !ws || !dL_dmeans2D || !dL_dopacity || !dL_dmeans3D)
+        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: missing input, workspace or gradient buffer", who);
+    if (((scales != nullptr) && (rotations != nullptr)) == (cov3D_precomp != nullptr) || ((scales != nullptr) != (rotations != nullptr)))
+        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: exactly one of (scales, rotations) / cov3D_precomp must be given", who);
+    if ((cov3D_precomp && !dL_dcov3D) || (scales && (!dL_dscales || !dL_drots)))
+        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_dcov3D required with cov3D_precomp, dL_dscales and dL_drots with scales and rotations", who);
+    if (R > 0 && !binning_ws) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: binning workspace missing", who);
+    int32_t det = 0;
+    GSR_TRY(gsr_get_option("deterministic_bwd", &det));
+    if (det) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: not available while the option deterministic_bwd is on (this pass sums with float atomics and has no slot form)", who);
+    if (ws_bytes < workspace_bytes(P)) return fail(GSR_ERR_WORKSPACE, "depth workspace %zu < %zu", ws_bytes, workspace_bytes(P));
+    if (acc_rows(P) >= (1u << 28)) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: P too large for the 28-bit accumulator row index", who);
+    float *const d_scales = scales ? dL_dscales : nullptr, *const d_rots = scales ? dL_drots : nullptr;      // the form that was not given is not written
+    if (R == 0) {                                       // nothing was composited: every gradient is zero
+        if (accumulate) return GSR_OK;
+        const size_t n = (size_t)P * sizeof(float);
+        HIP_TRY(hipMemsetAsync(dL_dmeans2D, 0, 3 * n, s), "clear gradients");
+        HIP_TRY(hipMemsetAsync(dL_dopacity, 0, n, s), "clear gradients");
+        HIP_TRY(hipMemsetAsync(dL_dmeans3D, 0, 3 * n, s), "clear gradients");
+        if (dL_dcov3D) HIP_TRY(hipMemsetAsync(dL_dcov3D, 0, 6 * n, s), "clear gradients");
+        if (d_scales) { HIP_TRY(hipMemsetAsync(d_scales, 0, 3 * n, s), "clear gradients"); HIP_TRY(hipMemsetAsync(d_rots, 0, 4 * n, s), "clear gradients"); }
+        return GSR_OK;
+    }
+    Views v;
+    GSR_TRY(carve(v, P, W, H, (long long)R, geom_ws, geom_bytes, binning_ws, binning_bytes, img_ws, img_bytes));
+
+    // 1. clear the rows that can be added into; 2. the reverse walk
+    float *acc = (float *)ws;
+    HIP_TRY(launch_zero_marked_rows(P, v.g.touched, v.g.touch_mark, acc, acc_rows(P), v.im.seg, 0, 0, s), "zero depth accumulators");
+    DepthArgs a = walk_args(v, P, W, H, (long long)R, mode);
+    a.gD = dL_ddepth; a.gA = dL_dalpha; a.acc = acc; a.acc_rows = acc_rows(P);
+    hipLaunchKernelGGL(depth_bwd_kernel, dim3(walk_blocks(a)), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError(), "depth backward launch");
+
+    // 3. the per-Gaussian chain S11-S13 on these rows: pergauss_bwd.hip's streaming kernel, no colour input, into the caller's buffers or
+    //    -- with accumulate -- into the staging area behind the rows
+    float *st = (float *)((char *)ws + acc_bytes(P));
+    const size_t n = (size_t)P;
+    float *const t_rots = st, *const t_m2 = st + 4 * n, *const t_m3 = st + 7 * n, *const t_op = st + 10 * n, *const t_sc = st + 11 * n, *const t_cov = st + 14 * n;
+    PergaussBwdArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.P = P; pa.W = W; pa.H = H; pa.rec = v.g.rec; pa.means3D = means3D; pa.scales = scales; pa.rotations = rotations; pa.cov3D_precomp = cov3D_precomp;
+    pa.opac = v.g.opac; pa.viewmatrix = viewmatrix; pa.projmatrix = projmatrix; pa.campos = campos;
+    pa.scale_modifier = scale_modifier; pa.tanfovx = tanfovx; pa.tanfovy = tanfovy; pa.radii = radii; pa.clamped = v.g.clamped;
+    pa.acc = acc; pa.hot = v.g.hot; pa.touched = v.g.touched; pa.touch_mark = v.g.touch_mark;
+    pa.dL_dmeans2D = accumulate ? t_m2 : dL_dmeans2D; pa.dL_dopacity = accumulate ? t_op : dL_dopacity; pa.dL_dmeans3D = accumulate ? t_m3 : dL_dmeans3D;
+    pa.dL_dcov3D = dL_dcov3D ? (accumulate ? t_cov : dL_dcov3D) : nullptr;
+    pa.dL_dscales = d_scales ? (accumulate ? t_sc : d_scales) : nullptr; pa.dL_drots = d_rots ? (accumulate ? t_rots : d_rots) : nullptr;
+    HIP_TRY(launch_pergauss_bwd(pa, s), "per-Gaussian backward launch");
+
+    // 4. dL/dv -> dL/dmeans3D, and the accumulation
+    FinishArgs f;
+    memset(&f, 0, sizeof f);
+    f.P = P; f.mode = mode; f.accumulate = accumulate ? 1 : 0; f.means3D = means3D; f.viewmatrix = viewmatrix; f.radii = radii;
+    f.touched = v.g.touched; f.clamped = v.g.clamped; f.touch_mark = v.g.touch_mark; f.hot = v.g.hot; f.acc = acc;
+    f.t_means2D = t_m2; f.t_opacity = t_op; f.t_means3D = t_m3; f.t_cov3D = t_cov; f.t_scales = t_sc; f.t_rots = t_rots;
+    f.dL_dmeans2D = dL_dmeans2D; f.dL_dopacity = dL_dopacity; f.dL_dmeans3D = dL_dmeans3D; f.dL_dcov3D = dL_dcov3D; f.dL_dscales = d_scales; f.dL_drots = d_rots;
+    hipLaunchKernelGGL(depth_finish_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, f);
+    HIP_TRY(hipGetLastError(), "depth finish launch");
+    return GSR_OK;
+}
+
+}  // extern "C"

@@ -248,6 +248,66 @@ class HipBackend:
             return g_means3D, g_means2D, g_sh, g_colors, g_opacity, g_scales, g_rots, g_cov3D, g_sh_rest
         return g_means3D, g_means2D, g_sh, g_colors, g_opacity, g_scales, g_rots, g_cov3D
 
+    def depth_forward(self, rs, P, num_rendered, mode, geom, binning, img):
+        """(depth, alpha), [H,W] each, of the render whose gsr_forward filled the three workspaces (include/gsr_depth.h)."""
+        dev = geom.device
+        H, W = int(rs.image_height), int(rs.image_width)
+        depth = torch.empty((H, W), dtype=torch.float32, device=dev)
+        alpha = torch.empty((H, W), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = self.lib.gsr_depth_forward(torch.cuda.current_stream(dev).cuda_stream, P, W, H, int(num_rendered), int(mode),
+                                            _ptr(geom), geom.numel(), _ptr(binning), binning.numel(), _ptr(img), img.numel(),
+                                            depth.data_ptr(), alpha.data_ptr())
+            _lib.check(rc, "gsr_depth_forward")
+        return depth, alpha
+
+    def arena_fill_in_flight(self, geom):
+        """True when the render that owns `geom` announced gradient tensors that are slices of a gradient arena: the library may be
+        zero-filling them on its second stream, and only gsr_backward joins that fill.  A map gradient alone must then not write
+        into the arena by itself: _RasterizeGaussiansDepth runs the colour pass (zero gradient) first and adds to its tensors."""
+        ann = self._announced.get(geom.device.index)
+        return ann is not None and ann[0] == geom.data_ptr() and ann[4] is not None
+
+    def depth_backward(self, rs, num_rendered, mode, dL_ddepth, dL_dalpha, means3D, radii, scales, rotations, cov3D_precomp,
+                       geom, binning, img, into=None, sh_floats=0):
+        """Gradients of the depth and alpha maps (include/gsr_depth.h).  into = None: new tensors (slices of the gradient arena when one
+        is set; the arena's SH slice, sh_floats = 3 M per Gaussian, is then zeroed: the maps have no SH gradient), accumulate = 0.
+        into = (g_means3D, g_means2D, g_opacity, g_scales, g_rots, g_cov3D) as HipBackend.backward of the same render just wrote
+        them: added to, accumulate = 1.  Returns that tuple."""
+        dev = means3D.device
+        P, H, W = int(means3D.shape[0]), int(rs.image_height), int(rs.image_width)
+        has_sr, has_cov = scales.numel() > 0, cov3D_precomp.numel() > 0
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if into is None:
+                M = sh_floats // 3
+                arena = _grad_arena
+                if arena is not None and (arena.device != dev or arena.dtype != torch.float32 or not arena.is_contiguous()
+                                          or arena.numel() < arena_floats(P, M, has_sr)):
+                    raise _lib.GsrError("gradient arena must be a contiguous float32 tensor on the render device with "
+                                        f"at least {arena_floats(P, M, has_sr)} elements")
+                self._release_arena(geom)
+                g_means3D, g_means2D, g_sh, _c, g_opacity, g_scales, g_rots, g_cov3D, _r = self._gradient_outputs(
+                    dev, P, M if arena is not None else 0, 0, has_sr, False, has_cov, arena)
+                if arena is not None and g_sh.numel():
+                    g_sh.zero_()
+            else:
+                g_means3D, g_means2D, g_opacity, g_scales, g_rots, g_cov3D = into
+            wsb = C.c_size_t()
+            _lib.check(self.lib.gsr_depth_workspace_bytes(P, C.byref(wsb)), "gsr_depth_workspace_bytes")
+            ws = torch.empty((wsb.value,), dtype=torch.uint8, device=dev)
+            vm = _f32c(rs.viewmatrix, "viewmatrix", dev); pm = _f32c(rs.projmatrix, "projmatrix", dev); cp = _f32c(rs.campos, "campos", dev)
+            gD = None if dL_ddepth is None else _f32c(dL_ddepth, "grad of the depth map", dev)
+            gA = None if dL_dalpha is None else _f32c(dL_dalpha, "grad of the alpha map", dev)
+            rc = self.lib.gsr_depth_backward(
+                stream, P, W, H, int(num_rendered), int(mode), _ptr(means3D), _ptr(radii), _ptr(scales), float(rs.scale_modifier),
+                _ptr(rotations), _ptr(cov3D_precomp), _ptr(vm), _ptr(pm), _ptr(cp), float(rs.tanfovx), float(rs.tanfovy),
+                _ptr(gD), _ptr(gA), _ptr(geom), geom.numel(), _ptr(binning), binning.numel(), _ptr(img), img.numel(),
+                _ptr(ws), ws.numel(), 0 if into is None else 1,
+                _ptr(g_means2D), _ptr(g_opacity), _ptr(g_means3D), _ptr(g_cov3D), _ptr(g_scales), _ptr(g_rots))
+            _lib.check(rc, "gsr_depth_backward")
+        return g_means3D, g_means2D, g_opacity, g_scales, g_rots, g_cov3D
+
     def composited_mask(self, geom, P):
         """bool [P]: the Gaussians the forward pass that filled `geom` composited at all (include/gsr.h gsr_composited_mask): a
         superset of those that can receive a gradient, usually far smaller than radii > 0."""
@@ -418,6 +478,66 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                                      cov3Ds_precomp, raster_settings)
 
 
+DEPTH_MODES = {"expected": _lib.DEPTH_EXPECTED, "inverse": _lib.DEPTH_INVERSE}
+
+
+class _RasterizeGaussiansDepth(torch.autograd.Function):
+    """(color, radii, depth, alpha): _RasterizeGaussians' render followed by the depth and alpha maps of the same lists
+    (include/gsr_depth.h).  The forward call is the plain one -- announcement, arena, binning hint as there -- then one walk over what
+    it left.  Backward runs what the losses used: the colour pass, the map pass, or the colour pass and then the map pass adding into
+    its tensors."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, mode):
+        be = get_backend()
+        if not hasattr(be, "depth_forward"):
+            raise _lib.GsrError(f"the {getattr(be, 'name', type(be).__name__)} backend renders no depth or alpha map")
+        dev = means3D.device
+        if means3D.dim() != 2 or means3D.shape[1] != 3:
+            raise _lib.GsrError("means3D must have dimensions (num_points, 3)")
+        args = [_f32c(t, n, dev) for t, n in ((means3D, "means3D"), (sh, "shs"), (colors_precomp, "colors_precomp"),
+                                              (opacities, "opacities"), (scales, "scales"), (rotations, "rotations"),
+                                              (cov3Ds_precomp, "cov3D_precomp"))]
+        means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c = args
+        num_rendered, color, radii, geom, binning, img = be.forward(
+            raster_settings, means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c,
+            **({"announce_backward": True} if any(ctx.needs_input_grad) and hasattr(be, "_announced") else {}))
+        depth, alpha = be.depth_forward(raster_settings, int(means3D_c.shape[0]), num_rendered, mode, geom, binning, img)
+        ctx.raster_settings, ctx.num_rendered, ctx.depth_mode = raster_settings, num_rendered, mode
+        _remember_forward(geom, int(means3D_c.shape[0]))
+        ctx.save_for_backward(colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img)
+        ctx.gsr_geom_index, ctx.gsr_means_index = 7, 1
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth.unsqueeze(0), alpha.unsqueeze(0)
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha):
+        be = get_backend()
+        rs = ctx.raster_settings
+        colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img = ctx.saved_tensors
+        maps = grad_depth is not None or grad_alpha is not None
+        if grad_color is None and not maps:
+            return (None,) * 10
+        g_sh = g_colors = None
+        colour_used = grad_color is not None
+        if not colour_used and hasattr(be, "arena_fill_in_flight") and be.arena_fill_in_flight(geom):
+            grad_color = torch.zeros((3, int(rs.image_height), int(rs.image_width)), dtype=torch.float32, device=means3D_c.device)
+        if grad_color is not None:
+            g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov = be.backward(
+                rs, ctx.num_rendered, grad_color, means3D_c, radii, sh_c, colors_c, scales_c, rots_c, cov_c, geom, binning, img)
+        if maps:
+            into = None if grad_color is None else (g_means3D, g_means2D, g_opac, g_scales, g_rots, g_cov)
+            g_means3D, g_means2D, g_opac, g_scales, g_rots, g_cov = be.depth_backward(
+                rs, ctx.num_rendered, ctx.depth_mode, grad_depth, grad_alpha, means3D_c, radii, scales_c, rots_c, cov_c,
+                geom, binning, img, into=into, sh_floats=3 * int(sh_c.shape[1]) if sh_c.numel() else 0)
+        none_if_empty = lambda g, src: g if (g is not None and src.numel() > 0) else None
+        if not colour_used:
+            g_sh = g_colors = None          # the maps give the colour inputs no gradient
+        return (g_means3D, g_means2D, none_if_empty(g_sh, sh_c), none_if_empty(g_colors, colors_c), g_opac,
+                none_if_empty(g_scales, scales_c), none_if_empty(g_rots, rots_c), none_if_empty(g_cov, cov_c), None, None)
+
+
 class _RasterizeGaussiansFused(torch.autograd.Function):
     """Fused-step variant: takes the RAW parameters of scene/gaussian_model.py (xyz, features_dc,
     features_rest, opacity logits, log-scales, un-normalised quaternions); the activations (:33-41) and the
@@ -481,8 +601,13 @@ class GaussianRasterizer(nn.Module):
             return get_backend().mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, depth=None):
+        """depth = None: (color, radii), the reference's call.  depth = "expected" or "inverse": (color, radii, depth, alpha) with
+        depth [1,H,W] = sum z alpha T (or sum (1/z) alpha T), not normalised, no background term, and alpha [1,H,W] = 1 - T_final;
+        gradients flow from all three images."""
         rs = self.raster_settings
+        if depth is not None and depth not in DEPTH_MODES:
+            raise _lib.GsrError(f"depth must be None, 'expected' or 'inverse', got {depth!r}")
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -494,4 +619,7 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
+        if depth is not None:
+            return _RasterizeGaussiansDepth.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs,
+                                                  DEPTH_MODES[depth])
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs)

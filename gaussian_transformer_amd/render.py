@@ -45,9 +45,11 @@ def eval_sh_torch(deg: int, sh: torch.Tensor, dirs: torch.Tensor) -> torch.Tenso
     return result
 
 
-def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0, override_color=None):
+def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0, override_color=None, depth=None):
     """viewpoint_camera: anything with image_height/width, FoVx/FoVy, world_view_transform,
-    full_proj_transform, camera_center (torch tensors on the device).  pc: GaussianParams-like."""
+    full_proj_transform, camera_center (torch tensors on the device).  pc: GaussianParams-like.
+    depth: None (the reference's dict), or "expected" / "inverse": the dict also holds "depth" and "alpha", [1,H,W] each
+    (GaussianRasterizer.forward)."""
     xyz = pc.get_xyz
     screenspace_points = torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True, device=xyz.device) + 0
     try:
@@ -79,6 +81,12 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
             shs = pc.get_features
     else:
         colors_precomp = override_color
+    if depth is not None:
+        rendered_image, radii, depth_map, alpha_map = rasterizer(
+            means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity, scales=scales,
+            rotations=rotations, cov3D_precomp=cov3D_precomp, depth=depth)
+        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
+                "depth": depth_map, "alpha": alpha_map}
     rendered_image, radii = rasterizer(means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp,
                                        opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
     return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
