@@ -784,8 +784,9 @@ def test_dense_per_gaussian_stage_matches_the_streaming_one(kw):
     """`dense_pergauss`: on the library's second stream, beside the compositing kernel, a fill kernel writes the zeros of every gradient
     output and a gather kernel lists the Gaussians with a gradient and copies their inputs into a compact buffer; pergauss_bwd then
     runs on full waves of those.  With the deterministic reverse pass (no atomics: identical accumulator rows) every gradient tensor
-    must equal the streaming kernel's bit for bit -- and a buffer that held garbage before the call must hold exact zeros wherever
-    no gradient exists."""
+    must equal the streaming kernel's bit for bit.  (That a buffer which held garbage before the call holds exact zeros wherever no
+    gradient exists is not visible here -- both runs get their outputs from torch.empty, usually the other run's blocks --
+    and is checked on NaN-filled outputs between guard zones by tests/test_gpu_grad_outputs.py.)"""
     from gaussian_transformer_amd import _lib
     sc = synth.make_scene(**kw)
     S = oracle_scene(sc)
