@@ -46,7 +46,8 @@ SOURCES = {
     "sequence.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],   # as preprocess.hip: gsr_visible_union's radii must round as gsr_forward's
     "density.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],    # record's norm and the split children round as written (include/gsr_density.h)
     "rows.hip": [],                # copies and float adds only (include/gsr_rows.h): nothing to contract
-    # as composite_bwd.hip, whose walk it restates for the depth and alpha maps (include/gsr_depth.h): native float atomic add, no packed f32 pairs
+    # as composite_bwd.hip, whose staging, replica rows and LDS reduction it shares (csrc/composite_common.h) under recurrences of its own
+    # for the depth and alpha maps (include/gsr_depth.h): native float atomic add, no packed f32 pairs
     "depth_maps.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result", "-fno-gpu-rdc"]

@@ -19,42 +19,16 @@
 // instruction (9 lanes) into the splat's 64-byte accumulator row: one memory-side request per (wave, splat).
 #include <atomic>
 
-#include "gsr_device.h"
+#include "composite_common.h"
 #include "gsr_internal.h"
 
 namespace gsr {
 extern int g_composite_lds_pad;
 
-#define LOG2E 1.4426950408889634f
-#define RED_STRIDE 68
 // LDS per wave: 64 staged records of 40 bytes, kept as three arrays (float4 | float4 | float2) so that every read stays aligned,
 // + the reduction scratch, 9 rows of RED_STRIDE floats (153 float4): 5 008 B -- 32 waves fit a CU's 160 KB, 8 per SIMD (the
 // kernel needs 53 VGPRs and is latency-sensitive: 48-byte records, 29 waves/CU, cost 4 %; 22 waves/CU cost another 9 %)
 #define BWD_LDS_F4 (64 * 2 + 32 + (9 * RED_STRIDE + 3) / 4)
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    const int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true);
-    return v + __int_as_float(moved);
-}
-// sum over the 16 lanes of each DPP row, result in every lane of the row
-__device__ __forceinline__ float row_allreduce(float v) {
-    v = dpp_add<0xB1>(v);   // quad_perm [1,0,3,2]
-    v = dpp_add<0x4E>(v);   // quad_perm [2,3,0,1]
-    v = dpp_add<0x141>(v);  // row_half_mirror
-    v = dpp_add<0x140>(v);  // row_mirror
-    return v;
-}
-// lanes 0-31: a[l] + a[l+32];  lanes 32-63: b[l-32] + b[l]
-__device__ __forceinline__ float fold32(float a, float b) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-// row0: a.r0 + a.r1;  row1: b.r0 + b.r1;  row2: a.r2 + a.r3;  row3: b.r2 + b.r3
-__device__ __forceinline__ float fold16(float a, float b) {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 
 // COUNT: instrumented instantiations (gsr_set_option("count_lanes", 1 or 2)): 1 tallies staged records, splat visits, 8x8 block
 // visits (= 64 lane slots each), blending lanes and the reason idle lanes were idle into a.counters (CompositeCounters); 2 only
@@ -64,9 +38,6 @@ __device__ __forceinline__ float fold16(float a, float b) {
 // det_reduce_kernel below adds each Gaussian's slots in a fixed order.  The in-wave reduction is order-fixed already.
 struct BwdTally { unsigned long long staged = 0, visits = 0, blocks = 0, ok = 0, past = 0, alpha = 0, red = 0, dead = 0; };
 
-// One work unit: the entries [lo, hi) of the list of `tile`, against the NPX blocks `sub` names.  hi < 0: up to the last contributor
-// of these pixels (the whole half tile, the classic decomposition).  ckslot != ~0: pixels that blended anything at or behind entry
-// hi start from the forward pass's checkpoint at that boundary instead of from the end of their list (SegView, gsr_internal.h).
 // ---- the reverse walk of one staged batch, 2 blocks per wave, written out (round 3; see composite_fwd.hip::walk_batch_2blocks) ----
 // The decisions (power, alpha, the tests on them) are formed exactly as in the C++ walk below and in the forward pass; the sums are
 // not bit-identical to the C++ walk's (packed multiply-adds for the moments, a differently associated 16-float tree), within the
@@ -79,6 +50,54 @@ struct BwdTally { unsigned long long staged = 0, visits = 0, blocks = 0, ok = 0,
 // v36..v63 are used by name: record v36-45 (px py a b | c opacity r g | blue, bits|row<<4); sums v46-48 (colour), v[50:51] (s dx,
 // s dy), v[52:53] (s dx dx, s dx dy), v49 (s dy dy), v54 (s); u w v56-57, (dx, dy) v[58:59], temporaries v55, v60-63; the reduction
 // reads its 16 floats into v36-43 and v56-63.
+// One block's part of a visit, as text.  HEAD: dx, the exponent and the decisions (power, alpha, in front of the pixel's last contributor:
+// vcc = the lanes that blend), alpha capped into v62 and 1 / (1 - alpha) into v63, the recurrences on T and accd, dL/dalpha into v55, and
+// v62 = alpha T in front of the splat; v60 = the pre-cap alpha of the blending lanes, 0 elsewhere.  Operands by name: the block's fx, last,
+// d0..d2, accd (A), T and tb.  WRITE: the first block of a visit sets the nine sums (and `any`); ADD: the second one adds to them.
+#define BWD_WALK_HEAD(fx, l, d0, d1, d2, A, T, tb) \
+        "v_sub_f32 v58, v36, %[" #fx "]\n" \
+        "v_fma_f32 v55, v38, v58, v56\n" \
+        "v_fma_f32 v55, v55, v58, v57\n" \
+        "v_exp_f32 v60, v55\n" \
+        "v_cmp_nlt_f32_e64 %[m1], 0, v55\n" \
+        "v_cmp_lt_i32 vcc, %[pos], %[" #l "]\n" \
+        "v_mul_f32 v61, %[" #d1 "], v43\n" \
+        "v_mul_f32 v60, v41, v60\n" \
+        "v_cmp_ngt_f32_e64 %[m3], %[amin], v60\n" \
+        "s_and_b64 %[m3], %[m3], %[m1]\n" \
+        "s_and_b64 vcc, %[m3], vcc\n" \
+        "v_cndmask_b32 v60, 0, v60, vcc\n" \
+        "v_min_f32 v62, 0x3f7d70a4, v60\n" \
+        "v_sub_f32 v63, 1.0, v62\n" \
+        "v_rcp_f32 v63, v63\n" \
+        "v_fmac_f32 v61, %[" #d0 "], v42\n" \
+        "v_fmac_f32 v61, %[" #d2 "], v44\n" \
+        "v_sub_f32 v61, v61, %[" #A "]\n" \
+        "v_fma_f32 v55, %[" #T "], v61, -%[" #tb "]\n" \
+        "v_mul_f32 %[" #T "], %[" #T "], v63\n" \
+        "v_mul_f32 v55, v55, v63\n" \
+        "v_fmac_f32 %[" #A "], v61, v62\n" \
+        "v_mul_f32 v62, v62, %[" #T "]\n"
+#define BWD_WALK_WRITE(d0, d1, d2) \
+        "s_mov_b64 %[any], vcc\n" \
+        "v_mul_f32 v46, %[" #d0 "], v62\n" \
+        "v_mul_f32 v47, %[" #d1 "], v62\n" \
+        "v_mul_f32 v48, %[" #d2 "], v62\n" \
+        "v_mul_f32 v54, v60, v55\n" \
+        "v_pk_mul_f32 v[50:51], v[54:55], v[58:59] op_sel_hi:[0,1]\n" \
+        "v_pk_mul_f32 v[52:53], v[50:51], v[58:59] op_sel_hi:[0,1]\n" \
+        "v_mul_f32 v49, v59, v51\n"
+#define BWD_WALK_ADD(d0, d1, d2) \
+        "s_or_b64 %[any], %[any], vcc\n" \
+        "v_fmac_f32 v46, %[" #d0 "], v62\n" \
+        "v_fmac_f32 v47, %[" #d1 "], v62\n" \
+        "v_fmac_f32 v48, %[" #d2 "], v62\n" \
+        "v_fmac_f32 v54, v60, v55\n" \
+        "v_mul_f32 v60, v60, v55\n" \
+        "v_pk_mul_f32 v[62:63], v[60:61], v[58:59] op_sel_hi:[0,1]\n" \
+        "v_pk_fma_f32 v[50:51], v[60:61], v[58:59], v[50:51] op_sel_hi:[0,1,1]\n" \
+        "v_pk_fma_f32 v[52:53], v[62:63], v[58:59], v[52:53] op_sel_hi:[0,1,1]\n" \
+        "v_fmac_f32 v49, v59, v63\n"
 struct BwdPx { float T, accd, fx, d0, d1, d2, tb; int last; };
 __device__ __forceinline__ void walk_batch_bwd_2blocks(uint32_t lds, uint32_t redw, uint32_t redr, uint32_t lane, int base, float fy,
                                                        unsigned long long m, unsigned long long b0m, unsigned long long b1m,
@@ -108,105 +127,16 @@ __device__ __forceinline__ void walk_batch_bwd_2blocks(uint32_t lds, uint32_t re
         "s_waitcnt lgkmcnt(0)\n"
         "s_bitcmp1_b64 %[b0m], %[j]\n"
         "s_cbranch_scc0 3f\n"
-        "v_sub_f32 v58, v36, %[fx0]\n"
-        "v_fma_f32 v55, v38, v58, v56\n"
-        "v_fma_f32 v55, v55, v58, v57\n"
-        "v_exp_f32 v60, v55\n"
-        "v_cmp_nlt_f32_e64 %[m1], 0, v55\n"
-        "v_cmp_lt_i32 vcc, %[pos], %[l0]\n"
-        "v_mul_f32 v61, %[d01], v43\n"
-        "v_mul_f32 v60, v41, v60\n"
-        "v_cmp_ngt_f32_e64 %[m3], %[amin], v60\n"
-        "s_and_b64 %[m3], %[m3], %[m1]\n"
-        "s_and_b64 vcc, %[m3], vcc\n"
-        "v_cndmask_b32 v60, 0, v60, vcc\n"
-        "v_min_f32 v62, 0x3f7d70a4, v60\n"
-        "v_sub_f32 v63, 1.0, v62\n"
-        "v_rcp_f32 v63, v63\n"
-        "v_fmac_f32 v61, %[d00], v42\n"
-        "v_fmac_f32 v61, %[d02], v44\n"
-        "v_sub_f32 v61, v61, %[A0]\n"
-        "v_fma_f32 v55, %[T0], v61, -%[tb0]\n"
-        "v_mul_f32 %[T0], %[T0], v63\n"
-        "v_mul_f32 v55, v55, v63\n"
-        "v_fmac_f32 %[A0], v61, v62\n"
-        "v_mul_f32 v62, v62, %[T0]\n"
-        "s_mov_b64 %[any], vcc\n"
-        "v_mul_f32 v46, %[d00], v62\n"
-        "v_mul_f32 v47, %[d01], v62\n"
-        "v_mul_f32 v48, %[d02], v62\n"
-        "v_mul_f32 v54, v60, v55\n"
-        "v_pk_mul_f32 v[50:51], v[54:55], v[58:59] op_sel_hi:[0,1]\n"
-        "v_pk_mul_f32 v[52:53], v[50:51], v[58:59] op_sel_hi:[0,1]\n"
-        "v_mul_f32 v49, v59, v51\n"
+        BWD_WALK_HEAD(fx0, l0, d00, d01, d02, A0, T0, tb0)
+        BWD_WALK_WRITE(d00, d01, d02)
         "s_bitcmp1_b64 %[b1m], %[j]\n"
         "s_cbranch_scc0 4f\n"
-        "v_sub_f32 v58, v36, %[fx1]\n"
-        "v_fma_f32 v55, v38, v58, v56\n"
-        "v_fma_f32 v55, v55, v58, v57\n"
-        "v_exp_f32 v60, v55\n"
-        "v_cmp_nlt_f32_e64 %[m1], 0, v55\n"
-        "v_cmp_lt_i32 vcc, %[pos], %[l1]\n"
-        "v_mul_f32 v61, %[d11], v43\n"
-        "v_mul_f32 v60, v41, v60\n"
-        "v_cmp_ngt_f32_e64 %[m3], %[amin], v60\n"
-        "s_and_b64 %[m3], %[m3], %[m1]\n"
-        "s_and_b64 vcc, %[m3], vcc\n"
-        "v_cndmask_b32 v60, 0, v60, vcc\n"
-        "v_min_f32 v62, 0x3f7d70a4, v60\n"
-        "v_sub_f32 v63, 1.0, v62\n"
-        "v_rcp_f32 v63, v63\n"
-        "v_fmac_f32 v61, %[d10], v42\n"
-        "v_fmac_f32 v61, %[d12], v44\n"
-        "v_sub_f32 v61, v61, %[A1]\n"
-        "v_fma_f32 v55, %[T1], v61, -%[tb1]\n"
-        "v_mul_f32 %[T1], %[T1], v63\n"
-        "v_mul_f32 v55, v55, v63\n"
-        "v_fmac_f32 %[A1], v61, v62\n"
-        "v_mul_f32 v62, v62, %[T1]\n"
-        "s_or_b64 %[any], %[any], vcc\n"
-        "v_fmac_f32 v46, %[d10], v62\n"
-        "v_fmac_f32 v47, %[d11], v62\n"
-        "v_fmac_f32 v48, %[d12], v62\n"
-        "v_fmac_f32 v54, v60, v55\n"
-        "v_mul_f32 v60, v60, v55\n"
-        "v_pk_mul_f32 v[62:63], v[60:61], v[58:59] op_sel_hi:[0,1]\n"
-        "v_pk_fma_f32 v[50:51], v[60:61], v[58:59], v[50:51] op_sel_hi:[0,1,1]\n"
-        "v_pk_fma_f32 v[52:53], v[62:63], v[58:59], v[52:53] op_sel_hi:[0,1,1]\n"
-        "v_fmac_f32 v49, v59, v63\n"
+        BWD_WALK_HEAD(fx1, l1, d10, d11, d12, A1, T1, tb1)
+        BWD_WALK_ADD(d10, d11, d12)
         "s_branch 4f\n"
         "3:\n"                                        // block 0 takes no part: block 1 does (the entry is in one of the masks)
-        "v_sub_f32 v58, v36, %[fx1]\n"
-        "v_fma_f32 v55, v38, v58, v56\n"
-        "v_fma_f32 v55, v55, v58, v57\n"
-        "v_exp_f32 v60, v55\n"
-        "v_cmp_nlt_f32_e64 %[m1], 0, v55\n"
-        "v_cmp_lt_i32 vcc, %[pos], %[l1]\n"
-        "v_mul_f32 v61, %[d11], v43\n"
-        "v_mul_f32 v60, v41, v60\n"
-        "v_cmp_ngt_f32_e64 %[m3], %[amin], v60\n"
-        "s_and_b64 %[m3], %[m3], %[m1]\n"
-        "s_and_b64 vcc, %[m3], vcc\n"
-        "v_cndmask_b32 v60, 0, v60, vcc\n"
-        "v_min_f32 v62, 0x3f7d70a4, v60\n"
-        "v_sub_f32 v63, 1.0, v62\n"
-        "v_rcp_f32 v63, v63\n"
-        "v_fmac_f32 v61, %[d10], v42\n"
-        "v_fmac_f32 v61, %[d12], v44\n"
-        "v_sub_f32 v61, v61, %[A1]\n"
-        "v_fma_f32 v55, %[T1], v61, -%[tb1]\n"
-        "v_mul_f32 %[T1], %[T1], v63\n"
-        "v_mul_f32 v55, v55, v63\n"
-        "v_fmac_f32 %[A1], v61, v62\n"
-        "v_mul_f32 v62, v62, %[T1]\n"
-        "s_mov_b64 %[any], vcc\n"
-        "v_mul_f32 v46, %[d10], v62\n"
-        "v_mul_f32 v47, %[d11], v62\n"
-        "v_mul_f32 v48, %[d12], v62\n"
-        "v_mul_f32 v54, v60, v55\n"
-        "v_pk_mul_f32 v[50:51], v[54:55], v[58:59] op_sel_hi:[0,1]\n"
-        "v_pk_mul_f32 v[52:53], v[50:51], v[58:59] op_sel_hi:[0,1]\n"
-        "v_mul_f32 v49, v59, v51\n"
+        BWD_WALK_HEAD(fx1, l1, d10, d11, d12, A1, T1, tb1)
+        BWD_WALK_WRITE(d10, d11, d12)
         "4:\n"
         "s_cmp_eq_u64 %[any], 0\n"
         "s_cbranch_scc1 5f\n"                         // no pixel of this wave blends the splat
@@ -263,7 +193,13 @@ __device__ __forceinline__ void walk_batch_bwd_2blocks(uint32_t lds, uint32_t re
         : "memory", "scc", "vcc", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49",
           "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63");
 }
+#undef BWD_WALK_HEAD
+#undef BWD_WALK_WRITE
+#undef BWD_WALK_ADD
 
+// One work unit: the entries [lo, hi) of the list of `tile`, against the NPX blocks `sub` names.  hi < 0: up to the last contributor
+// of these pixels (the whole half tile, the classic decomposition).  ckslot != ~0: pixels that blended anything at or behind entry
+// hi start from the forward pass's checkpoint at that boundary instead of from the end of their list (SegView, gsr_internal.h).
 template <int NPX, int COUNT, bool DET, bool ASMW = false>
 __device__ __forceinline__ void bwd_unit(const CompositeBwdArgs &a, float4 *my, const int lane, const int tile, const int sub, const int lo,
                                          int hi, const uint32_t ckslot, BwdTally &tl) {
@@ -271,7 +207,6 @@ __device__ __forceinline__ void bwd_unit(const CompositeBwdArgs &a, float4 *my, 
     const int tx = tile % a.gridx, ty = tile / a.gridx;
     float2 *myc = reinterpret_cast<float2 *>(my + 128);     // third array of the staged records
     float *red = reinterpret_cast<float *>(my + 128 + 32);  // [value 0..8][lane 0..63]
-    const float4 *rec4 = reinterpret_cast<const float4 *>(a.rec);
     const uint2 range = a.ranges[tile];
     const size_t HW = (size_t)a.W * a.H;
     const float bg0 = a.bg[0], bg1 = a.bg[1], bg2 = a.bg[2];
@@ -284,12 +219,10 @@ __device__ __forceinline__ void bwd_unit(const CompositeBwdArgs &a, float4 *my, 
     int max_last = 0;
 #pragma unroll
     for (int q = 0; q < NPX; q++) {
-        const int blk = NPX == 4 ? q : (NPX == 2 ? sub * 2 + q : sub);      // 0..3: (bx = blk&1, by = blk>>1)
-        const int x0 = tx * GSR_TILE + (blk & 1) * 8, y0 = ty * GSR_TILE + (blk >> 1) * 8;
-        const int x = x0 + (lane & 7), y = y0 + (lane >> 3);
-        const bool inside = x < a.W && y < a.H;
-        const size_t pix = (size_t)(inside ? y : 0) * a.W + (inside ? x : 0);
-        fx[q] = (float)x; fy[q] = (float)y;
+        const BlockGeom bg = block_geom(tx, ty, block_index<NPX>(sub, q), lane, a.W, a.H);
+        const bool inside = bg.inside;
+        const size_t pix = bg.pix;
+        fx[q] = (float)bg.x; fy[q] = (float)bg.y;
         const float Tf = inside ? a.final_T[pix] : 1.f;
         last[q] = inside ? (int)a.n_contrib[pix] : 0;
         d0[q] = inside ? a.dL_dpix[pix] : 0.f;
@@ -303,8 +236,7 @@ __device__ __forceinline__ void bwd_unit(const CompositeBwdArgs &a, float4 *my, 
 #pragma unroll
     for (int q = 0; q < NPX; q++) {
         int m = last[q];
-#pragma unroll
-        for (int sft = 32; sft > 0; sft >>= 1) m = max(m, __shfl_xor(m, sft));
+        GSR_WAVE_MAX_I32(m);
         blk_last[q] = __builtin_amdgcn_readfirstlane(m);
         max_last = max(max_last, blk_last[q]);
     }
@@ -322,15 +254,11 @@ __device__ __forceinline__ void bwd_unit(const CompositeBwdArgs &a, float4 *my, 
         }
     }
 
-    // Cross-lane reduction through LDS (the LDS pipe is idle otherwise, the VALU is the bottleneck):
-    // every lane stores its 9 partial sums as red[value][lane]; lane 4*value + part then adds the 16
-    // floats red[value][16*part .. 16*part+15] (4 x ds_read_b128), two DPP steps fold the 4 parts, and
-    // lanes 0,4,...,32 hold the nine totals: ONE 9-lane global_atomic_add_f32 per (wave, splat).
-    const int rvalue = lane >> 2, rpart = lane & 3;
-    // rows of RED_STRIDE = 68 floats: with 64 the nine rows start in the same LDS bank and the 36 reading lanes collide 9-way
-    const float4 *red_rd = reinterpret_cast<const float4 *>(red + (rvalue < 9 ? rvalue : 0) * RED_STRIDE + rpart * 16);
-    const bool red_lane = rvalue < 9;
-    const int slot = (red_lane && rpart == 0) ? rvalue : -1;
+    // the nine partial sums are reduced across the lanes through LDS (reduce_rows, composite_common.h); lanes 0, 4, .., 32 end up
+    // holding total `slot`
+    const float4 *red_rd;
+    bool red_lane;
+    const int slot = reduce_setup<9>(red, lane, red_rd, red_lane);
 
     for (int base = ((hi - 1) >> 6) << 6; base >= lo; base -= 64) {
         const int cnt = min(64, hi - base);
@@ -339,22 +267,21 @@ __device__ __forceinline__ void bwd_unit(const CompositeBwdArgs &a, float4 *my, 
         uint32_t mybits = 0u;                         // blocks of this wave the lane's entry can reach
         if (lane < cnt && GSR_IDX_OK((size_t)range.x + base + lane, a.contrib_stride, a.seg.hdr + GSR_DBG_SEG_WORD, GSR_BOUND_BWD_LIST_READ)) {
             const uint32_t g = a.point_list[range.x + base + lane];
-            const float4 r0 = rec4[3 * (size_t)g], r1 = rec4[3 * (size_t)g + 1], r2 = rec4[3 * (size_t)g + 2];
+            float4 r0, r1, r2;
+            gather_record(a.rec, g, r0, r1, r2);
             // blocks this entry can reach (exact ellipse-vs-block test, gsr_device.h), as the forward pass staged them
             uint32_t bits = 0u;
 #pragma unroll
             for (int q = 0; q < NPX; q++) {
-                const int blk = NPX == 4 ? q : (NPX == 2 ? sub * 2 + q : sub);
-                bits |= a.contrib[(size_t)blk * a.contrib_stride + range.x + base + lane] ? (1u << q) : 0u;
+                bits |= a.contrib[(size_t)block_index<NPX>(sub, q) * a.contrib_stride + range.x + base + lane] ? (1u << q) : 0u;
             }
             live = bits != 0u;
             mybits = bits;
-            const StagedConic sc = stage_conic(r0.z, r0.w, r1.x);       // as the forward pass staged it
-            my[lane] = make_float4(r0.x, r0.y, sc.a, sc.b);
-            my[64 + lane] = make_float4(sc.c, r1.y, r1.z, r1.w);
-            // accumulator row: the Gaussian's own, or -- for a splat with replica rows (gsr_internal.h) -- replica (tile mod K)
-            const uint32_t hot = __float_as_uint(r2.w);
-            const uint32_t row = hot ? (uint32_t)a.P + (hot >> 4) + ((uint32_t)tile & ((1u << (hot & 15u)) - 1u)) : g;
+            float4 s0, s1;
+            stage_record(r0, r1, s0, s1);                               // as the forward pass staged it
+            my[lane] = s0;
+            my[64 + lane] = s1;
+            const uint32_t row = replica_row(__float_as_uint(r2.w), g, a.P, tile);      // where this unit's sums for the Gaussian are added
             myc[lane] = make_float2(r2.x, __uint_as_float(bits | (row << 4)));      // row < 2^28 (checked by gsr_backward)
         }
         uint64_t todo = __ballot(live);
@@ -401,15 +328,9 @@ __device__ __forceinline__ void bwd_unit(const CompositeBwdArgs &a, float4 *my, 
                     tl.blocks += 1; tl.ok += __builtin_popcountll(okm); tl.past += __builtin_popcountll(mp);
                     tl.alpha += __builtin_popcountll(~okm & ~mp); tl.dead += okm == 0ull;
                 }
-#ifdef GSR_BWD_EXEC_MASK
-                const float alpha = fminf(GSR_ALPHA_MAX, araw);
-                if (__builtin_amdgcn_inverse_ballot_w64(okm)) {      // the other lanes are switched off (EXEC), not multiplied by zero
-                    const float araw_ok = araw;
-#else
                 {   // lanes that do not blend carry alpha = 0 through the same arithmetic: every sum below gets an exact 0
                     const float araw_ok = __builtin_amdgcn_inverse_ballot_w64(okm) ? araw : 0.f;   // exp2 of a skipped lane may be inf
                     const float alpha = fminf(GSR_ALPHA_MAX, araw_ok);
-#endif
                     const float inv = __builtin_amdgcn_rcpf(1.f - alpha);
                     const float Tk = Tr[q] * inv;                    // transmittance in front of this splat
                     // <colour - colour behind, dL/dpixel>: the colour behind is only ever needed through this inner
@@ -436,19 +357,8 @@ __device__ __forceinline__ void bwd_unit(const CompositeBwdArgs &a, float4 *my, 
                 if (todo_bits & (1u << q)) block_body(q);    // scalar branch per block (a fused all-blocks body: 7 % slower)
             if (any_ok == 0ull) return;                // wave-uniform: no pixel of this wave blends the splat
             if (COUNT == 1) tl.red += 1;
-            red[0 * RED_STRIDE + lane] = v0; red[1 * RED_STRIDE + lane] = v1; red[2 * RED_STRIDE + lane] = v2;
-            red[3 * RED_STRIDE + lane] = v3; red[4 * RED_STRIDE + lane] = v4; red[5 * RED_STRIDE + lane] = v5;
-            red[6 * RED_STRIDE + lane] = v6; red[7 * RED_STRIDE + lane] = v7; red[8 * RED_STRIDE + lane] = v8;
-            __builtin_amdgcn_wave_barrier();
-            float sel = 0.f;
-            if (red_lane) {
-                const float4 p0 = red_rd[0], p1 = red_rd[1], p2 = red_rd[2], p3 = red_rd[3];       // (v_pk_add_f32 pairs here: 2 % slower)
-                sel = ((p0.x + p0.y) + (p0.z + p0.w)) + ((p1.x + p1.y) + (p1.z + p1.w)) +
-                      (((p2.x + p2.y) + (p2.z + p2.w)) + ((p3.x + p3.y) + (p3.z + p3.w)));
-            }
-            __builtin_amdgcn_wave_barrier();
-            sel = dpp_add<0xB1>(sel);   // quad_perm [1,0,3,2]
-            sel = dpp_add<0x4E>(sel);   // quad_perm [2,3,0,1]
+            const float sums[9] = {v0, v1, v2, v3, v4, v5, v6, v7, v8};
+            const float sel = reduce_rows(red, red_rd, red_lane, lane, sums);
             if (slot >= 0) {
                 if (DET) {
                     a.det[((size_t)(range.x + pos) * UNITS_PER_TILE + sub) * GSR_ACC_FLOATS + slot] = sel;
@@ -480,8 +390,7 @@ __device__ __forceinline__ void bwd_flush_tally(const CompositeBwdArgs &a, const
         }
         if (a.counters->trace && (unsigned long long)trace_idx < a.counters->trace_cap)
             a.counters->trace[trace_idx] = make_uint4((uint32_t)t_start, (uint32_t)wall_clock64(), (uint32_t)tl.staged,
-                                                      (uint32_t)min(tl.visits, 4095ull) | (__builtin_amdgcn_s_getreg(30724) & 0xffffu) << 12 |   // HW_ID[15:0]: wave, simd, pipe, cu, sh, se
-                                                      (__builtin_amdgcn_s_getreg(6164) & 0xfu) << 28);                                           // XCC_ID
+                                                      wave_trace_word(tl.visits));
     }
 }
 
@@ -501,12 +410,12 @@ __device__ __forceinline__ void bwd_kernel_body(const CompositeBwdArgs &a, int n
     bwd_flush_tally<COUNT>(a, tl, lane, (unsigned)unit, t_start);
 }
 template <int NPX, int COUNT, bool DET>
-__global__ __launch_bounds__(256) void composite_bwd_kernel(CompositeBwdArgs a, int nblocks_padded, int /*exact_cull*/) {
+__global__ __launch_bounds__(256) void composite_bwd_kernel(CompositeBwdArgs a, int nblocks_padded, int /*unused*/) {
     bwd_kernel_body<NPX, COUNT, DET, false>(a, nblocks_padded);
 }
 // the default instantiation: written-out walk (8 waves per SIMD asked for explicitly: the walk names 28 registers)
 template <int COUNT>      // 0, or 2 = with the wave timeline
-__global__ __launch_bounds__(256, 8) void composite_bwd_walk_kernel(CompositeBwdArgs a, int nblocks_padded, int /*exact_cull*/) {
+__global__ __launch_bounds__(256, 8) void composite_bwd_walk_kernel(CompositeBwdArgs a, int nblocks_padded, int /*unused*/) {
     bwd_kernel_body<2, COUNT, false, true>(a, nblocks_padded);
 }
 
@@ -650,12 +559,6 @@ __global__ __launch_bounds__(64, 8) void composite_bwd_lpt_kernel(CompositeBwdAr
     u.z = __builtin_amdgcn_readfirstlane(u.z); u.w = __builtin_amdgcn_readfirstlane(u.w);
     BwdTally tl;
     bwd_unit<2, 0, false, true>(a, stage_dyn, lane, (int)(u.x >> 1), (int)(u.x & 1u), (int)u.y, (int)u.z, u.w, tl);
-}
-hipError_t launch_composite_bwd_lpt(const CompositeBwdArgs &a, hipStream_t s) {
-    if (a.gridx * a.gridy <= 0) return hipSuccess;
-    const unsigned grid = GSR_SEG_BANDS * a.seg.band_units;
-    hipLaunchKernelGGL(composite_bwd_lpt_kernel, dim3(grid), dim3(64), (size_t)BWD_LDS_F4 * sizeof(float4) + (size_t)g_composite_lds_pad, s, a);
-    return hipGetLastError();
 }
 
 // The unit list of one band (one workgroup of 256 threads): every half tile's pieces -- [k seg, (k+1) seg) below each checkpoint the
@@ -816,29 +719,6 @@ __global__ __launch_bounds__(256) void det_reduce_kernel(CompositeBwdArgs a, int
     for (int v = 0; v < 9; v++) row[v] = sum[v];
 }
 
-template <int NPX>
-static hipError_t launch_bwd(const CompositeBwdArgs &a, int exact_cull, int wpb, hipStream_t s) {
-    const int T = a.gridx * a.gridy;
-    const int units = T * (4 / NPX);
-    const int blocks = (units + wpb - 1) / wpb;
-    const int padded = (blocks + 7) / 8 * 8;
-    const size_t lds = (size_t)wpb * BWD_LDS_F4 * sizeof(float4) + (size_t)g_composite_lds_pad;
-    if (a.det) {
-        hipLaunchKernelGGL((composite_bwd_kernel<NPX, 0, true>), dim3(padded), dim3(64 * wpb), lds, s, a, padded, exact_cull);
-        hipLaunchKernelGGL(det_reduce_kernel, dim3((a.P + 255) / 256), dim3(256), 0, s, a, 4 / NPX);
-    } else if (a.counters && a.count_mode == 2 && NPX == 2 && a.asm_walk)
-        hipLaunchKernelGGL(composite_bwd_walk_kernel<2>, dim3(padded), dim3(64 * wpb), lds, s, a, padded, exact_cull);
-    else if (a.counters && a.count_mode == 2)
-        hipLaunchKernelGGL((composite_bwd_kernel<NPX, 2, false>), dim3(padded), dim3(64 * wpb), lds, s, a, padded, exact_cull);
-    else if (a.counters)
-        hipLaunchKernelGGL((composite_bwd_kernel<NPX, 1, false>), dim3(padded), dim3(64 * wpb), lds, s, a, padded, exact_cull);
-    else if (NPX == 2 && a.asm_walk)
-        hipLaunchKernelGGL(composite_bwd_walk_kernel<0>, dim3(padded), dim3(64 * wpb), lds, s, a, padded, exact_cull);
-    else
-        hipLaunchKernelGGL((composite_bwd_kernel<NPX, 0, false>), dim3(padded), dim3(64 * wpb), lds, s, a, padded, exact_cull);
-    return hipGetLastError();
-}
-
 // The reverse pass only adds into the rows of Gaussians the forward pass marked (GeomView::touched) and into replica rows: only
 // those are cleared -- one wave-wide 16-byte store per 4 marked rows instead of a 66 P byte memset (config 3: 9 % are marked).
 __global__ __launch_bounds__(256) void zero_marked_rows_kernel(int P, const uint8_t *__restrict__ touched, const uint32_t *__restrict__ mark,
@@ -867,32 +747,94 @@ hipError_t launch_zero_marked_rows(int P, const uint8_t *touched, const uint32_t
     return hipGetLastError();
 }
 
-// waves of the persistent kernel: exactly what the chip holds of this instantiation (occupancy query; a workgroup that is not resident
-// from the start would sit on its first ticket until another wave retires), or fewer when the image cannot have that many units
-template <typename K>
-static int resident_waves(K kernel, size_t lds, std::atomic<int> &cache) {
-    int n = cache.load();
-    if (n > 0) return n;
-    int dev = 0, cus = 256, per_cu = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, lds) != hipSuccess || per_cu <= 0) per_cu = 16;
-    n = cus * per_cu / GSR_SEG_BANDS * GSR_SEG_BANDS;
-    if (n < GSR_SEG_BANDS) n = GSR_SEG_BANDS;
-    cache.store(n);
-    return n;
-}
-static size_t pk_lds_bytes() { return (size_t)BWD_LDS_F4 * sizeof(float4) + (size_t)g_composite_lds_pad; }
+// ---- which reverse kernel a call launches, and how: the one place where that is decided ----
+// Three routes (gsr_api.hip's bwd_plan picks one): the classic decomposition (one wave per npx blocks of a tile, wpb waves per
+// workgroup), the persistent kernel and the length-ordered one (both 2 blocks per wave, one wave per workgroup).  Per route the
+// variant follows from the call: deterministic sums, lane counting (count 1), or else the written-out walk where it exists -- 2 blocks
+// per wave, and in the persistent kernel only without zero-fill units, which that variant does not take -- with or without the wave
+// timeline (count 2).
+enum BwdRoute { BWD_CLASSIC, BWD_PERSISTENT, BWD_LPT };
+enum BwdVariant { VAR_PLAIN, VAR_TRACE, VAR_COUNT, VAR_DET, VAR_WALK, VAR_WALK_TRACE, VAR_N };
+struct BwdLaunch {
+    const void *kernel;
+    BwdVariant variant;
+    unsigned block;          // threads per workgroup
+    size_t lds;              // dynamic LDS bytes per workgroup
+    int det_units;           // > 0: det_reduce_kernel follows and adds this many slots per list entry
+};
+#define KERNEL(...) reinterpret_cast<const void *>(&__VA_ARGS__)
+#define CLASSIC_ROW(N, WALK, WALK_TRACE) \
+    {KERNEL(composite_bwd_kernel<N, 0, false>), KERNEL(composite_bwd_kernel<N, 2, false>), KERNEL(composite_bwd_kernel<N, 1, false>), \
+     KERNEL(composite_bwd_kernel<N, 0, true>), WALK, WALK_TRACE}
+static const void *const BWD_KERNELS[4][VAR_N] = {      // [1, 2, 4 blocks per wave, persistent][variant]
+    CLASSIC_ROW(1, nullptr, nullptr),
+    CLASSIC_ROW(2, KERNEL(composite_bwd_walk_kernel<0>), KERNEL(composite_bwd_walk_kernel<2>)),
+    CLASSIC_ROW(4, nullptr, nullptr),
+    {KERNEL(composite_bwd_pk_kernel<0, false>), KERNEL(composite_bwd_pk_kernel<2, false>), KERNEL(composite_bwd_pk_kernel<1, false>),
+     KERNEL(composite_bwd_pk_kernel<0, true>), KERNEL(composite_bwd_pk_walk_kernel<0>), KERNEL(composite_bwd_pk_walk_kernel<2>)}};
+#undef CLASSIC_ROW
 
-int composite_bwd_persistent_grid(int T, int det, int count_mode, int asm_walk) {
-    static std::atomic<int> c_plain{0}, c_det{0}, c_cnt{0}, c_trace{0}, c_walk{0}, c_walk_trace{0};
-    int n;
-    if (det) n = resident_waves(composite_bwd_pk_kernel<0, true>, pk_lds_bytes(), c_det);
-    else if (count_mode == 2 && asm_walk) n = resident_waves(composite_bwd_pk_walk_kernel<2>, pk_lds_bytes(), c_walk_trace);
-    else if (count_mode == 2) n = resident_waves(composite_bwd_pk_kernel<2, false>, pk_lds_bytes(), c_trace);
-    else if (count_mode == 1) n = resident_waves(composite_bwd_pk_kernel<1, false>, pk_lds_bytes(), c_cnt);
-    else if (asm_walk) n = resident_waves(composite_bwd_pk_walk_kernel<0>, pk_lds_bytes(), c_walk);
-    else n = resident_waves(composite_bwd_pk_kernel<0, false>, pk_lds_bytes(), c_plain);
+// npx: 1, 2 or 4 (classic route); count: count_variant(); fill_chunk: Gaussians per zero-fill unit of the persistent kernel's lists, 0 = none
+static BwdLaunch select_bwd(BwdRoute route, int npx, int wpb, bool det, int count, bool asm_walk, int fill_chunk) {
+    const int waves = route == BWD_CLASSIC ? wpb : 1;
+    BwdLaunch l;
+    l.block = 64u * waves;
+    l.lds = (size_t)waves * BWD_LDS_F4 * sizeof(float4) + (size_t)g_composite_lds_pad;
+    l.det_units = 0;
+    if (route == BWD_LPT) {      // bwd_plan takes this route only for the plain written-out walk
+        l.kernel = KERNEL(composite_bwd_lpt_kernel); l.variant = VAR_WALK;
+        return l;
+    }
+    const bool walk = asm_walk && (route == BWD_CLASSIC ? npx == 2 : fill_chunk == 0);
+    l.variant = det ? VAR_DET : count == 1 ? VAR_COUNT : walk ? (count ? VAR_WALK_TRACE : VAR_WALK) : (count ? VAR_TRACE : VAR_PLAIN);
+    l.kernel = BWD_KERNELS[route == BWD_PERSISTENT ? 3 : (npx == 1 ? 0 : (npx == 2 ? 1 : 2))][l.variant];
+    if (det) l.det_units = route == BWD_PERSISTENT ? 2 : 4 / npx;
+    return l;
+}
+#undef KERNEL
+
+// `padded`: the classic kernels' second argument; their third is a word they do not read, kept because taking it out renames them
+// (the other routes' kernels take the first argument alone)
+static hipError_t run_bwd(const BwdLaunch &l, const CompositeBwdArgs &a, unsigned grid, int padded, hipStream_t s) {
+    CompositeBwdArgs ka = a;
+    int unused = 0;
+    void *kargs[] = {&ka, &padded, &unused};
+    const hipError_t e = hipLaunchKernel(l.kernel, dim3(grid), dim3(l.block), kargs, l.lds, s);
+    if (e != hipSuccess) return e;
+    if (l.det_units) hipLaunchKernelGGL(det_reduce_kernel, dim3((a.P + 255) / 256), dim3(256), 0, s, a, l.det_units);
+    return hipGetLastError();
+}
+
+hipError_t launch_composite_bwd(const CompositeBwdArgs &a, int npx, int wpb, hipStream_t s) {
+    if (a.gridx * a.gridy <= 0) return hipSuccess;
+    npx = npx == 1 || npx == 2 ? npx : 4;
+    const int units = a.gridx * a.gridy * (4 / npx);
+    const int blocks = (units + wpb - 1) / wpb;
+    const int padded = (blocks + 7) / 8 * 8;
+    return run_bwd(select_bwd(BWD_CLASSIC, npx, wpb, a.det != nullptr, count_variant(a.counters, a.count_mode), a.asm_walk != 0, 0), a, (unsigned)padded, padded, s);
+}
+
+hipError_t launch_composite_bwd_lpt(const CompositeBwdArgs &a, hipStream_t s) {
+    if (a.gridx * a.gridy <= 0) return hipSuccess;
+    return run_bwd(select_bwd(BWD_LPT, 2, 1, false, 0, true, 0), a, GSR_SEG_BANDS * a.seg.band_units, 0, s);
+}
+
+// waves of the persistent kernel: exactly what the chip holds of the variant that will be launched (occupancy query; a workgroup that
+// is not resident from the start would sit on its first ticket until another wave retires), or fewer when the image cannot have that
+// many units
+int composite_bwd_persistent_grid(int T, int det, int count, int asm_walk, int fill_chunk) {
+    static std::atomic<int> cache[VAR_N];
+    const BwdLaunch l = select_bwd(BWD_PERSISTENT, 2, 1, det != 0, count, asm_walk != 0, fill_chunk);
+    int n = cache[l.variant].load();
+    if (n <= 0) {
+        int dev = 0, cus = 256, per_cu = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, l.kernel, (int)l.block, l.lds) != hipSuccess || per_cu <= 0) per_cu = 16;
+        n = cus * per_cu / GSR_SEG_BANDS * GSR_SEG_BANDS;
+        if (n < GSR_SEG_BANDS) n = GSR_SEG_BANDS;
+        cache[l.variant].store(n);
+    }
     long long most = 2ll * T * (1 + GSR_SEG_MAXCK);              // units a frame can have at all
     most = (most + GSR_SEG_BANDS - 1) / GSR_SEG_BANDS * GSR_SEG_BANDS;     // a multiple of the bands: wave b starts in band b & 7
     return (int)(most < n ? (most > 0 ? most : GSR_SEG_BANDS) : n);
@@ -900,21 +842,7 @@ int composite_bwd_persistent_grid(int T, int det, int count_mode, int asm_walk) 
 
 hipError_t launch_composite_bwd_persistent(const CompositeBwdArgs &a, int grid, hipStream_t s) {
     if (a.gridx * a.gridy <= 0 || grid <= 0) return hipSuccess;
-    const size_t lds = pk_lds_bytes();
-    if (a.det) {
-        hipLaunchKernelGGL((composite_bwd_pk_kernel<0, true>), dim3(grid), dim3(64), lds, s, a);
-        hipLaunchKernelGGL(det_reduce_kernel, dim3((a.P + 255) / 256), dim3(256), 0, s, a, 2);
-    } else if (a.counters && a.count_mode == 2 && a.asm_walk && a.fill.chunk == 0)
-        hipLaunchKernelGGL(composite_bwd_pk_walk_kernel<2>, dim3(grid), dim3(64), lds, s, a);
-    else if (a.counters && a.count_mode == 2)
-        hipLaunchKernelGGL((composite_bwd_pk_kernel<2, false>), dim3(grid), dim3(64), lds, s, a);
-    else if (a.counters)
-        hipLaunchKernelGGL((composite_bwd_pk_kernel<1, false>), dim3(grid), dim3(64), lds, s, a);
-    else if (a.asm_walk && a.fill.chunk == 0)
-        hipLaunchKernelGGL(composite_bwd_pk_walk_kernel<0>, dim3(grid), dim3(64), lds, s, a);
-    else
-        hipLaunchKernelGGL((composite_bwd_pk_kernel<0, false>), dim3(grid), dim3(64), lds, s, a);
-    return hipGetLastError();
+    return run_bwd(select_bwd(BWD_PERSISTENT, 2, 1, a.det != nullptr, count_variant(a.counters, a.count_mode), a.asm_walk != 0, a.fill.chunk), a, (unsigned)grid, 0, s);
 }
 
 // debug-build self test: one deliberate out-of-range index; the words must then read (GSR_BOUND_SELFTEST, 5, 4, 1)
@@ -924,15 +852,6 @@ __global__ void bound_selftest_kernel(uint32_t *words) {
 hipError_t launch_bound_selftest(uint32_t *words, hipStream_t s) {
     hipLaunchKernelGGL(bound_selftest_kernel, dim3(1), dim3(1), 0, s, words);
     return hipGetLastError();
-}
-
-hipError_t launch_composite_bwd(const CompositeBwdArgs &a, int npx, int exact_cull, int wpb, hipStream_t s) {
-    if (a.gridx * a.gridy <= 0) return hipSuccess;
-    switch (npx) {
-        case 1: return launch_bwd<1>(a, exact_cull, wpb, s);
-        case 2: return launch_bwd<2>(a, exact_cull, wpb, s);
-        default: return launch_bwd<4>(a, exact_cull, wpb, s);
-    }
 }
 
 }  // namespace gsr

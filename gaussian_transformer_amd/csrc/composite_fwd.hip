@@ -14,13 +14,11 @@
 // per-pixel exponent feeds v_exp_f32 directly.
 // blockIdx is remapped so that each XCD (blocks b, b+8, ... share one) walks a contiguous band
 // of tiles: neighbouring tiles share splats, which keeps the record gathers in that XCD's L2.
-#include "gsr_device.h"
+#include "composite_common.h"
 #include "gsr_internal.h"
 
 namespace gsr {
 extern int g_composite_lds_pad;
-
-#define LOG2E 1.4426950408889634f
 
 // ---- the splat walk of one staged batch, 2 blocks per wave, written out (round 3) ----
 // What the compiler makes of the C++ walk below is bound by the SCALAR unit as much as by the vector one: 31 scalar instructions per
@@ -35,6 +33,28 @@ extern int g_composite_lds_pad;
 // Staged record of entry j at lds + 48 j: (px, py, a, b) (c, opacity, r, g) (b, ...).  v52..v63 are used by name (the b128 reads need
 // register tuples whose components can be addressed).  Hazards (gfx940 family): v_exp result first read one instruction later;
 // no VALU reads an SGPR a VALU wrote; EXEC is restored by SALU long before the next v_readlane-class instruction (there is none).
+// One block's part of a visit, as text: from dx to the blend.  Operands by name: the block's T, C0..C2, last (L) and fx; STOP is the label of
+// the block's "some pixel stops here" code behind the loop, BACK the one it returns to.  v53, v55, v56, v61 are its temporaries.
+#define FWD_WALK_BLOCK(T, C0, C1, C2, L, fx, STOP, BACK) \
+        "v_sub_f32 v61, v52, %[" #fx "]\n"             /* dx */ \
+        "v_fma_f32 v53, v54, v61, v62\n"             /* a dx + u */ \
+        "v_fma_f32 v61, v53, v61, v63\n"             /* power (log2 units) */ \
+        "v_exp_f32 v53, v61\n" \
+        "v_cmpx_nlt_f32 vcc, 0, v61\n"               /* !(power > 0) */ \
+        "v_mul_f32 v53, v57, v53\n"                  /* opacity * G  (the v_exp result is first read one instruction after it) */ \
+        "v_cmpx_ngt_f32 vcc, %[amin], v53\n"         /* !(alpha < 1/255) */ \
+        "v_min_f32 v55, 0x3f7d70a4, v53\n"           /* min(0.99, .) */ \
+        "v_fma_f32 v56, -%[" #T "], v55, %[" #T "]\n"        /* T (1 - alpha) */ \
+        "v_cmp_gt_f32 vcc, %[tmin], v56\n"           /* it would fall below 1e-4: the pixel stops in front of this splat */ \
+        "s_cbranch_vccnz " #STOP "f\n" \
+        #BACK ":\n" \
+        "v_mul_f32 %[" #T "], %[" #T "], v55\n" \
+        "s_waitcnt lgkmcnt(0)\n" \
+        "v_fmac_f32 %[" #C2 "], v60, %[" #T "]\n" \
+        "v_fmac_f32 %[" #C1 "], v59, %[" #T "]\n" \
+        "v_fmac_f32 %[" #C0 "], v58, %[" #T "]\n" \
+        "v_mov_b32 %[" #T "], v56\n" \
+        "v_mov_b32 %[" #L "], %[pos]\n"
 struct WalkState { float T, C0, C1, C2; uint32_t last; };
 __device__ __forceinline__ void walk_batch_2blocks(uint32_t lds, uint32_t pos1, float fx0, float fx1, float fy, unsigned long long &m,
                                                    unsigned long long &b0m, unsigned long long &b1m, unsigned long long &d0,
@@ -60,48 +80,12 @@ __device__ __forceinline__ void walk_batch_2blocks(uint32_t lds, uint32_t pos1, 
         "s_bitcmp1_b64 %[b0m], %[j]\n"
         "s_cbranch_scc0 2f\n"
         "s_not_b64 exec, %[d0]\n"
-        "v_sub_f32 v61, v52, %[fx0]\n"             // dx
-        "v_fma_f32 v53, v54, v61, v62\n"             // a dx + u
-        "v_fma_f32 v61, v53, v61, v63\n"             // power (log2 units)
-        "v_exp_f32 v53, v61\n"
-        "v_cmpx_nlt_f32 vcc, 0, v61\n"               // !(power > 0)
-        "v_mul_f32 v53, v57, v53\n"                  // opacity * G  (the v_exp result is first read one instruction after it)
-        "v_cmpx_ngt_f32 vcc, %[amin], v53\n"         // !(alpha < 1/255)
-        "v_min_f32 v55, 0x3f7d70a4, v53\n"           // min(0.99, .)
-        "v_fma_f32 v56, -%[T0], v55, %[T0]\n"        // T (1 - alpha)
-        "v_cmp_gt_f32 vcc, %[tmin], v56\n"           // it would fall below 1e-4: the pixel stops in front of this splat
-        "s_cbranch_vccnz 20f\n"
-        "21:\n"
-        "v_mul_f32 %[T0], %[T0], v55\n"
-        "s_waitcnt lgkmcnt(0)\n"
-        "v_fmac_f32 %[C02], v60, %[T0]\n"
-        "v_fmac_f32 %[C01], v59, %[T0]\n"
-        "v_fmac_f32 %[C00], v58, %[T0]\n"
-        "v_mov_b32 %[T0], v56\n"
-        "v_mov_b32 %[L0], %[pos]\n"
+        FWD_WALK_BLOCK(T0, C00, C01, C02, L0, fx0, 20, 21)
         "2:\n"
         "s_bitcmp1_b64 %[b1m], %[j]\n"
         "s_cbranch_scc0 3f\n"
         "s_not_b64 exec, %[d1]\n"
-        "v_sub_f32 v61, v52, %[fx1]\n"             // dx
-        "v_fma_f32 v53, v54, v61, v62\n"             // a dx + u
-        "v_fma_f32 v61, v53, v61, v63\n"             // power (log2 units)
-        "v_exp_f32 v53, v61\n"
-        "v_cmpx_nlt_f32 vcc, 0, v61\n"               // !(power > 0)
-        "v_mul_f32 v53, v57, v53\n"                  // opacity * G  (the v_exp result is first read one instruction after it)
-        "v_cmpx_ngt_f32 vcc, %[amin], v53\n"         // !(alpha < 1/255)
-        "v_min_f32 v55, 0x3f7d70a4, v53\n"           // min(0.99, .)
-        "v_fma_f32 v56, -%[T1], v55, %[T1]\n"        // T (1 - alpha)
-        "v_cmp_gt_f32 vcc, %[tmin], v56\n"           // it would fall below 1e-4: the pixel stops in front of this splat
-        "s_cbranch_vccnz 30f\n"
-        "31:\n"
-        "v_mul_f32 %[T1], %[T1], v55\n"
-        "s_waitcnt lgkmcnt(0)\n"
-        "v_fmac_f32 %[C12], v60, %[T1]\n"
-        "v_fmac_f32 %[C11], v59, %[T1]\n"
-        "v_fmac_f32 %[C10], v58, %[T1]\n"
-        "v_mov_b32 %[T1], v56\n"
-        "v_mov_b32 %[L1], %[pos]\n"
+        FWD_WALK_BLOCK(T1, C10, C11, C12, L1, fx1, 30, 31)
         "3:\n"
         "s_mov_b64 exec, -1\n"
         "s_waitcnt lgkmcnt(0)\n"                      // (a visit that blended nothing must not leave the read of v60 in flight)
@@ -147,7 +131,6 @@ __device__ __forceinline__ void fwd_unit(const CompositeArgs &a, float4 *my, con
     const int tx = tile % a.gridx, ty = tile / a.gridx;
     const uint2 range = a.ranges[tile];
     const int n = (int)(range.y - range.x);
-    const float4 *rec4 = reinterpret_cast<const float4 *>(a.rec);
 
     // Per-pixel state: Tr = transmittance so far (it simply stops changing once the pixel is finished), C = colour,
     // last = 1-based list position of the last blended splat.  Which pixels are finished is kept as one 64-bit lane
@@ -161,13 +144,11 @@ __device__ __forceinline__ void fwd_unit(const CompositeArgs &a, float4 *my, con
     uint32_t blk_done = 0;                            // bit q: every pixel of block q is finished (wave-uniform)
 #pragma unroll
     for (int q = 0; q < NPX; q++) {
-        const int blk = NPX == 4 ? q : (NPX == 2 ? sub * 2 + q : sub);
-        const int x0 = tx * GSR_TILE + (blk & 1) * 8, y0 = ty * GSR_TILE + (blk >> 1) * 8;
-        const int x = x0 + (lane & 7), y = y0 + (lane >> 3);
-        inside[q] = x < a.W && y < a.H;
-        fx[q] = (float)x; fy[q] = (float)y;
-        bxa[q] = (float)x0; bya[q] = (float)y0;
-        bxb[q] = (float)min(x0 + 7, a.W - 1); byb[q] = (float)min(y0 + 7, a.H - 1);
+        const BlockGeom bg = block_geom(tx, ty, block_index<NPX>(sub, q), lane, a.W, a.H);
+        inside[q] = bg.inside;
+        fx[q] = (float)bg.x; fy[q] = (float)bg.y;
+        bxa[q] = (float)bg.x0; bya[q] = (float)bg.y0;
+        bxb[q] = (float)min(bg.x0 + 7, a.W - 1); byb[q] = (float)min(bg.y0 + 7, a.H - 1);
         Tr[q] = 1.f; C0[q] = C1[q] = C2[q] = 0.f; last[q] = 0u;
         done[q] = __builtin_amdgcn_ballot_w64(!inside[q]);
         if (done[q] == ~0ull) blk_done |= 1u << q;
@@ -213,7 +194,8 @@ __device__ __forceinline__ void fwd_unit(const CompositeArgs &a, float4 *my, con
         uint32_t mybits = 0u;                         // blocks of this wave the lane's entry can reach
         if (lane < cnt && GSR_IDX_OK((size_t)range.x + base + lane, a.contrib_stride, a.seg.hdr + GSR_DBG_SEG_WORD, GSR_BOUND_FWD_LIST_READ)) {
             const uint32_t g = a.point_list[range.x + base + lane];
-            const float4 r0 = rec4[3 * (size_t)g], r1 = rec4[3 * (size_t)g + 1], r2 = rec4[3 * (size_t)g + 2];
+            float4 r0, r1, r2, s0, s1;
+            gather_record(a.rec, g, r0, r1, r2);
             uint32_t bits = (1u << NPX) - 1u;
             if (exact_cull && r2.z > 0.f) {           // tau == 0: forward ran with culling off -> no information
                 const float invA = 1.f / r0.z, invC = 1.f / r1.x;
@@ -230,15 +212,12 @@ __device__ __forceinline__ void fwd_unit(const CompositeArgs &a, float4 *my, con
             // the reverse pass stages the same entries against the same blocks: hand it the reachability bits
 #pragma unroll
             for (int q = 0; q < NPX; q++) {
-                const int blk = NPX == 4 ? q : (NPX == 2 ? sub * 2 + q : sub);
-                a.contrib[(size_t)blk * a.contrib_stride + range.x + base + lane] = (uint8_t)((bits >> q) & 1u);
+                a.contrib[(size_t)block_index<NPX>(sub, q) * a.contrib_stride + range.x + base + lane] = (uint8_t)((bits >> q) & 1u);
             }
             // (px, py, -0.5*log2e*A, -log2e*B) (-0.5*log2e*C, opacity, r, g) (b, -, block bits, -)
-            // (built as new vectors: overwriting components of the loaded ones sent them through scratch memory, 16 bytes of private
-            //  segment per lane and its set-up at every wave's start)
-            const StagedConic sc = stage_conic(r0.z, r0.w, r1.x);
-            my[lane * 3 + 0] = make_float4(r0.x, r0.y, sc.a, sc.b);
-            my[lane * 3 + 1] = make_float4(sc.c, r1.y, r1.z, r1.w);
+            stage_record(r0, r1, s0, s1);
+            my[lane * 3 + 0] = s0;
+            my[lane * 3 + 1] = s1;
             my[lane * 3 + 2] = make_float4(r2.x, 0.f, __uint_as_float(bits), 0.f);
         }
         uint64_t todo = __ballot(live);
@@ -318,8 +297,7 @@ __device__ __forceinline__ void fwd_unit(const CompositeArgs &a, float4 *my, con
         }
         if (a.counters->trace && (unsigned long long)trace_id < a.counters->trace_cap)
             a.counters->trace[trace_id] = make_uint4((uint32_t)t_start, (uint32_t)wall_clock64(), (uint32_t)c_staged,
-                                                 (uint32_t)min(c_visits, 4095ull) | (__builtin_amdgcn_s_getreg(30724) & 0xffffu) << 12 |   // HW_ID[15:0]: wave, simd, pipe, cu, sh, se
-                                                 (__builtin_amdgcn_s_getreg(6164) & 0xfu) << 28);                                           // XCC_ID
+                                                 wave_trace_word(c_visits));
     }
     if (file_info) {
         // back over the checkpoints: each one's colour (its own segment's) is replaced by the colour composited BEHIND its
@@ -338,8 +316,7 @@ __device__ __forceinline__ void fwd_unit(const CompositeArgs &a, float4 *my, con
         int ml = 0;
 #pragma unroll
         for (int q = 0; q < NPX; q++) ml = max(ml, (int)last[q]);
-#pragma unroll
-        for (int sft = 32; sft > 0; sft >>= 1) ml = max(ml, __shfl_xor(ml, sft));
+        GSR_WAVE_MAX_I32(ml);
         if (lane < 8) a.seg.ck_slot[(size_t)unit * 8 + lane] = ck_slots;
         if (lane == 0) a.seg.info[unit] = make_uint2((uint32_t)ml, (uint32_t)n_ck);
     }
@@ -388,25 +365,7 @@ __device__ __forceinline__ void walk_batch_1block(uint32_t lds, uint32_t pos1, f
         "s_waitcnt lgkmcnt(1)\n"
         "v_mul_f32 v63, v61, v56\n"                  // c dy
         "v_mul_f32 v63, v61, v63\n"                  // w = (c dy) dy
-        "v_sub_f32 v61, v52, %[fx]\n"                // dx
-        "v_fma_f32 v53, v54, v61, v62\n"             // a dx + u
-        "v_fma_f32 v61, v53, v61, v63\n"             // power (log2 units)
-        "v_exp_f32 v53, v61\n"
-        "v_cmpx_nlt_f32 vcc, 0, v61\n"               // !(power > 0)
-        "v_mul_f32 v53, v57, v53\n"                  // opacity * G
-        "v_cmpx_ngt_f32 vcc, %[amin], v53\n"         // !(alpha < 1/255)
-        "v_min_f32 v55, 0x3f7d70a4, v53\n"           // min(0.99, .)
-        "v_fma_f32 v56, -%[T], v55, %[T]\n"          // T (1 - alpha)
-        "v_cmp_gt_f32 vcc, %[tmin], v56\n"
-        "s_cbranch_vccnz 20f\n"
-        "21:\n"
-        "v_mul_f32 %[T], %[T], v55\n"
-        "s_waitcnt lgkmcnt(0)\n"
-        "v_fmac_f32 %[C2], v60, %[T]\n"
-        "v_fmac_f32 %[C1], v59, %[T]\n"
-        "v_fmac_f32 %[C0], v58, %[T]\n"
-        "v_mov_b32 %[T], v56\n"
-        "v_mov_b32 %[L], %[pos]\n"
+        FWD_WALK_BLOCK(T, C0, C1, C2, L, fx, 20, 21)
         "s_mov_b64 exec, -1\n"
         "s_waitcnt lgkmcnt(0)\n"
         "s_cmp_lg_u64 %[m], 0\n"
@@ -426,6 +385,8 @@ __device__ __forceinline__ void walk_batch_1block(uint32_t lds, uint32_t pos1, f
         : "memory", "scc", "vcc", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63");
 }
 
+#undef FWD_WALK_BLOCK
+
 struct PairShared {                 // one per workgroup (LDS), zeroed before the waves part ways
     uint32_t slot[GSR_SEG_MAXCK + 1];   // checkpoint k: 0 = nobody was here yet, 1 = being drawn, 2 + s = pool slot s, ~0u = the pool's share is used up
     uint32_t ml[2], nck[2];             // what each wave found: largest last contributor, checkpoints it wrote
@@ -443,11 +404,10 @@ __device__ __forceinline__ void fwd_unit_pair(const CompositeArgs &a, float4 *my
     const int n = __builtin_amdgcn_readfirstlane((int)(range.y - range.x));
     const float4 *rec4 = reinterpret_cast<const float4 *>(a.rec);
     const int blk = sub * 2 + w;
-    const int x0 = tx * GSR_TILE + (blk & 1) * 8, y0 = ty * GSR_TILE + (blk >> 1) * 8;
-    const int x = x0 + (lane & 7), y = y0 + (lane >> 3);
-    const bool inside = x < a.W && y < a.H;
-    const float fx = (float)x, fy = (float)y;
-    const float bxa = (float)x0, bya = (float)y0, bxb = (float)min(x0 + 7, a.W - 1), byb = (float)min(y0 + 7, a.H - 1);
+    const BlockGeom bg = block_geom(tx, ty, blk, lane, a.W, a.H);
+    const bool inside = bg.inside;
+    const float fx = (float)bg.x, fy = (float)bg.y;
+    const float bxa = (float)bg.x0, bya = (float)bg.y0, bxb = (float)min(bg.x0 + 7, a.W - 1), byb = (float)min(bg.y0 + 7, a.H - 1);
     WalkState p = {1.f, 0.f, 0.f, 0.f, 0u};
     unsigned long long done = __builtin_amdgcn_ballot_w64(!inside);
     const bool seg_on = a.seg_len > 0;
@@ -515,7 +475,7 @@ __device__ __forceinline__ void fwd_unit_pair(const CompositeArgs &a, float4 *my
     }
     if (COUNT && lane == 0 && a.counters && a.counters->trace && (unsigned long long)trace_id < a.counters->trace_cap)
         a.counters->trace[trace_id] = make_uint4((uint32_t)t_start, (uint32_t)wall_clock64(), (uint32_t)c_staged,
-                                                 (__builtin_amdgcn_s_getreg(30724) & 0xffffu) << 12 | (__builtin_amdgcn_s_getreg(6164) & 0xfu) << 28);
+                                                 wave_trace_word(0ull));
     if (seg_on) {
         n_ck = __builtin_amdgcn_readfirstlane(n_ck);      // (wave-uniform; said so for the compiler: readlane's index below)
         // back over the checkpoints this wave wrote: its own segment's colour -> the colour composited behind the boundary
@@ -527,8 +487,7 @@ __device__ __forceinline__ void fwd_unit_pair(const CompositeArgs &a, float4 *my
             p.C0 += c.y; p.C1 += c.z; p.C2 += c.w;
         }
         int ml = (int)p.last;
-#pragma unroll
-        for (int sft = 32; sft > 0; sft >>= 1) ml = max(ml, __shfl_xor(ml, sft));
+        GSR_WAVE_MAX_I32(ml);
         if (lane == 0) {
             ps->ml[w] = (uint32_t)ml; ps->nck[w] = (uint32_t)n_ck;
             __threadfence_block();
@@ -543,7 +502,7 @@ __device__ __forceinline__ void fwd_unit_pair(const CompositeArgs &a, float4 *my
     }
     if (inside) {
         const size_t HW = (size_t)a.W * a.H;
-        const size_t pix = (size_t)y * a.W + (size_t)x;
+        const size_t pix = (size_t)bg.y * a.W + (size_t)bg.x;
         a.final_T[pix] = p.T;
         a.n_contrib[pix] = p.last;
         a.out_color[pix] = p.C0 + p.T * a.bg[0];
@@ -594,44 +553,31 @@ __global__ __launch_bounds__(128, 8) void composite_fwd_pair_kernel(CompositeArg
     else if (w == 0) fwd_unit<2, COUNT, true>(a, stage_dyn, lane, tile, sub, unit * 2, exact_cull);
 }
 
-template <int NPX>
-static hipError_t launch_fwd(const CompositeArgs &a, int exact_cull, int wpb, hipStream_t s) {
-    const int T = a.gridx * a.gridy;
-    const int units = T * (4 / NPX);
-    const int blocks = (units + wpb - 1) / wpb;
-    const int padded = (blocks + 7) / 8 * 8;
-    if (NPX == 2 && a.asm_walk && a.pair_long_n > 0 && !(a.counters && a.count_mode == 1)) {
-        const int pblocks = (units + 7) / 8 * 8;      // one workgroup per half tile
-        const size_t plds = (size_t)2 * 64 * 3 * sizeof(float4) + (size_t)g_composite_lds_pad;
-        if (a.counters && a.count_mode == 2) hipLaunchKernelGGL(composite_fwd_pair_kernel<2>, dim3(pblocks), dim3(128), plds, s, a, pblocks, exact_cull);
-        else hipLaunchKernelGGL(composite_fwd_pair_kernel<0>, dim3(pblocks), dim3(128), plds, s, a, pblocks, exact_cull);
-        return hipGetLastError();
-    }
-    if (a.counters && a.count_mode == 2 && NPX == 2 && a.asm_walk)
-        hipLaunchKernelGGL(composite_fwd_walk_kernel<2>, dim3(padded), dim3(64 * wpb), (size_t)wpb * 64 * 3 * sizeof(float4) + (size_t)g_composite_lds_pad, s, a,
-                           padded, exact_cull);
-    else if (a.counters && a.count_mode == 2)
-        hipLaunchKernelGGL((composite_fwd_kernel<NPX, 2>), dim3(padded), dim3(64 * wpb), (size_t)wpb * 64 * 3 * sizeof(float4) + (size_t)g_composite_lds_pad, s, a,
-                           padded, exact_cull);
-    else if (a.counters)
-        hipLaunchKernelGGL((composite_fwd_kernel<NPX, 1>), dim3(padded), dim3(64 * wpb), (size_t)wpb * 64 * 3 * sizeof(float4) + (size_t)g_composite_lds_pad, s, a,
-                           padded, exact_cull);
-    else if (NPX == 2 && a.asm_walk)
-        hipLaunchKernelGGL(composite_fwd_walk_kernel<0>, dim3(padded), dim3(64 * wpb), (size_t)wpb * 64 * 3 * sizeof(float4) + (size_t)g_composite_lds_pad, s, a,
-                           padded, exact_cull);
-    else
-        hipLaunchKernelGGL((composite_fwd_kernel<NPX, 0>), dim3(padded), dim3(64 * wpb), (size_t)wpb * 64 * 3 * sizeof(float4) + (size_t)g_composite_lds_pad, s, a,
-                           padded, exact_cull);
-    return hipGetLastError();
-}
+// Which forward kernel a call launches, and how: the one place where that is decided.  count: count_variant() -- lane counting
+// (1) exists for the C++ walk alone.  The written-out walk exists for 2 blocks per wave; with pair_long_n > 0 it is launched as
+// workgroups of two waves, one per half tile (composite_fwd_pair_kernel).
+using FwdKernel = void (*)(CompositeArgs, int, int);
+static const FwdKernel FWD_KERNELS[5][3] = {      // [1, 2, 4 blocks per wave, written-out walk, ... by pairs of waves][count]
+    {composite_fwd_kernel<1, 0>, composite_fwd_kernel<1, 1>, composite_fwd_kernel<1, 2>},
+    {composite_fwd_kernel<2, 0>, composite_fwd_kernel<2, 1>, composite_fwd_kernel<2, 2>},
+    {composite_fwd_kernel<4, 0>, composite_fwd_kernel<4, 1>, composite_fwd_kernel<4, 2>},
+    {composite_fwd_walk_kernel<0>, nullptr, composite_fwd_walk_kernel<2>},
+    {composite_fwd_pair_kernel<0>, nullptr, composite_fwd_pair_kernel<2>}};
 
 hipError_t launch_composite_fwd(const CompositeArgs &a, int npx, int exact_cull, int wpb, hipStream_t s) {
     if (a.gridx * a.gridy <= 0) return hipSuccess;
-    switch (npx) {
-        case 1: return launch_fwd<1>(a, exact_cull, wpb, s);
-        case 2: return launch_fwd<2>(a, exact_cull, wpb, s);
-        default: return launch_fwd<4>(a, exact_cull, wpb, s);
-    }
+    npx = npx == 1 || npx == 2 ? npx : 4;
+    const int count = count_variant(a.counters, a.count_mode);
+    const bool walk = npx == 2 && a.asm_walk && count != 1;
+    const bool pair = walk && a.pair_long_n > 0;
+    const int units = a.gridx * a.gridy * (4 / npx);
+    const int waves = pair ? 2 : wpb;                             // per workgroup; pair: one workgroup per half tile
+    const int blocks = pair ? units : (units + wpb - 1) / wpb;
+    const int padded = (blocks + 7) / 8 * 8;
+    const size_t lds = (size_t)waves * 64 * 3 * sizeof(float4) + (size_t)g_composite_lds_pad;
+    const FwdKernel kernel = FWD_KERNELS[pair ? 4 : (walk ? 3 : (npx == 1 ? 0 : (npx == 2 ? 1 : 2)))][count];
+    hipLaunchKernelGGL(kernel, dim3(padded), dim3(64 * waves), lds, s, a, padded, exact_cull);
+    return hipGetLastError();
 }
 
 }  // namespace gsr

@@ -22,21 +22,24 @@
 // pergauss_bwd.hip's streaming kernel then runs unchanged on these rows (no colour input at all: shs = colors_precomp = NULL is a case
 // its launcher already takes), and depth_finish_kernel adds the dL/dv term to dL/dmeans3D -- and, with accumulate, the whole result
 // to the caller's buffers.
+// Shared with the colour passes, one copy each in composite_common.h: the staged conic pair, the replica-row rule and the LDS + DPP
+// reduction (here with 7 sums, there with 9); the signed wave-wide max is gsr_device.h's.  Kept here: the half tile's geometry (its y is
+// formed once for both blocks) and the record gather behind the range check on the id -- through the shared helpers these two kernels
+// come out with another instruction order (scripts/isa_diff.py).  The recurrences differ from bwd_unit's on purpose, see above.
 // Zeroing: only the rows that can be added into (marked Gaussians + replica rows) are cleared, by composite_bwd.hip's
 // launch_zero_marked_rows: 64 B per marked row and a byte read per Gaussian instead of a 66 P byte memset.
 #include <string.h>
 
 #include "../../include/gsr_depth.h"
-#include "gsr_device.h"
+#include "composite_common.h"
 #include "gsr_host.h"
 #include "gsr_internal.h"
 
 namespace gsr {
 namespace {
 
-#define DRED_STRIDE 68                                  // as composite_bwd.hip: rows of 64 would start in one LDS bank
 #define DEPTH_NSUM 7                                    // s dx, s dy, s dx dx, s dx dy, s dy dy, s, dL/dv -> row slots 3..9
-#define DEPTH_BWD_LDS_F4 (64 * 2 + (DEPTH_NSUM * DRED_STRIDE + 3) / 4)
+#define DEPTH_BWD_LDS_F4 (64 * 2 + (DEPTH_NSUM * RED_STRIDE + 3) / 4)
 
 struct DepthArgs {
     int W, H, gridx, gridy, P, mode;
@@ -52,12 +55,6 @@ struct DepthArgs {
     const float *gD, *gA;                   // reverse (either may be NULL)
     float *acc;
 };
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    const int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true);
-    return v + __int_as_float(moved);
-}
 
 // what a wave knows of its half tile before it walks: pixel coordinates, each pixel's last contributor (0 outside the image), the
 // largest one per block and overall (clamped to the list: a garbage n_contrib cannot send the walk past the tile's range)
@@ -83,8 +80,7 @@ __device__ __forceinline__ HalfTile half_tile(const DepthArgs &a, const int tile
         h.fx[q] = (float)x;
         h.last[q] = h.inside[q] ? (int)a.n_contrib[h.pix[q]] : 0;
         int m = h.last[q];
-#pragma unroll
-        for (int sft = 32; sft > 0; sft >>= 1) m = max(m, __shfl_xor(m, sft));
+        GSR_WAVE_MAX_I32(m);
         h.blk_last[q] = __builtin_amdgcn_readfirstlane(m);
         hi = max(hi, h.blk_last[q]);
     }
@@ -108,14 +104,14 @@ __device__ __forceinline__ bool stage_entry(const DepthArgs &a, const HalfTile &
     for (int q = 0; q < 2; q++) bits |= a.contrib[(size_t)(sub * 2 + q) * a.list_len + at] ? (1u << q) : 0u;
     uint32_t row = g;
     if (want_row) {
-        const uint32_t hot = __float_as_uint(r2.w);      // replica code (gsr_internal.h): 0 = the Gaussian's own row
-        if (hot) row = (uint32_t)a.P + (hot >> 4) + ((uint32_t)tile & ((1u << (hot & 15u)) - 1u));
+        row = replica_row(__float_as_uint(r2.w), g, a.P, tile);
         if ((size_t)row >= a.acc_rows) return false;
     }
-    const StagedConic sc = stage_conic(r0.z, r0.w, r1.x);        // as the colour pass stages it
+    float4 s0, s1;
+    stage_record(r0, r1, s0, s1);                                // as the colour pass stages it
     const float v = a.mode == GSR_DEPTH_INVERSE ? 1.0f / r2.y : r2.y;
-    my[lane] = make_float4(r0.x, r0.y, sc.a, sc.b);
-    my[64 + lane] = make_float4(sc.c, r1.y, v, __uint_as_float(bits | (row << 4)));      // row < 2^28 (checked by the entry point)
+    my[lane] = s0;
+    my[64 + lane] = make_float4(s1.x, s1.y, v, __uint_as_float(bits | (row << 4)));      // row < 2^28 (checked by the entry point)
     return bits != 0u;
 }
 
@@ -171,7 +167,7 @@ __global__ __launch_bounds__(256) void depth_bwd_kernel(DepthArgs a) {
     const int unit = blockIdx.x * 4 + wave, tile = unit >> 1, sub = unit & 1;
     if (tile >= a.gridx * a.gridy) return;              // wave-uniform
     float4 *my = stage[wave];
-    float *red = reinterpret_cast<float *>(my + 128);   // [value 0..6][lane 0..63], rows of DRED_STRIDE floats
+    float *red = reinterpret_cast<float *>(my + 128);   // [value 0..6][lane 0..63], rows of RED_STRIDE floats
     const HalfTile h = half_tile(a, tile, sub, lane);
     if (h.hi <= 0) return;
     // per pixel: Tr = transmittance behind the splats visited so far, S = sum of v alpha T over them (the running suffix of the depth
@@ -184,10 +180,10 @@ __global__ __launch_bounds__(256) void depth_bwd_kernel(DepthArgs a) {
         gAT[q] = h.inside[q] && a.gA ? a.gA[h.pix[q]] * Tr[q] : 0.f;
     }
     // lane 4 value + part adds red[value][16 part .. 16 part + 15]; two DPP steps fold the four parts; lanes 0, 4, .., 24 hold the totals
-    const int rvalue = lane >> 2, rpart = lane & 3;
-    const bool red_lane = rvalue < DEPTH_NSUM;
-    const float4 *red_rd = reinterpret_cast<const float4 *>(red + (red_lane ? rvalue : 0) * DRED_STRIDE + rpart * 16);
-    const int slot = (red_lane && rpart == 0) ? 3 + rvalue : -1;
+    const float4 *red_rd;
+    bool red_lane;
+    const int rvalue = reduce_setup<DEPTH_NSUM>(red, lane, red_rd, red_lane);
+    const int slot = rvalue >= 0 ? 3 + rvalue : -1;
 
     for (int base = ((h.hi - 1) >> 6) << 6; base >= 0; base -= 64) {
         const int cnt = min(64, h.hi - base);
@@ -234,19 +230,8 @@ __global__ __launch_bounds__(256) void depth_bwd_kernel(DepthArgs a) {
                 s3 += sx * dx; s4 += sx * dy; s5 += sy * dy;
             }
             if (any_ok == 0ull) continue;               // wave-uniform: no pixel of this wave blends the splat
-            red[0 * DRED_STRIDE + lane] = s1; red[1 * DRED_STRIDE + lane] = s2; red[2 * DRED_STRIDE + lane] = s3;
-            red[3 * DRED_STRIDE + lane] = s4; red[4 * DRED_STRIDE + lane] = s5; red[5 * DRED_STRIDE + lane] = s6;
-            red[6 * DRED_STRIDE + lane] = s7;
-            __builtin_amdgcn_wave_barrier();
-            float sel = 0.f;
-            if (red_lane) {
-                const float4 p0 = red_rd[0], p1 = red_rd[1], p2 = red_rd[2], p3 = red_rd[3];
-                sel = ((p0.x + p0.y) + (p0.z + p0.w)) + ((p1.x + p1.y) + (p1.z + p1.w)) +
-                      (((p2.x + p2.y) + (p2.z + p2.w)) + ((p3.x + p3.y) + (p3.z + p3.w)));
-            }
-            __builtin_amdgcn_wave_barrier();
-            sel = dpp_add<0xB1>(sel);   // quad_perm [1,0,3,2]
-            sel = dpp_add<0x4E>(sel);   // quad_perm [2,3,0,1]
+            const float sums[DEPTH_NSUM] = {s1, s2, s3, s4, s5, s6, s7};
+            const float sel = reduce_rows(red, red_rd, red_lane, lane, sums);
             if (slot >= 0) atomicAdd(a.acc + GSR_ACC_FLOATS * (size_t)row + slot, sel);
         }
     }

@@ -619,10 +619,10 @@ static void bwd_plan(Call &c, Reverse &r) {      // which of the three reverse c
     r.persistent = c.pl.persistent_bwd && r.R > 0;
     // the written-out reverse walk addresses the accumulator rows with a 32-bit byte offset: rows < 2^26
     r.bwd_asm = c.o.asm_walk && !r.det && (!r.counters || c.o.count_lanes == 2) && acc_rows(c.P) < (1u << 26) ? 1 : 0;
-    r.pk_grid = r.persistent ? composite_bwd_persistent_grid(c.pl.T, r.det ? 1 : 0, r.counters ? c.o.count_lanes : 0, r.bwd_asm) : 0;
     // large images: half tiles in order of decreasing length (the forward pass filed the lengths when it ran with the same options)
     r.lpt = c.pl.lpt_span && !r.persistent && r.bwd_asm && !r.counters && r.R > 0 && c.o.wpb == 1;
     r.fill_chunk = r.persistent && c.o.fill_in_tail ? seg_fill_chunk(c.P) : 0;       // zero-fill units in the persistent kernel's lists
+    r.pk_grid = r.persistent ? composite_bwd_persistent_grid(c.pl.T, r.det ? 1 : 0, count_variant(r.counters, c.o.count_lanes), r.bwd_asm, r.fill_chunk) : 0;
     r.pa.rec = c.g.rec; r.pa.clamped = c.g.clamped; r.pa.opac = c.g.opac; r.pa.hot = c.g.hot; r.pa.touched = c.g.touched; r.pa.touch_mark = c.g.touch_mark;
     r.pa.skip_unmarked = r.fill_chunk > 0 && r.R > 0 ? 1 : 0; r.pa.dense = 0;
     r.pa.vis_count = nullptr; r.pa.vis_list = nullptr; r.pa.vis_rec = nullptr; r.pa.vis_cap = 0;
@@ -691,7 +691,7 @@ static int32_t bwd_composite(Call &c, const Reverse &r, const float *bg, const f
     ca.fill.scales = a.scales ? a.dL_dscales : nullptr; ca.fill.rots = a.scales ? a.dL_drots : nullptr;
     if (r.persistent) HIP_TRY(launch_composite_bwd_persistent(ca, r.pk_grid, c.s), "composite backward launch");
     else if (r.lpt) HIP_TRY(launch_composite_bwd_lpt(ca, c.s), "composite backward launch");
-    else HIP_TRY(launch_composite_bwd(ca, c.o.bwd_npx, c.o.exact_cull, c.o.wpb, c.s), "composite backward launch");
+    else HIP_TRY(launch_composite_bwd(ca, c.o.bwd_npx, c.o.wpb, c.s), "composite backward launch");
     return c.debug ? hip_rc(hipStreamSynchronize(c.s), "composite backward") : GSR_OK;
 }
 static int32_t bwd_pergauss(Call &c, Reverse &r) {      // joins the second stream in front of the per-Gaussian stage

@@ -55,6 +55,10 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     for (int m = 32; m > 0; m >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m));
     return v;
 }
+// signed: m = the largest m of the wave, in place.  A statement, not a function: through a function's parameter the compositing kernels
+// come out with another instruction order (the value is then known to be defined, and the lane arithmetic of the shuffles is hoisted
+// above the load it follows today) -- scripts/isa_diff.py
+#define GSR_WAVE_MAX_I32(m) _Pragma("unroll") for (int sft_ = 32; sft_ > 0; sft_ >>= 1) (m) = max((m), __shfl_xor((m), sft_))
 __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {

@@ -773,6 +773,51 @@ def test_forward_walkers_agree(kw):
             assert grad_err(v, gb["grads"][k]) <= 2e-4, k
 
 
+@pytest.mark.parametrize("asm_walk,persistent_bwd,pair_long", [(1, 0, 0), (1, 1, 0), (0, 0, 0), (0, 1, 0), (1, 1, 64)])
+def test_wave_timeline_kernels_agree_with_the_plain_ones(asm_walk, persistent_bwd, pair_long):
+    """`count_lanes = 2` launches instantiations of their own -- the written-out walks and the pair kernel with COUNT = 2, the C++
+    forms <.., 2, false> -- which record one timeline entry per wave and otherwise run the plain kernels' code.  Under the same
+    options colour, final transmittance and last contributor must equal the plain kernels' bit for bit, the gradients within the
+    order of addition of the float atomics (the bound of test_forward_walkers_agree), and both passes must have filed waves that
+    staged something."""
+    from gaussian_transformer_amd import _lib
+    sc = synth.make_scene(P=3000, width=160, height=112, sh_degree=3, s0=0.03, seed=0)      # 70 tiles, lists longer than one staging batch
+    S = oracle_scene(sc)
+    lib = _lib.load()
+
+    def read_trace(which):
+        buf = np.zeros((4096, 4), dtype=np.uint32)
+        _lib.check(lib.gsr_debug_read_wave_trace(which, buf.ctypes.data_as(C.c_void_p), 4096), "read trace")
+        return buf
+    try:
+        _lib.set_option("asm_walk", asm_walk)
+        _lib.set_option("persistent_bwd", persistent_bwd)
+        _lib.set_option("fwd_pair_long", pair_long)
+        a = _stage_dump(S)
+        ga = hip_forward_backward(S, sc.dL_dimage)
+        _lib.set_option("count_lanes", 2)
+        b = _stage_dump(S)
+        for which in (0, 1):
+            read_trace(which)                     # reading clears: what follows is this call's alone
+        gb = hip_forward_backward(S, sc.dL_dimage)
+        traces = [read_trace(0), read_trace(1)]
+    finally:
+        _lib.set_option("count_lanes", 0)
+        _lib.set_option("fwd_pair_long", -1)
+        _lib.set_option("persistent_bwd", 2)
+        _lib.set_option("asm_walk", 1)
+    assert a["n"] == b["n"] and a["n"] > 0
+    assert (a["ranges"][:, 1] - a["ranges"][:, 0]).max() > 64
+    for k in ("color", "final_T", "n_contrib"):
+        assert np.array_equal(a[k], b[k]), k
+    assert np.array_equal(ga["color"], gb["color"])
+    for k, v in ga["grads"].items():
+        if v is not None:
+            assert grad_err(v, gb["grads"][k]) <= 2e-4, k
+    for which, t in enumerate(traces):
+        assert ((t[:, 1] != 0) & (t[:, 2] > 0)).any(), which
+
+
 @pytest.mark.parametrize("kw", [
     dict(P=3000, width=160, height=112, sh_degree=3, s0=0.03, seed=0),
     dict(P=20001, width=250, height=131, sh_degree=1, max_sh_degree=3, s0=0.05, seed=7),    # P not a multiple of 4: unaligned tensor tails in the zero-fill
