@@ -142,6 +142,17 @@ DEPTH_SIGNATURES = {
                                   _p, _p, _p, _p, _p, _p]),                              # dL_d{means2D opacity means3D cov3D scales rots}
 }
 
+# include/gsr_pose.h (likewise a table of its own)
+POSE_COLOR, POSE_DEPTH_EXPECTED, POSE_DEPTH_INVERSE = 0, 1, 2
+POSE_SIGNATURES = {
+    "gsr_pose_workspace_bytes": (_i32, [_i32, C.POINTER(_sz)]),                          # P bytes
+    "gsr_pose_backward": (_i32, [_p, _i32, _i32, _i32, _i32, _i32, _i32, C.c_int64,      # stream kind P D M W H R
+                                 _p, _p, _p, _p, _p, _f, _p, _p,                         # means3D radii shs colors scales mod rotations cov3D
+                                 _p, _p, _p, _f, _f,                                     # view proj campos tanfovx tanfovy
+                                 _p, _sz, _p, _sz, _p, _sz,                              # geom acc ws (+bytes)
+                                 _p, _p, _p]),                                           # dL_d{viewmatrix projmatrix campos}
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -169,7 +180,7 @@ def load() -> C.CDLL:
         except OSError as e:
             raise GsrError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES, **SEQUENCE_SIGNATURES, **ROWS_SIGNATURES, **DENSITY_SIGNATURES,
-                                   **DEPTH_SIGNATURES}.items():
+                                   **DEPTH_SIGNATURES, **POSE_SIGNATURES}.items():
             fn = getattr(lib, name)       # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

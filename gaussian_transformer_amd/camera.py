@@ -91,6 +91,34 @@ def make_camera(R, t, fovx: float, fovy: float, width: int, height: int,
     return CameraMatrices(int(width), int(height), float(fovx), float(fovy), wvt, proj, full, center)
 
 
+class TorchPoseCamera:
+    """What render() reads from a camera, as differentiable torch functions of a pose (torch_camera below)."""
+
+    def __init__(self, width, height, fovx, fovy, wvt, full, center):
+        self.image_width, self.image_height = int(width), int(height)
+        self.FoVx, self.FoVy = float(fovx), float(fovy)
+        self.world_view_transform, self.full_proj_transform, self.camera_center = wvt, full, center
+
+
+def torch_camera(w2c, fovx: float, fovy: float, width: int, height: int, znear: float = ZNEAR, zfar: float = ZFAR) -> TorchPoseCamera:
+    """Camera for render() whose three tensors are differentiable torch functions of `w2c`, the [4,4] world-to-camera matrix
+    (column-vector convention, rigid: rotation | translation, what world_to_view returns) as a float32 torch tensor on any device;
+    a numpy pose is converted.  With a camera tensor that requires grad, GaussianRasterizer hands back dL/dviewmatrix, dL/dprojmatrix
+    and dL/dcampos, and autograd carries them on to the pose: pose refinement, tracking.
+    The products are make_camera's -- world_view_transform = w2c^T, full_proj_transform = w2c^T @ P^T in float32 -- and the centre is
+    the closed form of a rigid transform, -R^T t: no linalg.inv on the device."""
+    import torch
+    if not isinstance(w2c, torch.Tensor):
+        w2c = torch.tensor(np.asarray(w2c, dtype=np.float32))
+    if w2c.shape != (4, 4):
+        raise ValueError(f"w2c must be [4,4], got {tuple(w2c.shape)}")
+    proj_t = torch.tensor(projection_matrix(znear, zfar, fovx, fovy).T.copy(), dtype=w2c.dtype, device=w2c.device)
+    wvt = w2c.t()
+    full = wvt @ proj_t
+    center = -(w2c[:3, 3] @ w2c[:3, :3])
+    return TorchPoseCamera(width, height, fovx, fovy, wvt, full, center)
+
+
 def look_at_camera(eye, target, up, fovx: float, width: int, height: int) -> CameraMatrices:
     """Synthetic pose helper (no reference counterpart: images.bin is missing).
 

@@ -206,7 +206,9 @@ class HipBackend:
         return int(n.value), color, radii, geom, binning, img
 
     def backward(self, rs, num_rendered, dL_dpix, means3D, radii, shs, colors_precomp, scales, rotations,
-                 cov3D_precomp, geom, binning, img, shs_rest=None, raw_params=False):
+                 cov3D_precomp, geom, binning, img, shs_rest=None, raw_params=False, return_ws=False):
+        """return_ws: the workspace tensor this call allocated is returned as one more element, so that the caller can keep it alive
+        and hand it to pose_backward (include/gsr_pose.h: its accumulator rows, unmodified, on the same stream)."""
         dev = means3D.device
         P, H, W = int(means3D.shape[0]), int(rs.image_height), int(rs.image_width)
         M = int(shs.shape[1]) if shs.numel() else 0
@@ -244,9 +246,10 @@ class HipBackend:
                 _ptr(g_sh_rest))
             del ann
             _lib.check(rc, "gsr_backward")
+        out = (g_means3D, g_means2D, g_sh, g_colors, g_opacity, g_scales, g_rots, g_cov3D)
         if shs_rest is not None:
-            return g_means3D, g_means2D, g_sh, g_colors, g_opacity, g_scales, g_rots, g_cov3D, g_sh_rest
-        return g_means3D, g_means2D, g_sh, g_colors, g_opacity, g_scales, g_rots, g_cov3D
+            out = out + (g_sh_rest,)
+        return out + (bwd_ws,) if return_ws else out
 
     def depth_forward(self, rs, P, num_rendered, mode, geom, binning, img):
         """(depth, alpha), [H,W] each, of the render whose gsr_forward filled the three workspaces (include/gsr_depth.h)."""
@@ -269,11 +272,12 @@ class HipBackend:
         return ann is not None and ann[0] == geom.data_ptr() and ann[4] is not None
 
     def depth_backward(self, rs, num_rendered, mode, dL_ddepth, dL_dalpha, means3D, radii, scales, rotations, cov3D_precomp,
-                       geom, binning, img, into=None, sh_floats=0):
+                       geom, binning, img, into=None, sh_floats=0, return_ws=False):
         """Gradients of the depth and alpha maps (include/gsr_depth.h).  into = None: new tensors (slices of the gradient arena when one
         is set; the arena's SH slice, sh_floats = 3 M per Gaussian, is then zeroed: the maps have no SH gradient), accumulate = 0.
         into = (g_means3D, g_means2D, g_opacity, g_scales, g_rots, g_cov3D) as HipBackend.backward of the same render just wrote
-        them: added to, accumulate = 1.  Returns that tuple."""
+        them: added to, accumulate = 1.  Returns that tuple; with return_ws, followed by the workspace tensor this call allocated (for
+        pose_backward, as HipBackend.backward)."""
         dev = means3D.device
         P, H, W = int(means3D.shape[0]), int(rs.image_height), int(rs.image_width)
         has_sr, has_cov = scales.numel() > 0, cov3D_precomp.numel() > 0
@@ -306,7 +310,37 @@ class HipBackend:
                 _ptr(ws), ws.numel(), 0 if into is None else 1,
                 _ptr(g_means2D), _ptr(g_opacity), _ptr(g_means3D), _ptr(g_cov3D), _ptr(g_scales), _ptr(g_rots))
             _lib.check(rc, "gsr_depth_backward")
-        return g_means3D, g_means2D, g_opacity, g_scales, g_rots, g_cov3D
+        out = (g_means3D, g_means2D, g_opacity, g_scales, g_rots, g_cov3D)
+        return out + (ws,) if return_ws else out
+
+    def pose_backward(self, rs, kind, num_rendered, means3D, radii, shs, colors_precomp, scales, rotations, cov3D_precomp, geom, acc_ws,
+                      want=(True, True, True)):
+        """(dL/dviewmatrix [4,4], dL/dprojmatrix [4,4], dL/dcampos [3]) of the loss whose reverse pass -- backward() for kind 0,
+        depth_backward() for kind 1 (expected depth) or 2 (inverse depth) -- was given `acc_ws` and ran last on this stream
+        (include/gsr_pose.h).  want: which of the three are computed; the others are None (NULL to the library)."""
+        dev = means3D.device
+        P, H, W = int(means3D.shape[0]), int(rs.image_height), int(rs.image_width)
+        M = int(shs.shape[1]) if shs.numel() else 0
+        if not any(want):
+            return None, None, None
+        f32 = dict(dtype=torch.float32, device=dev)
+        g_view = torch.empty((4, 4), **f32) if want[0] else None
+        g_proj = torch.empty((4, 4), **f32) if want[1] else None
+        g_campos = torch.empty((3,), **f32) if want[2] else None
+        with torch.cuda.device(dev):
+            wsb = C.c_size_t()
+            _lib.check(self.lib.gsr_pose_workspace_bytes(P, C.byref(wsb)), "gsr_pose_workspace_bytes")
+            ws = torch.empty((wsb.value,), dtype=torch.uint8, device=dev)
+            vm = _f32c(rs.viewmatrix, "viewmatrix", dev); pm = _f32c(rs.projmatrix, "projmatrix", dev); cp = _f32c(rs.campos, "campos", dev)
+            colour = int(kind) == _lib.POSE_COLOR
+            rc = self.lib.gsr_pose_backward(
+                torch.cuda.current_stream(dev).cuda_stream, int(kind), P, int(rs.sh_degree), M, W, H, int(num_rendered),
+                _ptr(means3D), _ptr(radii), _ptr(shs) if colour else None, _ptr(colors_precomp) if colour else None,
+                _ptr(scales), float(rs.scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(vm), _ptr(pm), _ptr(cp),
+                float(rs.tanfovx), float(rs.tanfovy), _ptr(geom), geom.numel(), _ptr(acc_ws), acc_ws.numel(), _ptr(ws), ws.numel(),
+                _ptr(g_view), _ptr(g_proj), _ptr(g_campos))
+            _lib.check(rc, "gsr_pose_backward")
+        return g_view, g_proj, g_campos
 
     def composited_mask(self, geom, P):
         """bool [P]: the Gaussians the forward pass that filled `geom` composited at all (include/gsr.h gsr_composited_mask): a
@@ -538,6 +572,90 @@ class _RasterizeGaussiansDepth(torch.autograd.Function):
                 none_if_empty(g_scales, scales_c), none_if_empty(g_rots, rots_c), none_if_empty(g_cov, cov_c), None, None)
 
 
+class _RasterizeGaussiansPose(torch.autograd.Function):
+    """_RasterizeGaussians (mode None: (color, radii)) or _RasterizeGaussiansDepth (mode 0 / 1: (color, radii, depth, alpha)) with
+    the camera as tensor arguments: viewmatrix, projmatrix and campos receive gradients too (include/gsr_pose.h).  The forward call
+    is theirs -- announcement, arena, binning hint.  Backward runs their reverse passes, then gsr_pose_backward once per pass that
+    ran, on the workspace that pass just used; the colour and the map contributions are added in torch.  The Gaussians' gradients
+    are computed whether or not anybody asked for them: the camera gradient is made from the same accumulator rows."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos,
+                raster_settings, mode):
+        be = get_backend()
+        if not hasattr(be, "pose_backward") or (mode is not None and not hasattr(be, "depth_forward")):
+            raise _lib.GsrError(f"the {getattr(be, 'name', type(be).__name__)} backend has no camera gradients")
+        dev = means3D.device
+        if means3D.dim() != 2 or means3D.shape[1] != 3:
+            raise _lib.GsrError("means3D must have dimensions (num_points, 3)")
+        if viewmatrix.numel() != 16 or projmatrix.numel() != 16 or campos.numel() != 3:
+            raise _lib.GsrError("viewmatrix and projmatrix must have 16 elements and campos 3")
+        args = [_f32c(t, n, dev) for t, n in ((means3D, "means3D"), (sh, "shs"), (colors_precomp, "colors_precomp"),
+                                              (opacities, "opacities"), (scales, "scales"), (rotations, "rotations"),
+                                              (cov3Ds_precomp, "cov3D_precomp"))]
+        means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c = args
+        cam = [_f32c(t.detach(), n, dev) for t, n in ((viewmatrix, "viewmatrix"), (projmatrix, "projmatrix"), (campos, "campos"))]
+        rs = raster_settings._replace(viewmatrix=cam[0], projmatrix=cam[1], campos=cam[2])
+        num_rendered, color, radii, geom, binning, img = be.forward(
+            rs, means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c,
+            **({"announce_backward": True} if any(ctx.needs_input_grad) and hasattr(be, "_announced") else {}))
+        ctx.raster_settings, ctx.num_rendered, ctx.depth_mode = rs, num_rendered, mode
+        ctx.cam_like = [(tuple(t.shape), t.dtype, t.device) for t in (viewmatrix, projmatrix, campos)]
+        _remember_forward(geom, int(means3D_c.shape[0]))
+        ctx.save_for_backward(colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img)
+        ctx.gsr_geom_index, ctx.gsr_means_index = 7, 1
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        if mode is None:
+            return color, radii
+        depth, alpha = be.depth_forward(rs, int(means3D_c.shape[0]), num_rendered, mode, geom, binning, img)
+        return color, radii, depth.unsqueeze(0), alpha.unsqueeze(0)
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii, grad_depth=None, grad_alpha=None):
+        be = get_backend()
+        rs = ctx.raster_settings
+        colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img = ctx.saved_tensors
+        maps = grad_depth is not None or grad_alpha is not None
+        if grad_color is None and not maps and ctx.depth_mode is not None:
+            return (None,) * 13
+        want = tuple(ctx.needs_input_grad[8:11])
+        g_sh = g_colors = None
+        colour_used = grad_color is not None
+        if not colour_used and (ctx.depth_mode is None or (hasattr(be, "arena_fill_in_flight") and be.arena_fill_in_flight(geom))):
+            grad_color = torch.zeros((3, int(rs.image_height), int(rs.image_width)), dtype=torch.float32, device=means3D_c.device)
+        cams = []
+        if grad_color is not None:
+            g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov, ws = be.backward(
+                rs, ctx.num_rendered, grad_color, means3D_c, radii, sh_c, colors_c, scales_c, rots_c, cov_c, geom, binning, img,
+                return_ws=True)
+            if colour_used or not maps:
+                cams.append(be.pose_backward(rs, _lib.POSE_COLOR, ctx.num_rendered, means3D_c, radii, sh_c, colors_c, scales_c, rots_c,
+                                             cov_c, geom, ws, want=want))
+        if maps:
+            into = None if grad_color is None else (g_means3D, g_means2D, g_opac, g_scales, g_rots, g_cov)
+            g_means3D, g_means2D, g_opac, g_scales, g_rots, g_cov, ws = be.depth_backward(
+                rs, ctx.num_rendered, ctx.depth_mode, grad_depth, grad_alpha, means3D_c, radii, scales_c, rots_c, cov_c,
+                geom, binning, img, into=into, sh_floats=3 * int(sh_c.shape[1]) if sh_c.numel() else 0, return_ws=True)
+            kind = _lib.POSE_DEPTH_INVERSE if ctx.depth_mode == _lib.DEPTH_INVERSE else _lib.POSE_DEPTH_EXPECTED
+            cams.append(be.pose_backward(rs, kind, ctx.num_rendered, means3D_c, radii, sh_c, colors_c, scales_c, rots_c, cov_c, geom, ws,
+                                         want=want))
+        g_cam = []
+        for k, (shape, dtype, device) in enumerate(ctx.cam_like):      # in the input tensors' shapes and dtypes
+            parts = [c[k] for c in cams if c[k] is not None]
+            if not want[k] or not parts:
+                g_cam.append(None)
+                continue
+            g = parts[0] if len(parts) == 1 else parts[0] + parts[1]
+            g_cam.append(g.reshape(shape).to(device=device, dtype=dtype))
+        none_if_empty = lambda g, src: g if (g is not None and src.numel() > 0) else None
+        if not colour_used:
+            g_sh = g_colors = None          # the maps give the colour inputs no gradient
+        return (g_means3D, g_means2D, none_if_empty(g_sh, sh_c), none_if_empty(g_colors, colors_c), g_opac,
+                none_if_empty(g_scales, scales_c), none_if_empty(g_rots, rots_c), none_if_empty(g_cov, cov_c),
+                g_cam[0], g_cam[1], g_cam[2], None, None)
+
+
 class _RasterizeGaussiansFused(torch.autograd.Function):
     """Fused-step variant: takes the RAW parameters of scene/gaussian_model.py (xyz, features_dc,
     features_rest, opacity logits, log-scales, un-normalised quaternions); the activations (:33-41) and the
@@ -583,7 +701,8 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
 
 
 def rasterize_gaussians_fused(means3D, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, raster_settings):
-    """(color, radii) from the raw Gaussian parameters; gradients flow to the raw parameters."""
+    """(color, radii) from the raw Gaussian parameters; gradients flow to the raw parameters.  No camera gradient: the settings'
+    viewmatrix, projmatrix and campos are constants here even when they require grad (include/gsr_pose.h has no raw_params form)."""
     return _RasterizeGaussiansFused.apply(means3D, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
                                           rotation_raw, raster_settings)
 
@@ -604,7 +723,9 @@ class GaussianRasterizer(nn.Module):
                 cov3D_precomp=None, depth=None):
         """depth = None: (color, radii), the reference's call.  depth = "expected" or "inverse": (color, radii, depth, alpha) with
         depth [1,H,W] = sum z alpha T (or sum (1/z) alpha T), not normalised, no background term, and alpha [1,H,W] = 1 - T_final;
-        gradients flow from all three images."""
+        gradients flow from all three images.  When grad mode is on and viewmatrix, projmatrix or campos of the settings requires
+        grad, the camera receives gradients as well (_RasterizeGaussiansPose, include/gsr_pose.h); every other call goes where it
+        went before."""
         rs = self.raster_settings
         if depth is not None and depth not in DEPTH_MODES:
             raise _lib.GsrError(f"depth must be None, 'expected' or 'inverse', got {depth!r}")
@@ -619,6 +740,10 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
+        cam = (rs.viewmatrix, rs.projmatrix, rs.campos)
+        if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in cam):
+            return _RasterizeGaussiansPose.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                                 *cam, rs, None if depth is None else DEPTH_MODES[depth])
         if depth is not None:
             return _RasterizeGaussiansDepth.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs,
                                                   DEPTH_MODES[depth])

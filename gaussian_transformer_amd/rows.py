@@ -168,6 +168,8 @@ def render_rows(cameras, rows: torch.Tensor, pipe, bg: torch.Tensor, scaling_mod
     that order into dL/drows with one launch (flag columns +0.0): no per-parameter autograd nodes, and an order of summation that
     does not depend on the autograd engine.  Under torch.no_grad() (target and prompt renders) nothing is kept.
     Non-contiguous rows are copied once; the gradient still reaches the caller's tensor.
+    No camera gradient: the cameras' tensors are constants here even when they require grad (the raw-parameter path has none,
+    include/gsr_pose.h).
     `rasterizer.composited_mask()` without an argument refers to the LAST camera's render afterwards (while the images' graph is
     alive: a no_grad call keeps no workspace); composited_mask(image) does not know the images of this function and returns None."""
     who = "render_rows"

@@ -66,7 +66,8 @@ const char *gsr_last_error(void);
  *   img_bytes  : per-tile ranges + per-pixel final transmittance / last contributor
  *   bwd_bytes  : scratch used only inside gsr_backward (gradient accumulators: one 64-byte row per Gaussian plus
  *                P/32 + 1024 replica rows; behind them the dense per-Gaussian stage's list and record buffer, 4 P + 240 max(131072, P/4)
- *                bytes; no initialisation needed, gsr_backward clears what it uses) */
+ *                bytes; no initialisation needed, gsr_backward clears what it uses; contents irrelevant afterwards, except to
+ *                gsr_pose_backward of gsr_pose.h, which reads the accumulator rows of the call it follows) */
 int32_t gsr_workspace_sizes(int32_t P, int32_t W, int32_t H, size_t *geom_bytes, size_t *img_bytes, size_t *bwd_bytes);
 
 /* Size of gsr_backward's scratch workspace for a forward that rendered R pairs: the bwd_bytes of gsr_workspace_sizes,
