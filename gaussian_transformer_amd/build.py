@@ -49,7 +49,8 @@ SOURCES = {
     # as composite_bwd.hip, whose staging, replica rows and LDS reduction it shares (csrc/composite_common.h) under recurrences of its own
     # for the depth and alpha maps (include/gsr_depth.h): native float atomic add, no packed f32 pairs
     "depth_maps.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],
-    # as pergauss_bwd.hip, whose chain it restates up to the terms the camera gradient shares with dL/dmeans3D (include/gsr_pose.h)
+    # as pergauss_bwd.hip, whose chain (csrc/pergauss_chain.h) it calls up to the terms the camera gradient shares with dL/dmeans3D
+    # (include/gsr_pose.h)
     "pose_grad.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result", "-fno-gpu-rdc"]

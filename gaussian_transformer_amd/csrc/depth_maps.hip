@@ -34,6 +34,7 @@
 #include "composite_common.h"
 #include "gsr_host.h"
 #include "gsr_internal.h"
+#include "pergauss_chain.h"
 
 namespace gsr {
 namespace {
@@ -257,11 +258,7 @@ __global__ __launch_bounds__(256) void depth_finish_kernel(FinishArgs f) {
     const size_t si = (size_t)i;
     if (!(f.radii[si] > 0 && (uint32_t)f.touched[si] == *f.touch_mark)) return;
     float dv = f.acc[GSR_ACC_FLOATS * si + 9];
-    if (f.clamped[si] & 0x80u) {                        // replica rows (gsr_internal.h): their slot 9 is folded in
-        const uint32_t hot = f.hot[si];
-        const size_t first = (size_t)f.P + (hot >> 4);
-        for (uint32_t k = 0; k < (1u << (hot & 15u)); k++) dv += f.acc[GSR_ACC_FLOATS * (first + k) + 9];
-    }
+    if (f.clamped[si] & 0x80u) fold_replica_rows<9, false>(f.acc, f.P, f.hot[si], 0, nullptr, nullptr, true, dv);   // their slot 9 is folded in
     const float *m = f.viewmatrix;
     const float x = f.means3D[3 * si], y = f.means3D[3 * si + 1], z = f.means3D[3 * si + 2];
     const float zv = m[2] * x + m[6] * y + m[10] * z + m[14];

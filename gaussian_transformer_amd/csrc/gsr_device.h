@@ -380,6 +380,29 @@ __device__ __forceinline__ void load_sh_row(const float *__restrict__ shs, size_
     }
 }
 
+// load_sh_row for K = 1 and 9, where 3 K is no whole number of float4s: load_sh_row then reads one float beyond the 3 K in its
+// 16-byte form only, and the compiler keeps an array defined differently by the two forms in scratch (16 bytes of private segment).
+// The same loads, cut at 3 K: whole float4s, then single floats.  pose_grad.hip uses it; preprocess.hip and pergauss_bwd.hip do not
+// yet (private = 16 in their <0, *, false> and <2, *, false> kernels): DESIGN.md 7, open.
+template <int K>
+__device__ __forceinline__ void load_sh_row_exact(const float *__restrict__ shs, size_t i, int M, float c[3 * K + 3]) {
+    const float *row = shs + i * (size_t)M * 3;
+    constexpr int NV = (3 * K) / 4;
+    if (((M * 3) & 3) == 0 && ((reinterpret_cast<uintptr_t>(shs) & 15) == 0)) {
+        const float4 *r4 = reinterpret_cast<const float4 *>(row);
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+            const float4 t = r4[v];
+            c[4 * v] = t.x; c[4 * v + 1] = t.y; c[4 * v + 2] = t.z; c[4 * v + 3] = t.w;
+        }
+#pragma unroll
+        for (int v = 4 * NV; v < 3 * K; v++) c[v] = row[v];
+    } else {
+#pragma unroll
+        for (int v = 0; v < 3 * K; v++) c[v] = row[v];
+    }
+}
+
 // SH row given as two tensors, as the reference stores them (scene/gaussian_model.py:108-111):
 // dc [P,1,3] holds coefficient 0, rest [P,M-1,3] holds coefficients 1..M-1.  Avoids the torch.cat.
 template <int K>

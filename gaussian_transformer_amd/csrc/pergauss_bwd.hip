@@ -6,8 +6,8 @@
 // HBM-streaming: reads 64 (accumulator row) + 44 + 12*K bytes, writes 64 + 12*M bytes per
 // Gaussian.  Compiled with -ffp-contract=off to track oracle/gsr_ref.c.
 #include <atomic>
-#include "gsr_device.h"
-#include "gsr_internal.h"
+#include "gsr_host.h"
+#include "pergauss_chain.h"
 
 namespace gsr {
 
@@ -77,14 +77,7 @@ __device__ __forceinline__ void pergauss_one(const PergaussBwdArgs &a, const int
             }
         } else {
             p[0] = a.means3D[3 * si]; p[1] = a.means3D[3 * si + 1]; p[2] = a.means3D[3 * si + 2];
-            if (a.cov3D_precomp) {
-#pragma unroll
-                for (int k = 0; k < 6; k++) c6[k] = a.cov3D_precomp[6 * si + k];
-            } else {
-                s[0] = a.scales[3 * si]; s[1] = a.scales[3 * si + 1]; s[2] = a.scales[3 * si + 2];
-                const float4 q4 = reinterpret_cast<const float4 *>(a.rotations)[si];
-                q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
-            }
+            GSR_LOAD_COV_INPUTS(a, si, c6, s, q)
             opac = a.opac[si];
             if (a.shs) {
                 if (SPLIT) load_sh_row_split<K>(a.shs, a.shs_rest, si, a.M, c);
@@ -94,47 +87,22 @@ __device__ __forceinline__ void pergauss_one(const PergaussBwdArgs &a, const int
         // DENSE: few waves per SIMD, nobody covers a wave's memory latency: the accumulator row is requested here, with the record
         // (the compiler may not move a load across the barrier)
         if (DENSE) asm volatile("" ::: "memory");
-        if (cl & 0x80u) {                                     // a splat over hundreds of tiles: its waves added into replica rows
-            const uint32_t hot = a.hot[si];
-            const size_t first = (size_t)a.P + (hot >> 4);
-            for (uint32_t k = 0; k < (1u << (hot & 15u)); k++) {
-                const float4 *r4 = reinterpret_cast<const float4 *>(a.acc) + 4 * (first + k);
-                const float4 B0 = r4[0], B1 = r4[1];
-                A0.x += B0.x; A0.y += B0.y; A0.z += B0.z; A0.w += B0.w;
-                A1.x += B1.x; A1.y += B1.y; A1.z += B1.z; A1.w += B1.w;
-                A8 += a.acc[GSR_ACC_FLOATS * (first + k) + 8];
-            }
-        }
+        if (cl & 0x80u) fold_replica_rows<8, false>(a.acc, a.P, a.hot[si], 0, &A0, &A1, true, A8);
         dcol[0] = A0.x; dcol[1] = A0.y; dcol[2] = A0.z;
         float pv[3];
         xform4x3(a.viewmatrix, p, pv);
-        if (!a.cov3D_precomp) {
-            if (RAW) {
-                s[0] = expf(s[0]); s[1] = expf(s[1]); s[2] = expf(s[2]);
-                act_normalize4(q, q_inv_norm);
-            }
-            cov3d_from_scale_rot(s, a.scale_modifier, q, c6);
-        }
+        if (!a.cov3D_precomp) q_inv_norm = cov3d_activated<RAW>(s, q, a.scale_modifier, c6);
         // ---- S11 ----
         Ewa e;
         ewa_project(pv, c6, a.viewmatrix, a.tanfovx, a.tanfovy, a.W, a.H, e);
-        const float ea = e.a, eb = e.b, ec = e.c;
-        const float det = ea * ec - eb * eb;
-        // The compositing kernel (composite_bwd.hip) accumulates moments of s = opacity * G * dL/dalpha over the pixels:
-        // A0.w, A1.x = sum s*d;  A1.yzw = sum s * d d^T;  A8 = sum s.  The factors that are constant per Gaussian
-        // are applied here:
-        //   mean2D gradient w.r.t. NDC = -(W/2, H/2) * conic * sum s*d;   conic gradient = -1/2 * sum s * d d^T;
-        //   dL/dopacity = sum G * dL/dalpha = (sum s) / opacity   (a Gaussian that blends anywhere has opacity >= 1/255)
+        // A8 = sum s over the pixels (conic_moments): dL/dopacity = sum G * dL/dalpha = (sum s) / opacity   (a Gaussian that blends
+        // anywhere has opacity >= 1/255)
         dop = opac > 0.f ? A8 / opac : 0.f;
-        const float det_inv = 1.f / det;                        // the conic as the forward pass formed it (S4)
-        const float cA = ec * det_inv, cB = -eb * det_inv, cC = ea * det_inv;
-        dm2[0] = -0.5f * (float)a.W * (cA * A0.w + cB * A1.x); dm2[1] = -0.5f * (float)a.H * (cB * A0.w + cC * A1.x);
-        const float gA = -0.5f * A1.y, gB = -0.5f * A1.z, gC = -0.5f * A1.w;
-        const float d2inv = 1.f / (det * det + GSR_DENOM_EPS);
+        float det, gA, gB, gC, d2inv;
+        conic_moments(e, A0, A1, a.W, a.H, det, dm2, gA, gB, gC, d2inv);
         if (d2inv != 0.f) {
-            const float dL_da = d2inv * (-ec * ec * gA + 2.f * eb * ec * gB + (det - ea * ec) * gC);
-            const float dL_dc = d2inv * (-ea * ea * gC + 2.f * ea * eb * gB + (det - ea * ec) * gA);
-            const float dL_db = d2inv * 2.f * (eb * ec * gA - (det + 2.f * eb * eb) * gB + ea * eb * gC);
+            const Cov2dGrad d2 = cov2d_grad(e, det, d2inv, gA, gB, gC);
+            const float dL_da = d2.a, dL_db = d2.b, dL_dc = d2.c;
             const float(*Tm)[3] = e.T;
             dcov[0] = Tm[0][0] * Tm[0][0] * dL_da + Tm[0][0] * Tm[1][0] * dL_db + Tm[1][0] * Tm[1][0] * dL_dc;
             dcov[3] = Tm[0][1] * Tm[0][1] * dL_da + Tm[0][1] * Tm[1][1] * dL_db + Tm[1][1] * Tm[1][1] * dL_dc;
@@ -142,30 +110,15 @@ __device__ __forceinline__ void pergauss_one(const PergaussBwdArgs &a, const int
             dcov[1] = 2.f * Tm[0][0] * Tm[0][1] * dL_da + (Tm[0][0] * Tm[1][1] + Tm[0][1] * Tm[1][0]) * dL_db + 2.f * Tm[1][0] * Tm[1][1] * dL_dc;
             dcov[2] = 2.f * Tm[0][0] * Tm[0][2] * dL_da + (Tm[0][0] * Tm[1][2] + Tm[0][2] * Tm[1][0]) * dL_db + 2.f * Tm[1][0] * Tm[1][2] * dL_dc;
             dcov[4] = 2.f * Tm[0][2] * Tm[0][1] * dL_da + (Tm[0][1] * Tm[1][2] + Tm[0][2] * Tm[1][1]) * dL_db + 2.f * Tm[1][1] * Tm[1][2] * dL_dc;
-            float dT[2][3];
+            float dT[2][3], dt[3];
+            ewa_T_grad(e, dL_da, dL_db, dL_dc, dT, dt);
 #pragma unroll
-            for (int k = 0; k < 3; k++) {
-                dT[0][k] = 2.f * dL_da * e.TS[0][k] + dL_db * e.TS[1][k];
-                dT[1][k] = dL_db * e.TS[0][k] + 2.f * dL_dc * e.TS[1][k];
-            }
-            float dJ00 = 0.f, dJ02 = 0.f, dJ11 = 0.f, dJ12 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                dJ00 += dT[0][k] * e.Wm[0][k]; dJ02 += dT[0][k] * e.Wm[2][k];
-                dJ11 += dT[1][k] * e.Wm[1][k]; dJ12 += dT[1][k] * e.Wm[2][k];
-            }
-            const float tz = 1.f / e.t[2], tz2 = tz * tz, tz3 = tz2 * tz;
-            const float dtx = (e.clampx ? 0.f : 1.f) * (-e.fx * tz2 * dJ02);
-            const float dty = (e.clampy ? 0.f : 1.f) * (-e.fy * tz2 * dJ12);
-            const float dtz = -e.fx * tz2 * dJ00 - e.fy * tz2 * dJ11 + 2.f * e.fx * e.t[0] * tz3 * dJ02 + 2.f * e.fy * e.t[1] * tz3 * dJ12;
-#pragma unroll
-            for (int k = 0; k < 3; k++) dmean[k] += e.Wm[0][k] * dtx + e.Wm[1][k] * dty + e.Wm[2][k] * dtz;
+            for (int k = 0; k < 3; k++) dmean[k] += e.Wm[0][k] * dt[0] + e.Wm[1][k] * dt[1] + e.Wm[2][k] * dt[2];
         }
         // ---- S12a ----
         {
             float ph[4];
-            xform4x4(a.projmatrix, p, ph);
-            const float mw = 1.f / (ph[3] + GSR_W_EPS);
+            const float mw = persp_divide(a.projmatrix, p, ph);
             const float mul1 = ph[0] * mw * mw, mul2 = ph[1] * mw * mw;
             const float *Pm = a.projmatrix;
 #pragma unroll
@@ -174,23 +127,11 @@ __device__ __forceinline__ void pergauss_one(const PergaussBwdArgs &a, const int
         }
         // ---- S12b ----
         if (a.shs) {
-            const float v[3] = {p[0] - a.campos[0], p[1] - a.campos[1], p[2] - a.campos[2]};
-            const float len2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], il = 1.f / sqrtf(len2);
-            const float dir[3] = {v[0] * il, v[1] * il, v[2] * il};
-            float bas[16], bg3[16][3];
+            float dir[3], bas[16];
+            const float il = view_dir(p, a.campos, dir);
             sh_basis<D>(dir, bas);
-            sh_basis_grad<D>(dir, bg3);
-            float ddir[3] = {0.f, 0.f, 0.f};
+            GSR_SH_DIR_GRAD(D, c, cl, dcol, dir, gch, ddir);
             float *out = (SPLIT) ? nullptr : a.dL_dsh + si * (size_t)a.M * 3;
-            float gch[3];
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) gch[ch] = ((cl >> ch) & 1) ? 0.f : dcol[ch];
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++)
-#pragma unroll
-                for (int k = 0; k < K; k++)
-#pragma unroll
-                    for (int ax = 0; ax < 3; ax++) ddir[ax] += bg3[k][ax] * c[k * 3 + ch] * gch[ch];
             if (!(SPLIT) && tile_path) {
                 float row[48];
 #pragma unroll
@@ -215,9 +156,10 @@ __device__ __forceinline__ void pergauss_one(const PergaussBwdArgs &a, const int
                 }
                 for (int k = 3 * (K - 1); k < 3 * (a.M - 1); k++) orest[k] = 0.f;
             }
-            const float dot = dir[0] * ddir[0] + dir[1] * ddir[1] + dir[2] * ddir[2];
+            float g[3];
+            sh_dir_project(dir, ddir, il, g);
 #pragma unroll
-            for (int ax = 0; ax < 3; ax++) dmean[ax] += (ddir[ax] - dir[ax] * dot) * il;
+            for (int ax = 0; ax < 3; ax++) dmean[ax] += g[ax];
         }
         // ---- S13 ----
         if (!a.cov3D_precomp) {
@@ -495,12 +437,12 @@ hipError_t launch_pergauss_bwd(const PergaussBwdArgs &a_in, hipStream_t s) {
         (void)hipGetDevice(&dev);
         if (!(attr_set.load() & (1ull << (dev & 63)))) {
             hipError_t e = hipSuccess;
-            const void *fns[] = {(const void *)pergauss_bwd_kernel<0, false, false>, (const void *)pergauss_bwd_kernel<1, false, false>,
-                                 (const void *)pergauss_bwd_kernel<2, false, false>, (const void *)pergauss_bwd_kernel<3, false, false>,
-                                 (const void *)pergauss_bwd_kernel<0, true, false>, (const void *)pergauss_bwd_kernel<1, true, false>,
-                                 (const void *)pergauss_bwd_kernel<2, true, false>, (const void *)pergauss_bwd_kernel<3, true, false>};
-            for (const void *f : fns)
-                if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            for (int dd = 0; dd < 4; dd++)                   // every instantiation that can take the tile: not split
+                for (int r = 0; r < 2; r++)
+                    with_sh_degree(dd, [&](auto D) { with_flag(r != 0, [&](auto RAW) {
+                        const void *f = (const void *)pergauss_bwd_kernel<decltype(D)::value, decltype(RAW)::value, false>;
+                        if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                    }); });
             if (e != hipSuccess) return e;
             attr_set.fetch_or(1ull << (dev & 63));
         }
@@ -508,32 +450,14 @@ hipError_t launch_pergauss_bwd(const PergaussBwdArgs &a_in, hipStream_t s) {
     if (a.dense) {                                    // gsr_backward checked: SH tensor with M = 16, scales + rotations, not split
         const dim3 dgrid((a.P + 63) / 64), dblock(64);
         const size_t dlds = lds / 4;                 // one wave's tile
-        switch (d * 2 + (raw ? 1 : 0)) {
-            case 0: hipLaunchKernelGGL((pergauss_bwd_dense_kernel<0, false>), dgrid, dblock, dlds, s, a); break;
-            case 1: hipLaunchKernelGGL((pergauss_bwd_dense_kernel<0, true>), dgrid, dblock, dlds, s, a); break;
-            case 2: hipLaunchKernelGGL((pergauss_bwd_dense_kernel<1, false>), dgrid, dblock, dlds, s, a); break;
-            case 3: hipLaunchKernelGGL((pergauss_bwd_dense_kernel<1, true>), dgrid, dblock, dlds, s, a); break;
-            case 4: hipLaunchKernelGGL((pergauss_bwd_dense_kernel<2, false>), dgrid, dblock, dlds, s, a); break;
-            case 5: hipLaunchKernelGGL((pergauss_bwd_dense_kernel<2, true>), dgrid, dblock, dlds, s, a); break;
-            case 6: hipLaunchKernelGGL((pergauss_bwd_dense_kernel<3, false>), dgrid, dblock, dlds, s, a); break;
-            default: hipLaunchKernelGGL((pergauss_bwd_dense_kernel<3, true>), dgrid, dblock, dlds, s, a); break;
-        }
+        with_sh_degree(d, [&](auto D) { with_flag(raw, [&](auto RAW) {
+            hipLaunchKernelGGL((pergauss_bwd_dense_kernel<decltype(D)::value, decltype(RAW)::value>), dgrid, dblock, dlds, s, a);
+        }); });
         return hipGetLastError();
     }
-#define GSR_LAUNCH(DD)                                                                                   \
-    do {                                                                                                 \
-        if (!raw && !split) hipLaunchKernelGGL((pergauss_bwd_kernel<DD, false, false>), grid, block, lds, s, a);           \
-        else if (raw && !split) hipLaunchKernelGGL((pergauss_bwd_kernel<DD, true, false>), grid, block, lds, s, a);        \
-        else if (!raw && split) hipLaunchKernelGGL((pergauss_bwd_kernel<DD, false, true>), grid, block, 0, s, a);        \
-        else hipLaunchKernelGGL((pergauss_bwd_kernel<DD, true, true>), grid, block, 0, s, a);                            \
-    } while (0)
-    switch (d) {
-        case 0: GSR_LAUNCH(0); break;
-        case 1: GSR_LAUNCH(1); break;
-        case 2: GSR_LAUNCH(2); break;
-        default: GSR_LAUNCH(3); break;
-    }
-#undef GSR_LAUNCH
+    with_sh_degree(d, [&](auto D) { with_flag(raw, [&](auto RAW) { with_flag(split, [&](auto SPLIT) {       // split: lds is 0
+        hipLaunchKernelGGL((pergauss_bwd_kernel<decltype(D)::value, decltype(RAW)::value, decltype(SPLIT)::value>), grid, block, lds, s, a);
+    }); }); });
     return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // pose_grad.hip -- camera gradients of a render (include/gsr_pose.h): dL/dviewmatrix, dL/dprojmatrix, dL/dcampos; kernels and entry points.
 //
 // Built beside the reverse passes, which it does not touch: it reads the accumulator rows gsr_backward or gsr_depth_backward left at the
-// start of their workspace and restates pergauss_bwd.hip's chain (S11, S12a, S12b) on the same gsr_device.h helpers, with the same flags
+// start of their workspace and calls pergauss_bwd.hip's chain (S11, S12a, S12b: the stages of pergauss_chain.h), with the same flags
 // (-ffp-contract=off -fno-slp-vectorize), up to the intermediate terms that reach dL/dmeans3D there: the same terms times the camera-side
 // factors are the camera gradient.  Nothing per Gaussian is written: 27 sums over P Gaussians leave as 35 floats.
 //
@@ -18,9 +18,8 @@
 #include <string.h>
 
 #include "../../include/gsr_pose.h"
-#include "gsr_device.h"
 #include "gsr_host.h"
-#include "gsr_internal.h"
+#include "pergauss_chain.h"
 
 namespace gsr {
 namespace {
@@ -45,28 +44,6 @@ __device__ __forceinline__ double wave_tree_sum(double v) {
 #pragma unroll
     for (int sft = 32; sft > 0; sft >>= 1) v += __shfl_xor(v, sft);
     return v;
-}
-
-// load_sh_row for K = 1 and 9, where 3 K is no whole number of float4s: gsr_device.h's loader then reads one float beyond the 3 K in its
-// 16-byte form only, and this kernel's compiler keeps an array defined differently by the two forms in scratch (16 bytes of private
-// segment).  The same loads, cut at 3 K: whole float4s, then single floats.
-template <int K>
-__device__ __forceinline__ void load_sh_row_exact(const float *__restrict__ shs, size_t i, int M, float c[3 * K + 3]) {
-    const float *row = shs + i * (size_t)M * 3;
-    constexpr int NV = (3 * K) / 4;
-    if (((M * 3) & 3) == 0 && ((reinterpret_cast<uintptr_t>(shs) & 15) == 0)) {
-        const float4 *r4 = reinterpret_cast<const float4 *>(row);
-#pragma unroll
-        for (int v = 0; v < NV; v++) {
-            const float4 t = r4[v];
-            c[4 * v] = t.x; c[4 * v + 1] = t.y; c[4 * v + 2] = t.z; c[4 * v + 3] = t.w;
-        }
-#pragma unroll
-        for (int v = 4 * NV; v < 3 * K; v++) c[v] = row[v];
-    } else {
-#pragma unroll
-        for (int v = 0; v < 3 * K; v++) c[v] = row[v];
-    }
 }
 
 // the four waves' totals -> out[0..31] (zeros behind the live sums); `part` is the workgroup's LDS
@@ -113,64 +90,24 @@ __global__ __launch_bounds__(256) void pose_terms_kernel(PoseArgs a) {
         float A9 = a.kind != GSR_POSE_COLOR ? a.acc[GSR_ACC_FLOATS * si + 9] : 0.f;
         float p[3], c6[6], s[3] = {0.f, 0.f, 0.f}, q[4] = {1.f, 0.f, 0.f, 0.f}, c[3 * K + 3];
         p[0] = a.means3D[3 * si]; p[1] = a.means3D[3 * si + 1]; p[2] = a.means3D[3 * si + 2];
-        if (a.cov3D_precomp) {
-#pragma unroll
-            for (int k = 0; k < 6; k++) c6[k] = a.cov3D_precomp[6 * si + k];
-        } else {
-            s[0] = a.scales[3 * si]; s[1] = a.scales[3 * si + 1]; s[2] = a.scales[3 * si + 2];
-            const float4 q4 = reinterpret_cast<const float4 *>(a.rotations)[si];
-            q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
-        }
+        GSR_LOAD_COV_INPUTS(a, si, c6, s, q)
         if (SH) {
             if constexpr ((3 * K) % 4 == 0) load_sh_row<K>(a.shs, si, a.M, c);
             else load_sh_row_exact<K>(a.shs, si, a.M, c);
         }
-        if (cl & 0x80u) {                                 // replica rows, folded as pergauss_one folds them
-            const uint32_t hot = a.hot[si];
-            const size_t first = (size_t)a.P + (hot >> 4);
-            for (uint32_t k = 0; k < (1u << (hot & 15u)); k++) {
-                if (first + k >= a.acc_rows) break;       // a code can only name rows of the workspace: nothing beyond it is read
-                const float4 *r4 = reinterpret_cast<const float4 *>(a.acc) + 4 * (first + k);
-                const float4 B0 = r4[0], B1 = r4[1];
-                A0.x += B0.x; A0.y += B0.y; A0.z += B0.z; A0.w += B0.w;
-                A1.x += B1.x; A1.y += B1.y; A1.z += B1.z; A1.w += B1.w;
-                if (a.kind != GSR_POSE_COLOR) A9 += a.acc[GSR_ACC_FLOATS * (first + k) + 9];
-            }
-        }
+        if (cl & 0x80u) fold_replica_rows<9, true>(a.acc, a.P, a.hot[si], a.acc_rows, &A0, &A1, a.kind != GSR_POSE_COLOR, A9);
         float pv[3];
         xform4x3(a.viewmatrix, p, pv);
-        if (!a.cov3D_precomp) cov3d_from_scale_rot(s, a.scale_modifier, q, c6);
+        if (!a.cov3D_precomp) cov3d_activated<false>(s, q, a.scale_modifier, c6);
         // ---- S11: conic -> 2D covariance -> T = J Wm and t = Wm p + translation ----
         Ewa e;
         ewa_project(pv, c6, a.viewmatrix, a.tanfovx, a.tanfovy, a.W, a.H, e);
-        const float ea = e.a, eb = e.b, ec = e.c;
-        const float det = ea * ec - eb * eb;
-        const float det_inv = 1.f / det;
-        const float cA = ec * det_inv, cB = -eb * det_inv, cC = ea * det_inv;
-        const float dm2[2] = {-0.5f * (float)a.W * (cA * A0.w + cB * A1.x), -0.5f * (float)a.H * (cB * A0.w + cC * A1.x)};
-        const float gA = -0.5f * A1.y, gB = -0.5f * A1.z, gC = -0.5f * A1.w;
-        const float d2inv = 1.f / (det * det + GSR_DENOM_EPS);
+        float det, dm2[2], gA, gB, gC, d2inv;
+        conic_moments(e, A0, A1, a.W, a.H, det, dm2, gA, gB, gC, d2inv);
         if (d2inv != 0.f) {
-            const float dL_da = d2inv * (-ec * ec * gA + 2.f * eb * ec * gB + (det - ea * ec) * gC);
-            const float dL_dc = d2inv * (-ea * ea * gC + 2.f * ea * eb * gB + (det - ea * ec) * gA);
-            const float dL_db = d2inv * 2.f * (eb * ec * gA - (det + 2.f * eb * eb) * gB + ea * eb * gC);
-            float dT[2][3];
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                dT[0][k] = 2.f * dL_da * e.TS[0][k] + dL_db * e.TS[1][k];
-                dT[1][k] = dL_db * e.TS[0][k] + 2.f * dL_dc * e.TS[1][k];
-            }
-            float dJ00 = 0.f, dJ02 = 0.f, dJ11 = 0.f, dJ12 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                dJ00 += dT[0][k] * e.Wm[0][k]; dJ02 += dT[0][k] * e.Wm[2][k];
-                dJ11 += dT[1][k] * e.Wm[1][k]; dJ12 += dT[1][k] * e.Wm[2][k];
-            }
-            const float tz = 1.f / e.t[2], tz2 = tz * tz, tz3 = tz2 * tz;
-            float dt[3];
-            dt[0] = (e.clampx ? 0.f : 1.f) * (-e.fx * tz2 * dJ02);
-            dt[1] = (e.clampy ? 0.f : 1.f) * (-e.fy * tz2 * dJ12);
-            dt[2] = -e.fx * tz2 * dJ00 - e.fy * tz2 * dJ11 + 2.f * e.fx * e.t[0] * tz3 * dJ02 + 2.f * e.fy * e.t[1] * tz3 * dJ12;
+            const Cov2dGrad d2 = cov2d_grad(e, det, d2inv, gA, gB, gC);
+            float dT[2][3], dt[3];
+            ewa_T_grad(e, d2.a, d2.b, d2.c, dT, dt);
             // the Jacobian as ewa_project forms it (clamped t)
             const float J00 = e.fx / e.t[2], J02 = -(e.fx * e.t[0]) / (e.t[2] * e.t[2]);
             const float J11 = e.fy / e.t[2], J12 = -(e.fy * e.t[1]) / (e.t[2] * e.t[2]);
@@ -186,8 +123,7 @@ __global__ __launch_bounds__(256) void pose_terms_kernel(PoseArgs a) {
         // ---- S12a: NDC mean -> projmatrix ----
         {
             float ph[4];
-            xform4x4(a.projmatrix, p, ph);
-            const float mw = 1.f / (ph[3] + GSR_W_EPS);
+            const float mw = persp_divide(a.projmatrix, p, ph);
             const float g[3] = {dm2[0] * mw, dm2[1] * mw, -(dm2[0] * ph[0] + dm2[1] * ph[1]) * mw * mw};
 #pragma unroll
             for (int j = 0; j < 3; j++)
@@ -198,25 +134,13 @@ __global__ __launch_bounds__(256) void pose_terms_kernel(PoseArgs a) {
         }
         // ---- S12b: colour -> view direction -> campos ----
         if (SH) {
-            const float v[3] = {p[0] - a.campos[0], p[1] - a.campos[1], p[2] - a.campos[2]};
-            const float len2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], il = 1.f / sqrtf(len2);
-            const float dir[3] = {v[0] * il, v[1] * il, v[2] * il};
-            float bg3[16][3];
-            sh_basis_grad<D>(dir, bg3);
-            float ddir[3] = {0.f, 0.f, 0.f};
             const float dcol[3] = {A0.x, A0.y, A0.z};
-            float gch[3];
+            float dir[3], g[3];
+            const float il = view_dir(p, a.campos, dir);
+            GSR_SH_DIR_GRAD(D, c, cl, dcol, dir, gch, ddir);
+            sh_dir_project(dir, ddir, il, g);
 #pragma unroll
-            for (int ch = 0; ch < 3; ch++) gch[ch] = ((cl >> ch) & 1) ? 0.f : dcol[ch];
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++)
-#pragma unroll
-                for (int k = 0; k < K; k++)
-#pragma unroll
-                    for (int ax = 0; ax < 3; ax++) ddir[ax] += bg3[k][ax] * c[k * 3 + ch] * gch[ch];
-            const float dot = dir[0] * ddir[0] + dir[1] * ddir[1] + dir[2] * ddir[2];
-#pragma unroll
-            for (int ax = 0; ax < 3; ax++) sC[ax] = -((ddir[ax] - dir[ax] * dot) * il);
+            for (int ax = 0; ax < 3; ax++) sC[ax] = -g[ax];
         }
         // ---- the maps' depth value: dL/dv dv/dz into the z row of viewmatrix ----
         if (a.kind != GSR_POSE_COLOR) {
@@ -333,13 +257,8 @@ int32_t gsr_pose_backward(gsr_stream_t stream, int32_t kind, int32_t P, int32_t 
     a.radii = radii; a.clamped = g.clamped; a.touched = g.touched; a.touch_mark = g.touch_mark; a.hot = g.hot;
     a.acc = (const float *)acc_ws; a.rows = (double *)ws;
     const dim3 grid((unsigned)pose_rows(P)), block(256);
-    switch (sh ? D : -1) {
-        case 0: hipLaunchKernelGGL((pose_terms_kernel<0, true>), grid, block, 0, s, a); break;
-        case 1: hipLaunchKernelGGL((pose_terms_kernel<1, true>), grid, block, 0, s, a); break;
-        case 2: hipLaunchKernelGGL((pose_terms_kernel<2, true>), grid, block, 0, s, a); break;
-        case 3: hipLaunchKernelGGL((pose_terms_kernel<3, true>), grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL((pose_terms_kernel<0, false>), grid, block, 0, s, a); break;
-    }
+    if (!sh) hipLaunchKernelGGL((pose_terms_kernel<0, false>), grid, block, 0, s, a);
+    else with_sh_degree(D, [&](auto DD) { hipLaunchKernelGGL((pose_terms_kernel<decltype(DD)::value, true>), grid, block, 0, s, a); });
     HIP_TRY(hipGetLastError(), "pose terms launch");
     hipLaunchKernelGGL(pose_sum_kernel, dim3(1), block, 0, s, (const double *)ws, (int)pose_rows(P), dL_dviewmatrix, dL_dprojmatrix, dL_dcampos);
     HIP_TRY(hipGetLastError(), "pose sum launch");

@@ -3,8 +3,8 @@
 // 256-thread workgroups.  HBM-streaming: reads 44 + 12*K bytes, writes 48 (record) + 4 (depth)
 // + 8 (rect) + 4 (tiles) + 4 (radii) + 1 (clamp mask) per Gaussian.
 // Compiled with -ffp-contract=off: discrete outputs are bit-identical to oracle/gsr_ref.c.
-#include "gsr_device.h"
-#include "gsr_internal.h"
+#include "gsr_host.h"
+#include "pergauss_chain.h"
 
 namespace gsr {
 
@@ -62,8 +62,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void p
     }
     if (pv[2] > GSR_NEAR_Z) {                                                       // S1
         float ph[4];
-        xform4x4(pm, p, ph);
-        const float pw = 1.f / (ph[3] + GSR_W_EPS);
+        const float pw = persp_divide(pm, p, ph);
         const float ndcx = ph[0] * pw, ndcy = ph[1] * pw;
         float c6[6];
         if (a.cov3D_precomp) {
@@ -71,14 +70,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void p
             for (int k = 0; k < 6; k++) c6[k] = a.cov3D_precomp[6 * si + k];
         } else {                                                                    // S2
             float s[3] = {s_in[0], s_in[1], s_in[2]};
-            const float4 q4 = q4_in;
-            float q[4] = {q4.x, q4.y, q4.z, q4.w};
-            if (RAW) {              // fused activations: exp / normalize
-                s[0] = expf(s[0]); s[1] = expf(s[1]); s[2] = expf(s[2]);
-                float inv_norm;
-                act_normalize4(q, inv_norm);
-            }
-            cov3d_from_scale_rot(s, a.scale_modifier, q, c6);
+            float q[4] = {q4_in.x, q4_in.y, q4_in.z, q4_in.w};
+            cov3d_activated<RAW>(s, q, a.scale_modifier, c6);       // fused activations: exp / normalize
         }
         Ewa e;
         ewa_project(pv, c6, vm, a.tanfovx, a.tanfovy, a.W, a.H, e);       // S3
@@ -86,14 +79,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void p
         if (det != 0.f) {
             const float det_inv = 1.f / det;
             const float conA = e.c * det_inv, conB = -e.b * det_inv, conC = e.a * det_inv;
-            const float mid = 0.5f * (e.a + e.c);
-            float disc = mid * mid - det;
-            if (disc < GSR_LAMBDA_FLOOR) disc = GSR_LAMBDA_FLOOR;
-            const float l1 = mid + sqrtf(disc), l2 = mid - sqrtf(disc);
-            const float lmax = l1 > l2 ? l1 : l2;
-            const int radius = (int)ceilf(GSR_SIGMA_EXTENT * sqrtf(lmax));
-            const float px = ((ndcx + 1.f) * (float)a.W - 1.f) * 0.5f;             // S5
-            const float py = ((ndcy + 1.f) * (float)a.H - 1.f) * 0.5f;
+            const int radius = splat_radius(e, det);
+            const float px = ndc_to_pixel(ndcx, a.W), py = ndc_to_pixel(ndcy, a.H);             // S5
             int x0, y0, x1, y1;
             tile_rect(px, py, radius, a.gridx, a.gridy, x0, y0, x1, y1);
             const int area = (x1 - x0) * (y1 - y0);
@@ -214,20 +201,9 @@ hipError_t launch_preprocess_fwd(const PreprocessArgs &a, hipStream_t s) {
     const dim3 grid((a.P + 255) / 256), block(256);
     const int d = a.shs ? a.D : 0;
     const bool raw = a.raw_params != 0, split = a.shs_rest != nullptr;
-#define GSR_LAUNCH(DD)                                                                                   \
-    do {                                                                                                 \
-        if (!raw && !split) hipLaunchKernelGGL((preprocess_fwd_kernel<DD, false, false>), grid, block, 0, s, a);           \
-        else if (raw && !split) hipLaunchKernelGGL((preprocess_fwd_kernel<DD, true, false>), grid, block, 0, s, a);        \
-        else if (!raw && split) hipLaunchKernelGGL((preprocess_fwd_kernel<DD, false, true>), grid, block, 0, s, a);        \
-        else hipLaunchKernelGGL((preprocess_fwd_kernel<DD, true, true>), grid, block, 0, s, a);                            \
-    } while (0)
-    switch (d) {
-        case 0: GSR_LAUNCH(0); break;
-        case 1: GSR_LAUNCH(1); break;
-        case 2: GSR_LAUNCH(2); break;
-        default: GSR_LAUNCH(3); break;
-    }
-#undef GSR_LAUNCH
+    with_sh_degree(d, [&](auto D) { with_flag(raw, [&](auto RAW) { with_flag(split, [&](auto SPLIT) {
+        hipLaunchKernelGGL((preprocess_fwd_kernel<decltype(D)::value, decltype(RAW)::value, decltype(SPLIT)::value>), grid, block, 0, s, a);
+    }); }); });
     return hipGetLastError();
 }
 

@@ -2,16 +2,16 @@
 //   box sort : key kernel (box of every row, decided against the boundary table in LDS) -> stable rocPRIM radix sort of
 //              (box, index) over just the bits the boxes need -> gather kernel (rows, permutation, count, zero tail).
 //              Dropped rows carry the key n^3, so the stable sort leaves them behind every box: no compaction step, no atomic.
-//   visible_union : one lane per Gaussian, 3-D covariance built once, then the geometry stages S1-S5 of preprocess.hip per camera.
+//   visible_union : one lane per Gaussian, 3-D covariance built once (pergauss_chain.h's cov3d_activated, as preprocess.hip calls it),
+//              then the geometry stages S1-S5 of preprocess.hip per camera.
 // Compiled with -ffp-contract=off -fno-slp-vectorize like preprocess.hip: the radii round exactly as gsr_forward's.
 #include <cstring>  // ROCm 7.2 rocprim/texture_cache_iterator.hpp uses memset without including it
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/gsr_sequence.h"
-#include "gsr_device.h"
 #include "gsr_host.h"
-#include "gsr_internal.h"
+#include "pergauss_chain.h"
 
 namespace gsr {
 
@@ -136,7 +136,8 @@ static hipError_t launch_box_sort(int P, int D, const float *rows, int xyz_col, 
 // ---------------------------------------------------------------- visibility ----------------------------------------------------------------
 
 // 256 threads, one Gaussian per lane; the cameras' matrices sit in LDS (8 KB at B = 64), their scalars in the kernel arguments.
-// Per camera the sequence of operations is that of preprocess_fwd_kernel up to `area != 0`, on the same helpers.
+// Per camera the sequence of operations is that of preprocess_fwd_kernel up to `area != 0`: the same three tests around calls of the
+// same stages (pergauss_chain.h: persp_divide, ewa_project, splat_radius, ndc_to_pixel, tile_rect).
 template <bool RAW>
 __global__ __launch_bounds__(256) void visible_union_kernel(VisibleArgs a) {
     __shared__ float s_vm[GSR_SEQ_MAX_B * 16], s_pm[GSR_SEQ_MAX_B * 16];
@@ -154,12 +155,7 @@ __global__ __launch_bounds__(256) void visible_union_kernel(VisibleArgs a) {
         float s[3] = {a.scales[3 * si], a.scales[3 * si + 1], a.scales[3 * si + 2]};
         const float4 q4 = reinterpret_cast<const float4 *>(a.rotations)[si];
         float q[4] = {q4.x, q4.y, q4.z, q4.w};
-        if (RAW) {
-            s[0] = expf(s[0]); s[1] = expf(s[1]); s[2] = expf(s[2]);
-            float inv_norm;
-            act_normalize4(q, inv_norm);
-        }
-        cov3d_from_scale_rot(s, a.scale_modifier, q, c6);
+        cov3d_activated<RAW>(s, q, a.scale_modifier, c6);
     }
     bool any = false;
     for (int b = 0; b < a.B; b++) {
@@ -173,21 +169,14 @@ __global__ __launch_bounds__(256) void visible_union_kernel(VisibleArgs a) {
         xform4x3(vm, p, pv);
         if (pv[2] > GSR_NEAR_Z) {                                                       // S1
             float ph[4];
-            xform4x4(pm, p, ph);
-            const float pw = 1.f / (ph[3] + GSR_W_EPS);
+            const float pw = persp_divide(pm, p, ph);
             const float ndcx = ph[0] * pw, ndcy = ph[1] * pw;
             Ewa e;
             ewa_project(pv, c6, vm, a.tanfovx[b], a.tanfovy[b], W, H, e);               // S3
             const float det = e.a * e.c - e.b * e.b;                                    // S4
             if (det != 0.f) {
-                const float mid = 0.5f * (e.a + e.c);
-                float disc = mid * mid - det;
-                if (disc < GSR_LAMBDA_FLOOR) disc = GSR_LAMBDA_FLOOR;
-                const float l1 = mid + sqrtf(disc), l2 = mid - sqrtf(disc);
-                const float lmax = l1 > l2 ? l1 : l2;
-                const int radius = (int)ceilf(GSR_SIGMA_EXTENT * sqrtf(lmax));
-                const float px = ((ndcx + 1.f) * (float)W - 1.f) * 0.5f;                // S5
-                const float py = ((ndcy + 1.f) * (float)H - 1.f) * 0.5f;
+                const int radius = splat_radius(e, det);
+                const float px = ndc_to_pixel(ndcx, W), py = ndc_to_pixel(ndcy, H);                // S5
                 int x0, y0, x1, y1;
                 tile_rect(px, py, radius, gridx, gridy, x0, y0, x1, y1);
                 if ((x1 - x0) * (y1 - y0) != 0) radius_out = radius;

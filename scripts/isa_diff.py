@@ -6,8 +6,10 @@ The gate of a refactor that must not change a shipped kernel: each named file of
 assembly (device side only) with the flags gaussian_transformer_amd/build.py gives it -- COMMON + SOURCES[file], imported, not
 copied -- once from `git show <base-rev>:...` laid out in a temporary directory (headers included) and once from the working tree.
 The listings are split per function symbol and normalised (comments, .file/.loc/.ident, the __hip_cuid_<hash> symbol hipcc derives
-from the source text, the function index in compiler-made labels); per kernel it prints `identical` or `differs` and the register,
-scratch and LDS figures of the code object's metadata from both sides.  Exit status 1 if any kernel differs or exists on one side only.  --diff adds a unified diff of each kernel that differs.
+from the source text, the function index in compiler-made labels); per kernel it prints `identical`, `reordered` or `differs` and the register,
+scratch and LDS figures of the code object's metadata from both sides.  `reordered`: another text of as many instructions, with the
+same multiset of mnemonics (first token of each line that is no label) and the same four figures.  Exit status 1 if any kernel
+differs or exists on one side only, 0 if every kernel is identical or reordered.  --diff adds a unified diff of each kernel that differs.
 Host-only: needs hipcc, no GPU.  It compares text; it looks for no particular instruction.
 """
 from __future__ import annotations
@@ -19,6 +21,7 @@ import re
 import subprocess
 import sys
 import tempfile
+from collections import Counter
 from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -80,17 +83,30 @@ def split_kernels(text: str) -> dict:
     return out
 
 
+def _mnemonics(body):
+    """The first token of every line that is no label, as a multiset"""
+    return Counter(line.split()[0] for line in body if not line.endswith(":"))
+
+
 def compare(base_text: str, new_text: str):
-    """([(symbol, verdict, base figures or None, new figures or None)], number of symbols that are not `identical`)"""
+    """([(symbol, verdict, base figures or None, new figures or None)], number of symbols that are neither `identical` nor `reordered`)
+
+    `reordered`: the bodies differ, but in as many instructions, with the same multiset of mnemonics and the same four figures -- what
+    a compiler makes of the same arithmetic reached through another spelling (operands of commutative instructions swapped, registers
+    renumbered, instructions scheduled in another order)."""
     base, new = split_kernels(base_text), split_kernels(new_text)
     rows, bad = [], 0
     for sym in sorted(set(base) | set(new)):
         b, n = base.get(sym), new.get(sym)
         if b is None or n is None:
             verdict = "only in base" if n is None else "only in working tree"
+        elif b["body"] == n["body"]:
+            verdict = "identical"
+        elif b["figures"] == n["figures"] and _mnemonics(b["body"]) == _mnemonics(n["body"]):   # equal multisets: equal counts
+            verdict = "reordered"
         else:
-            verdict = "identical" if b["body"] == n["body"] else "differs"
-        bad += verdict != "identical"
+            verdict = "differs"
+        bad += verdict not in ("identical", "reordered")
         rows.append((sym, verdict, b and b["figures"], n and n["figures"]))
     return rows, bad
 
@@ -141,7 +157,7 @@ def main(argv) -> int:
         return 2
     rev, files = argv[1], argv[2:] or DEFAULT_FILES
     build = _load_build()
-    total = bad_total = 0
+    total = bad_total = reordered_total = 0
     with tempfile.TemporaryDirectory() as tmp:
         _checkout(rev, os.path.join(tmp, "base"))
         jobs = [(os.path.join(tmp, "base"), f, os.path.join(tmp, "base_" + f + ".s")) for f in files] + \
@@ -151,7 +167,7 @@ def main(argv) -> int:
     for i, f in enumerate(files):
         rows, bad = compare(texts[i], texts[len(files) + i])
         names = _demangle([r[0] for r in rows])
-        print(f"== {f} ({' '.join(build.COMMON + build.SOURCES[f])}): {len(rows)} functions, {bad} not identical")
+        print(f"== {f} ({' '.join(build.COMMON + build.SOURCES[f])}): {len(rows)} functions, {bad} neither identical nor reordered")
         for sym, verdict, b, n in rows:
             fig = " ".join(f"{k.split('_')[0]}={(b or {}).get(k, '-')}/{(n or {}).get(k, '-')}" for k in FIGURES)
             print(f"{verdict:21s} {fig:44s} {names[sym]}")
@@ -159,7 +175,9 @@ def main(argv) -> int:
                 print(kernel_diff(texts[i], texts[len(files) + i], sym))
         total += len(rows)
         bad_total += bad
-    print(f"== total: {total} functions against {rev}, {total - bad_total} identical, {bad_total} not   (figures: base/working tree; vgpr, sgpr, private = scratch bytes, group = LDS bytes)")
+        reordered_total += sum(r[1] == "reordered" for r in rows)
+    print(f"== total: {total} functions against {rev}, {total - bad_total - reordered_total} identical, {reordered_total} reordered, "
+          f"{bad_total} differing or one-sided   (figures: base/working tree; vgpr, sgpr, private = scratch bytes, group = LDS bytes)")
     return 1 if bad_total else 0
 
 

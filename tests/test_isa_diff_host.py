@@ -88,12 +88,12 @@ def test_same_kernels_under_other_comments_cuid_and_order_are_identical():
 def test_one_changed_instruction_is_reported_for_its_kernel_alone():
     base = _listing(["_Z5alphav", "_Z4betav"], BODIES, "4e6ad1bbb72490bd", "base")
     changed = dict(BODIES)
-    changed["_Z4betav"] = lambda i, note: BODIES["_Z4betav"](i, note).replace("v_fmac_f32 v2, v0, v1", "v_fmac_f32 v2, v1, v0")
+    changed["_Z4betav"] = lambda i, note: BODIES["_Z4betav"](i, note).replace("v_fmac_f32 v2, v0, v1", "v_fma_f32 v2, v1, v0, v2")
     new = _listing(["_Z5alphav", "_Z4betav"], changed, "da3ea229d1e0f6a3", "new")
     rows, bad = isa_diff.compare(base, new)
     assert bad == 1
     assert {r[0]: r[1] for r in rows} == {"_Z5alphav": "identical", "_Z4betav": "differs"}
-    assert "v_fmac_f32 v2, v1, v0" in isa_diff.kernel_diff(base, new, "_Z4betav")
+    assert "v_fma_f32 v2, v1, v0, v2" in isa_diff.kernel_diff(base, new, "_Z4betav")
 
 
 def test_a_kernel_on_one_side_only_is_reported_by_name():
@@ -104,3 +104,51 @@ def test_a_kernel_on_one_side_only_is_reported_by_name():
     assert {r[0]: r[1] for r in rows} == {"_Z5alphav": "identical", "_Z4betav": "only in base"}
     rows, bad = isa_diff.compare(new, base)
     assert bad == 1 and ("_Z4betav", "only in working tree") in [(r[0], r[1]) for r in rows]
+
+
+# the same arithmetic as the compiler lists it after a refactor that changes no result: operands of commutative instructions swapped,
+# registers renumbered, two independent instructions in the other order
+_GAMMA = """\tv_mul_f32_e32 v3, v1, v2
+\tv_add_f32_e32 v4, v3, v0
+\tv_mul_f32_e32 v5, v4, v4
+\ts_cbranch_scc0 .LBB{i}_2
+\tv_add_f32_e32 v5, v5, v3
+.LBB{i}_2:
+\ts_endpgm
+"""
+_GAMMA_REORDERED = """\tv_mul_f32_e32 v7, v2, v1
+\tv_add_f32_e32 v6, v0, v7
+\tv_mul_f32_e32 v5, v6, v6
+\ts_cbranch_scc0 .LBB{i}_2
+\tv_add_f32_e32 v5, v7, v5
+.LBB{i}_2:
+\ts_endpgm
+"""
+
+
+def _gamma_pair(new_body, new_vgpr=12):
+    base = _listing(["_Z5alphav", "_Z5gammav"], dict(BODIES, _Z5gammav=lambda i, note: _GAMMA.format(i=i)), "4e6ad1bbb72490bd", "base")
+    new = _listing(["_Z5alphav", "_Z5gammav"], dict(BODIES, _Z5gammav=lambda i, note: new_body.format(i=i)), "da3ea229d1e0f6a3", "new")
+    return base, new.replace(_meta("_Z5gammav", 12), _meta("_Z5gammav", new_vgpr))
+
+
+def test_swapped_operands_and_renamed_registers_are_reordered():
+    rows, bad = isa_diff.compare(*_gamma_pair(_GAMMA_REORDERED))
+    assert bad == 0
+    assert {r[0]: r[1] for r in rows} == {"_Z5alphav": "identical", "_Z5gammav": "reordered"}
+
+
+def test_reordered_plus_one_changed_mnemonic_or_one_changed_figure_differs():
+    # as many instructions, one of them another one
+    rows, bad = isa_diff.compare(*_gamma_pair(_GAMMA_REORDERED.replace("v_add_f32_e32 v5, v7, v5", "v_sub_f32_e32 v5, v7, v5")))
+    assert bad == 1
+    assert {r[0]: r[1] for r in rows} == {"_Z5alphav": "identical", "_Z5gammav": "differs"}
+    # one instruction more
+    rows, bad = isa_diff.compare(*_gamma_pair(_GAMMA_REORDERED.replace("\ts_endpgm", "\ts_nop 0\n\ts_endpgm")))
+    assert bad == 1 and {r[0]: r[1] for r in rows}["_Z5gammav"] == "differs"
+    # the same reordered text with one register more in the metadata
+    rows, bad = isa_diff.compare(*_gamma_pair(_GAMMA_REORDERED, new_vgpr=13))
+    assert bad == 1
+    assert {r[0]: r[1] for r in rows} == {"_Z5alphav": "identical", "_Z5gammav": "differs"}
+    g = [r for r in rows if r[0] == "_Z5gammav"][0]
+    assert g[2]["vgpr_count"] == "12" and g[3]["vgpr_count"] == "13"
