@@ -9,6 +9,7 @@ upstream package; the native layer underneath is libgsr_hip.so th
 from __future__ import annotations
 
 import ctypes as C
+import math
 import weakref
 from typing import NamedTuple, Optional
 
@@ -47,6 +48,40 @@ def _f32c(t: torch.Tensor, name: str, device) -> torch.Tensor:
     if t.device != device:
         t = t.to(device)
     return t.contiguous()
+
+
+def camera_settings(cam, bg, scale_modifier, sh_degree, debug) -> GaussianRasterizationSettings:
+    """The settings of one render from a camera object (image_height / image_width, FoVx / FoVy, world_view_transform,
+    full_proj_transform, camera_center), as the reference builds them (gaussian_renderer/__init__.py:32-49)."""
+    return GaussianRasterizationSettings(
+        image_height=int(cam.image_height), image_width=int(cam.image_width),
+        tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5), bg=bg, scale_modifier=scale_modifier,
+        viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, sh_degree=sh_degree,
+        campos=cam.camera_center, prefiltered=False, debug=bool(debug))
+
+
+def _camera(rs: GaussianRasterizationSettings, dev):
+    return _f32c(rs.viewmatrix, "viewmatrix", dev), _f32c(rs.projmatrix, "projmatrix", dev), _f32c(rs.campos, "campos", dev)
+
+
+def _workspace(lib, sizer: str, dev, *sizes) -> torch.Tensor:
+    """A uint8 tensor of as many bytes as the library's `sizer` (one of the gsr_*_workspace_bytes) asks for at these sizes."""
+    n = C.c_size_t()
+    _lib.check(getattr(lib, sizer)(*sizes, C.byref(n)), sizer)
+    return torch.empty((n.value,), dtype=torch.uint8, device=dev)
+
+
+def _arena_fits(arena: torch.Tensor, dev, P: int, M: int, has_sr: bool) -> bool:
+    return arena.device == dev and arena.dtype == torch.float32 and arena.is_contiguous() and arena.numel() >= arena_floats(P, M, has_sr)
+
+
+def _usable_arena(dev, P: int, M: int, has_sr: bool):
+    """The gradient arena a reverse pass carves its outputs from (None: none is set), refused if it cannot hold them."""
+    arena = _grad_arena
+    if arena is not None and not _arena_fits(arena, dev, P, M, has_sr):
+        raise _lib.GsrError("gradient arena must be a contiguous float32 tensor on the render device with "
+                            f"at least {arena_floats(P, M, has_sr)} elements")
+    return arena
 
 
 class HipBackend:
@@ -162,12 +197,11 @@ class HipBackend:
                     return None
             cb = _lib.ALLOC_FN(alloc)
             n = C.c_int64(0)
-            bg = _f32c(rs.bg, "bg", dev); vm = _f32c(rs.viewmatrix, "viewmatrix", dev)
-            pm = _f32c(rs.projmatrix, "projmatrix", dev); cp = _f32c(rs.campos, "campos", dev)
+            bg = _f32c(rs.bg, "bg", dev)
+            vm, pm, cp = _camera(rs, dev)
             grads = None
             arena = _grad_arena            # set around the forward call too: the announced tensors are its slices (and get zeroed now)
-            if arena is not None and (arena.device != dev or arena.dtype != torch.float32 or not arena.is_contiguous()
-                                      or arena.numel() < arena_floats(P, M, scales.numel() > 0)):
+            if arena is not None and not _arena_fits(arena, dev, P, M, scales.numel() > 0):
                 announce_backward = False  # backward() raises the error
             claimed = arena is not None and announce_backward and P > 0
             if claimed:
@@ -216,15 +250,10 @@ class HipBackend:
         f32 = dict(dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            bbs = C.c_size_t()         # depends on the pair count while the deterministic mode is on
-            _lib.check(self.lib.gsr_backward_workspace_bytes(P, int(num_rendered), C.byref(bbs)), "gsr_backward_workspace_bytes")
-            bwd_ws = torch.empty((bbs.value,), dtype=torch.uint8, device=dev)
+            # depends on the pair count while the deterministic mode is on
+            bwd_ws = _workspace(self.lib, "gsr_backward_workspace_bytes", dev, P, int(num_rendered))
             has_sr = scales.numel() > 0
-            arena = _grad_arena
-            if arena is not None and (arena.device != dev or arena.dtype != torch.float32 or not arena.is_contiguous()
-                                      or arena.numel() < arena_floats(P, M + Mrest, has_sr)):
-                raise _lib.GsrError("gradient arena must be a contiguous float32 tensor on the render device with "
-                                    f"at least {arena_floats(P, M + Mrest, has_sr)} elements")
+            arena = _usable_arena(dev, P, M + Mrest, has_sr)
             self._release_arena(geom)      # the arena claimed at forward time is the caller's again after this call
             ann = self._announced.pop(dev.index, None)
             if ann is not None and ann[:3] == (geom.data_ptr(), P, M) and Mrest == 0 and \
@@ -233,8 +262,8 @@ class HipBackend:
             else:
                 grads = self._gradient_outputs(dev, P, M, Mrest, has_sr, colors_precomp.numel() > 0, cov3D_precomp.numel() > 0, arena)
             g_means3D, g_means2D, g_sh, g_colors, g_opacity, g_scales, g_rots, g_cov3D, g_sh_rest = grads
-            bg = _f32c(rs.bg, "bg", dev); vm = _f32c(rs.viewmatrix, "viewmatrix", dev)
-            pm = _f32c(rs.projmatrix, "projmatrix", dev); cp = _f32c(rs.campos, "campos", dev)
+            bg = _f32c(rs.bg, "bg", dev)
+            vm, pm, cp = _camera(rs, dev)
             dL = _f32c(dL_dpix, "grad of rendered image", dev)
             rc = self.lib.gsr_backward(
                 stream, P, int(rs.sh_degree), M + Mrest, int(num_rendered), W, H, _ptr(bg), _ptr(means3D), _ptr(radii),
@@ -285,11 +314,7 @@ class HipBackend:
             stream = torch.cuda.current_stream(dev).cuda_stream
             if into is None:
                 M = sh_floats // 3
-                arena = _grad_arena
-                if arena is not None and (arena.device != dev or arena.dtype != torch.float32 or not arena.is_contiguous()
-                                          or arena.numel() < arena_floats(P, M, has_sr)):
-                    raise _lib.GsrError("gradient arena must be a contiguous float32 tensor on the render device with "
-                                        f"at least {arena_floats(P, M, has_sr)} elements")
+                arena = _usable_arena(dev, P, M, has_sr)
                 self._release_arena(geom)
                 g_means3D, g_means2D, g_sh, _c, g_opacity, g_scales, g_rots, g_cov3D, _r = self._gradient_outputs(
                     dev, P, M if arena is not None else 0, 0, has_sr, False, has_cov, arena)
@@ -297,10 +322,8 @@ class HipBackend:
                     g_sh.zero_()
             else:
                 g_means3D, g_means2D, g_opacity, g_scales, g_rots, g_cov3D = into
-            wsb = C.c_size_t()
-            _lib.check(self.lib.gsr_depth_workspace_bytes(P, C.byref(wsb)), "gsr_depth_workspace_bytes")
-            ws = torch.empty((wsb.value,), dtype=torch.uint8, device=dev)
-            vm = _f32c(rs.viewmatrix, "viewmatrix", dev); pm = _f32c(rs.projmatrix, "projmatrix", dev); cp = _f32c(rs.campos, "campos", dev)
+            ws = _workspace(self.lib, "gsr_depth_workspace_bytes", dev, P)
+            vm, pm, cp = _camera(rs, dev)
             gD = None if dL_ddepth is None else _f32c(dL_ddepth, "grad of the depth map", dev)
             gA = None if dL_dalpha is None else _f32c(dL_dalpha, "grad of the alpha map", dev)
             rc = self.lib.gsr_depth_backward(
@@ -328,10 +351,8 @@ class HipBackend:
         g_proj = torch.empty((4, 4), **f32) if want[1] else None
         g_campos = torch.empty((3,), **f32) if want[2] else None
         with torch.cuda.device(dev):
-            wsb = C.c_size_t()
-            _lib.check(self.lib.gsr_pose_workspace_bytes(P, C.byref(wsb)), "gsr_pose_workspace_bytes")
-            ws = torch.empty((wsb.value,), dtype=torch.uint8, device=dev)
-            vm = _f32c(rs.viewmatrix, "viewmatrix", dev); pm = _f32c(rs.projmatrix, "projmatrix", dev); cp = _f32c(rs.campos, "campos", dev)
+            ws = _workspace(self.lib, "gsr_pose_workspace_bytes", dev, P)
+            vm, pm, cp = _camera(rs, dev)
             colour = int(kind) == _lib.POSE_COLOR
             rc = self.lib.gsr_pose_backward(
                 torch.cuda.current_stream(dev).cuda_stream, int(kind), P, int(rs.sh_degree), M, W, H, int(num_rendered),
@@ -456,21 +477,46 @@ def composited_mask(image: Optional[torch.Tensor] = None):
     return None if geom is None else be.composited_mask(geom, P)
 
 
+_INPUT_NAMES = ("shs", "colors_precomp", "opacities", "scales", "rotations", "cov3D_precomp")      # of GaussianRasterizer.forward, after means3D
+
+
+def _gaussian_inputs(means3D, tensors, names):
+    """means3D and the tensors after it as the backend takes them: float32, dense, on means3D's device."""
+    if means3D.dim() != 2 or means3D.shape[1] != 3:
+        raise _lib.GsrError("means3D must have dimensions (num_points, 3)")
+    dev = means3D.device
+    return [_f32c(means3D, "means3D", dev)] + [_f32c(t, n, dev) for t, n in zip(tensors, names)]
+
+
+def _announce(ctx, be):
+    """The keyword that tells be.forward that a backward call will follow, for backends that announce (the tests' stand-ins take no
+    such keyword)."""
+    return {"announce_backward": True} if any(ctx.needs_input_grad) and hasattr(be, "_announced") else {}
+
+
+def _keep(ctx, saved, geom_index, means_index, radii):
+    """What every render leaves behind for its backward call and for composited_mask()."""
+    _remember_forward(saved[geom_index], int(saved[means_index].shape[0]))
+    ctx.save_for_backward(*saved)
+    ctx.gsr_geom_index, ctx.gsr_means_index = geom_index, means_index        # composited_mask(image) finds the workspace through image.grad_fn
+    ctx.mark_non_differentiable(radii)
+    ctx.set_materialize_grads(False)      # no zero tensor for the int32 radii output on every backward (a 4 P byte fill)
+
+
+def _zero_colour_grad(rs, dev):
+    """Materialisation is off (_keep): an unused colour output arrives as None, and the colour pass takes this in its place."""
+    return torch.zeros((3, int(rs.image_height), int(rs.image_width)), dtype=torch.float32, device=dev)
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
         be = get_backend()
-        dev = means3D.device
-        if means3D.dim() != 2 or means3D.shape[1] != 3:
-            raise _lib.GsrError("means3D must have dimensions (num_points, 3)")
-        args = [_f32c(t, n, dev) for t, n in ((means3D, "means3D"), (sh, "shs"), (colors_precomp, "colors_precomp"),
-                                              (opacities, "opacities"), (scales, "scales"), (rotations, "rotations"),
-                                              (cov3Ds_precomp, "cov3D_precomp"))]
+        args = _gaussian_inputs(means3D, (sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp), _INPUT_NAMES)
         means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c = args
         try:
             num_rendered, color, radii, geom, binning, img = be.forward(
-                raster_settings, means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c,
-                **({"announce_backward": True} if any(ctx.needs_input_grad) and hasattr(be, "_announced") else {}))
+                raster_settings, means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c, **_announce(ctx, be))
         except Exception:
             if raster_settings.debug:
                 _dump("snapshot_fw.dump", *args, raster_settings._asdict())
@@ -478,20 +524,16 @@ class _RasterizeGaussians(torch.autograd.Function):
             raise
         ctx.raster_settings = raster_settings
         ctx.num_rendered = num_rendered
-        _remember_forward(geom, int(means3D_c.shape[0]))
-        ctx.save_for_backward(colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img)
-        ctx.gsr_geom_index, ctx.gsr_means_index = 7, 1        # composited_mask(image) finds the workspace through image.grad_fn
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)      # no zero tensor for the int32 radii output on every backward (a 4 P byte fill)
+        _keep(ctx, (colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img), 7, 1, radii)
         return color, radii
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii):
         be = get_backend()
         rs = ctx.raster_settings
-        if grad_out_color is None:            # materialisation is off: an unused colour output arrives as None
-            grad_out_color = torch.zeros((3, int(rs.image_height), int(rs.image_width)), dtype=torch.float32, device=ctx.saved_tensors[1].device)
         colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img = ctx.saved_tensors
+        if grad_out_color is None:
+            grad_out_color = _zero_colour_grad(rs, means3D_c.device)
         try:
             g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov = be.backward(
                 rs, ctx.num_rendered, grad_out_color, means3D_c, radii, sh_c, colors_c, scales_c, rots_c, cov_c,
@@ -515,6 +557,40 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
 DEPTH_MODES = {"expected": _lib.DEPTH_EXPECTED, "inverse": _lib.DEPTH_INVERSE}
 
 
+def _reverse_passes(ctx, be, grad_color, grad_depth, grad_alpha, camera_pass=None):
+    """The reverse passes of a render with maps or camera gradients (at least one of the three gradients given, or no maps at
+    all): the colour pass, the map pass, or the colour pass and then the map pass adding into its tensors.  Returns the gradients
+    of the eight Gaussian inputs.  camera_pass: called as camera_pass(pose kind, workspace) right after each pass whose loss the
+    caller differentiates, while that pass is the last one on the stream; the workspaces are asked for (return_ws) only then."""
+    rs = ctx.raster_settings
+    colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img = ctx.saved_tensors
+    maps = grad_depth is not None or grad_alpha is not None
+    keep_ws = {} if camera_pass is None else {"return_ws": True}
+    g_sh = g_colors = None
+    colour_used = grad_color is not None
+    # A map gradient alone must not write into an arena the library may still be zero-filling (HipBackend.arena_fill_in_flight): the
+    # colour pass joins that fill, so it runs first, on a zero gradient.  Without maps the colour pass is all there is to run.
+    if not colour_used and (not maps or (hasattr(be, "arena_fill_in_flight") and be.arena_fill_in_flight(geom))):
+        grad_color = _zero_colour_grad(rs, means3D_c.device)
+    if grad_color is not None:
+        g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov, *ws = be.backward(
+            rs, ctx.num_rendered, grad_color, means3D_c, radii, sh_c, colors_c, scales_c, rots_c, cov_c, geom, binning, img, **keep_ws)
+        if camera_pass is not None and (colour_used or not maps):
+            camera_pass(_lib.POSE_COLOR, ws[0])
+    if maps:
+        into = None if grad_color is None else (g_means3D, g_means2D, g_opac, g_scales, g_rots, g_cov)
+        g_means3D, g_means2D, g_opac, g_scales, g_rots, g_cov, *ws = be.depth_backward(
+            rs, ctx.num_rendered, ctx.depth_mode, grad_depth, grad_alpha, means3D_c, radii, scales_c, rots_c, cov_c,
+            geom, binning, img, into=into, sh_floats=3 * int(sh_c.shape[1]) if sh_c.numel() else 0, **keep_ws)
+        if camera_pass is not None:
+            camera_pass(_lib.POSE_DEPTH_INVERSE if ctx.depth_mode == _lib.DEPTH_INVERSE else _lib.POSE_DEPTH_EXPECTED, ws[0])
+    none_if_empty = lambda g, src: g if (g is not None and src.numel() > 0) else None
+    if not colour_used:
+        g_sh = g_colors = None          # the maps give the colour inputs no gradient
+    return (g_means3D, g_means2D, none_if_empty(g_sh, sh_c), none_if_empty(g_colors, colors_c), g_opac,
+            none_if_empty(g_scales, scales_c), none_if_empty(g_rots, rots_c), none_if_empty(g_cov, cov_c))
+
+
 class _RasterizeGaussiansDepth(torch.autograd.Function):
     """(color, radii, depth, alpha): _RasterizeGaussians' render followed by the depth and alpha maps of the same lists
     (include/gsr_depth.h).  The forward call is the plain one -- announcement, arena, binning hint as there -- then one walk over what
@@ -526,50 +602,20 @@ class _RasterizeGaussiansDepth(torch.autograd.Function):
         be = get_backend()
         if not hasattr(be, "depth_forward"):
             raise _lib.GsrError(f"the {getattr(be, 'name', type(be).__name__)} backend renders no depth or alpha map")
-        dev = means3D.device
-        if means3D.dim() != 2 or means3D.shape[1] != 3:
-            raise _lib.GsrError("means3D must have dimensions (num_points, 3)")
-        args = [_f32c(t, n, dev) for t, n in ((means3D, "means3D"), (sh, "shs"), (colors_precomp, "colors_precomp"),
-                                              (opacities, "opacities"), (scales, "scales"), (rotations, "rotations"),
-                                              (cov3Ds_precomp, "cov3D_precomp"))]
+        args = _gaussian_inputs(means3D, (sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp), _INPUT_NAMES)
         means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c = args
         num_rendered, color, radii, geom, binning, img = be.forward(
-            raster_settings, means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c,
-            **({"announce_backward": True} if any(ctx.needs_input_grad) and hasattr(be, "_announced") else {}))
+            raster_settings, means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c, **_announce(ctx, be))
         depth, alpha = be.depth_forward(raster_settings, int(means3D_c.shape[0]), num_rendered, mode, geom, binning, img)
         ctx.raster_settings, ctx.num_rendered, ctx.depth_mode = raster_settings, num_rendered, mode
-        _remember_forward(geom, int(means3D_c.shape[0]))
-        ctx.save_for_backward(colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img)
-        ctx.gsr_geom_index, ctx.gsr_means_index = 7, 1
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
+        _keep(ctx, (colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img), 7, 1, radii)
         return color, radii, depth.unsqueeze(0), alpha.unsqueeze(0)
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha):
-        be = get_backend()
-        rs = ctx.raster_settings
-        colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img = ctx.saved_tensors
-        maps = grad_depth is not None or grad_alpha is not None
-        if grad_color is None and not maps:
+        if grad_color is None and grad_depth is None and grad_alpha is None:
             return (None,) * 10
-        g_sh = g_colors = None
-        colour_used = grad_color is not None
-        if not colour_used and hasattr(be, "arena_fill_in_flight") and be.arena_fill_in_flight(geom):
-            grad_color = torch.zeros((3, int(rs.image_height), int(rs.image_width)), dtype=torch.float32, device=means3D_c.device)
-        if grad_color is not None:
-            g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov = be.backward(
-                rs, ctx.num_rendered, grad_color, means3D_c, radii, sh_c, colors_c, scales_c, rots_c, cov_c, geom, binning, img)
-        if maps:
-            into = None if grad_color is None else (g_means3D, g_means2D, g_opac, g_scales, g_rots, g_cov)
-            g_means3D, g_means2D, g_opac, g_scales, g_rots, g_cov = be.depth_backward(
-                rs, ctx.num_rendered, ctx.depth_mode, grad_depth, grad_alpha, means3D_c, radii, scales_c, rots_c, cov_c,
-                geom, binning, img, into=into, sh_floats=3 * int(sh_c.shape[1]) if sh_c.numel() else 0)
-        none_if_empty = lambda g, src: g if (g is not None and src.numel() > 0) else None
-        if not colour_used:
-            g_sh = g_colors = None          # the maps give the colour inputs no gradient
-        return (g_means3D, g_means2D, none_if_empty(g_sh, sh_c), none_if_empty(g_colors, colors_c), g_opac,
-                none_if_empty(g_scales, scales_c), none_if_empty(g_rots, rots_c), none_if_empty(g_cov, cov_c), None, None)
+        return _reverse_passes(ctx, get_backend(), grad_color, grad_depth, grad_alpha) + (None, None)
 
 
 class _RasterizeGaussiansPose(torch.autograd.Function):
@@ -585,27 +631,18 @@ class _RasterizeGaussiansPose(torch.autograd.Function):
         be = get_backend()
         if not hasattr(be, "pose_backward") or (mode is not None and not hasattr(be, "depth_forward")):
             raise _lib.GsrError(f"the {getattr(be, 'name', type(be).__name__)} backend has no camera gradients")
-        dev = means3D.device
-        if means3D.dim() != 2 or means3D.shape[1] != 3:
-            raise _lib.GsrError("means3D must have dimensions (num_points, 3)")
         if viewmatrix.numel() != 16 or projmatrix.numel() != 16 or campos.numel() != 3:
             raise _lib.GsrError("viewmatrix and projmatrix must have 16 elements and campos 3")
-        args = [_f32c(t, n, dev) for t, n in ((means3D, "means3D"), (sh, "shs"), (colors_precomp, "colors_precomp"),
-                                              (opacities, "opacities"), (scales, "scales"), (rotations, "rotations"),
-                                              (cov3Ds_precomp, "cov3D_precomp"))]
+        args = _gaussian_inputs(means3D, (sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp), _INPUT_NAMES)
         means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c = args
+        dev = means3D.device
         cam = [_f32c(t.detach(), n, dev) for t, n in ((viewmatrix, "viewmatrix"), (projmatrix, "projmatrix"), (campos, "campos"))]
         rs = raster_settings._replace(viewmatrix=cam[0], projmatrix=cam[1], campos=cam[2])
         num_rendered, color, radii, geom, binning, img = be.forward(
-            rs, means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c,
-            **({"announce_backward": True} if any(ctx.needs_input_grad) and hasattr(be, "_announced") else {}))
+            rs, means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c, **_announce(ctx, be))
         ctx.raster_settings, ctx.num_rendered, ctx.depth_mode = rs, num_rendered, mode
         ctx.cam_like = [(tuple(t.shape), t.dtype, t.device) for t in (viewmatrix, projmatrix, campos)]
-        _remember_forward(geom, int(means3D_c.shape[0]))
-        ctx.save_for_backward(colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img)
-        ctx.gsr_geom_index, ctx.gsr_means_index = 7, 1
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
+        _keep(ctx, (colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img), 7, 1, radii)
         if mode is None:
             return color, radii
         depth, alpha = be.depth_forward(rs, int(means3D_c.shape[0]), num_rendered, mode, geom, binning, img)
@@ -613,33 +650,17 @@ class _RasterizeGaussiansPose(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, grad_depth=None, grad_alpha=None):
-        be = get_backend()
-        rs = ctx.raster_settings
-        colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img = ctx.saved_tensors
-        maps = grad_depth is not None or grad_alpha is not None
-        if grad_color is None and not maps and ctx.depth_mode is not None:
+        if grad_color is None and grad_depth is None and grad_alpha is None and ctx.depth_mode is not None:
             return (None,) * 13
+        be = get_backend()
+        colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, _binning, _img = ctx.saved_tensors
         want = tuple(ctx.needs_input_grad[8:11])
-        g_sh = g_colors = None
-        colour_used = grad_color is not None
-        if not colour_used and (ctx.depth_mode is None or (hasattr(be, "arena_fill_in_flight") and be.arena_fill_in_flight(geom))):
-            grad_color = torch.zeros((3, int(rs.image_height), int(rs.image_width)), dtype=torch.float32, device=means3D_c.device)
         cams = []
-        if grad_color is not None:
-            g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov, ws = be.backward(
-                rs, ctx.num_rendered, grad_color, means3D_c, radii, sh_c, colors_c, scales_c, rots_c, cov_c, geom, binning, img,
-                return_ws=True)
-            if colour_used or not maps:
-                cams.append(be.pose_backward(rs, _lib.POSE_COLOR, ctx.num_rendered, means3D_c, radii, sh_c, colors_c, scales_c, rots_c,
-                                             cov_c, geom, ws, want=want))
-        if maps:
-            into = None if grad_color is None else (g_means3D, g_means2D, g_opac, g_scales, g_rots, g_cov)
-            g_means3D, g_means2D, g_opac, g_scales, g_rots, g_cov, ws = be.depth_backward(
-                rs, ctx.num_rendered, ctx.depth_mode, grad_depth, grad_alpha, means3D_c, radii, scales_c, rots_c, cov_c,
-                geom, binning, img, into=into, sh_floats=3 * int(sh_c.shape[1]) if sh_c.numel() else 0, return_ws=True)
-            kind = _lib.POSE_DEPTH_INVERSE if ctx.depth_mode == _lib.DEPTH_INVERSE else _lib.POSE_DEPTH_EXPECTED
-            cams.append(be.pose_backward(rs, kind, ctx.num_rendered, means3D_c, radii, sh_c, colors_c, scales_c, rots_c, cov_c, geom, ws,
-                                         want=want))
+
+        def camera_pass(kind, ws):
+            cams.append(be.pose_backward(ctx.raster_settings, kind, ctx.num_rendered, means3D_c, radii, sh_c, colors_c, scales_c, rots_c,
+                                         cov_c, geom, ws, want=want))
+        gaussians = _reverse_passes(ctx, be, grad_color, grad_depth, grad_alpha, camera_pass)
         g_cam = []
         for k, (shape, dtype, device) in enumerate(ctx.cam_like):      # in the input tensors' shapes and dtypes
             parts = [c[k] for c in cams if c[k] is not None]
@@ -648,12 +669,7 @@ class _RasterizeGaussiansPose(torch.autograd.Function):
                 continue
             g = parts[0] if len(parts) == 1 else parts[0] + parts[1]
             g_cam.append(g.reshape(shape).to(device=device, dtype=dtype))
-        none_if_empty = lambda g, src: g if (g is not None and src.numel() > 0) else None
-        if not colour_used:
-            g_sh = g_colors = None          # the maps give the colour inputs no gradient
-        return (g_means3D, g_means2D, none_if_empty(g_sh, sh_c), none_if_empty(g_colors, colors_c), g_opac,
-                none_if_empty(g_scales, scales_c), none_if_empty(g_rots, rots_c), none_if_empty(g_cov, cov_c),
-                g_cam[0], g_cam[1], g_cam[2], None, None)
+        return gaussians + (g_cam[0], g_cam[1], g_cam[2], None, None)
 
 
 class _RasterizeGaussiansFused(torch.autograd.Function):
@@ -664,26 +680,17 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, raster_settings):
         be = get_backend()
-        dev = means3D.device
-        if means3D.dim() != 2 or means3D.shape[1] != 3:
-            raise _lib.GsrError("means3D must have dimensions (num_points, 3)")
-        a = [_f32c(t, n, dev) for t, n in ((means3D, "means3D"), (features_dc, "features_dc"), (features_rest, "features_rest"),
-                                            (opacity_raw, "opacity"), (scaling_raw, "scaling"), (rotation_raw, "rotation"))]
-        m3, dc, rest, op, sc, rot = a
+        m3, dc, rest, op, sc, rot = _gaussian_inputs(means3D, (features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw),
+                                                     ("features_dc", "features_rest", "opacity", "scaling", "rotation"))
         if dc.dim() != 3 or dc.shape[1] != 1 or rest.dim() != 3 or rest.shape[1] < 1:
             raise _lib.GsrError("features_dc must be [P,1,3] and features_rest [P,M-1,3] with M >= 2")
         empty = m3.new_empty((0,))
         # announce_backward: nothing is announced in the fused form (HipBackend.forward); it only lets a gradient arena set around
         # this call be claimed for this render, so that ONE arena around several renders in flight is refused here as well
         num_rendered, color, radii, geom, binning, img = be.forward(raster_settings, m3, dc, empty, op, sc, rot, empty,
-                                                                    shs_rest=rest, raw_params=True,
-                                                                    **({"announce_backward": True} if any(ctx.needs_input_grad) and hasattr(be, "_announced") else {}))
+                                                                    shs_rest=rest, raw_params=True, **_announce(ctx, be))
         ctx.raster_settings, ctx.num_rendered = raster_settings, num_rendered
-        _remember_forward(geom, int(m3.shape[0]))
-        ctx.save_for_backward(m3, dc, rest, sc, rot, radii, geom, binning, img)
-        ctx.gsr_geom_index, ctx.gsr_means_index = 6, 0
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)      # no zero tensor for the int32 radii output on every backward (a 4 P byte fill)
+        _keep(ctx, (m3, dc, rest, sc, rot, radii, geom, binning, img), 6, 0, radii)
         return color, radii
 
     @staticmethod
@@ -691,8 +698,7 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
         be = get_backend()
         m3, dc, rest, sc, rot, radii, geom, binning, img = ctx.saved_tensors
         if grad_out_color is None:
-            rs_ = ctx.raster_settings
-            grad_out_color = torch.zeros((3, int(rs_.image_height), int(rs_.image_width)), dtype=torch.float32, device=m3.device)
+            grad_out_color = _zero_colour_grad(ctx.raster_settings, m3.device)
         empty = m3.new_empty((0,))
         g_m3, g_m2, g_dc, _g_col, g_op, g_sc, g_rot, _g_cov, g_rest = be.backward(
             ctx.raster_settings, ctx.num_rendered, grad_out_color, m3, radii, dc, empty, sc, rot, empty, geom, binning, img,

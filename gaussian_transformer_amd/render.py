@@ -8,12 +8,11 @@ works unchanged against `diff_gaussian_rasterization` from this repo.
 """
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass
 
 import torch
 
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians_fused
+from .rasterizer import GaussianRasterizer, camera_settings, rasterize_gaussians_fused
 
 
 @dataclass
@@ -56,13 +55,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
         screenspace_points.retain_grad()
     except Exception:
         pass
-    tanfovx = math.tan(viewpoint_camera.FoVx * 0.5)
-    tanfovy = math.tan(viewpoint_camera.FoVy * 0.5)
-    raster_settings = GaussianRasterizationSettings(
-        image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
-        tanfovx=tanfovx, tanfovy=tanfovy, bg=bg_color, scale_modifier=scaling_modifier,
-        viewmatrix=viewpoint_camera.world_view_transform, projmatrix=viewpoint_camera.full_proj_transform,
-        sh_degree=pc.active_sh_degree, campos=viewpoint_camera.camera_center, prefiltered=False, debug=pipe.debug)
+    raster_settings = camera_settings(viewpoint_camera, bg_color, scaling_modifier, pc.active_sh_degree, pipe.debug)
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)
     means3D, means2D, opacity = xyz, screenspace_points, pc.get_opacity
     scales = rotations = cov3D_precomp = None
@@ -103,12 +96,7 @@ def render_fused(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_mod
         screenspace_points.retain_grad()
     except Exception:
         pass
-    rs = GaussianRasterizationSettings(
-        image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
-        tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
-        scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
-        projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
-        campos=viewpoint_camera.camera_center, prefiltered=False, debug=pipe.debug)
+    rs = camera_settings(viewpoint_camera, bg_color, scaling_modifier, pc.active_sh_degree, pipe.debug)
     image, radii = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
                                              pc._scaling, pc._rotation, rs)
     return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}

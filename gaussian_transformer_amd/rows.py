@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from .model import GaussianParams
-from .rasterizer import GaussianRasterizationSettings, _remember_forward, arena_floats, get_backend, gradient_arena
+from .rasterizer import _remember_forward, arena_floats, camera_settings, get_backend, gradient_arena
 from .sequence import _check_device, _check_tensor
 
 MAX_B = 64           # GSR_ROWS_MAX_B: arenas per native pack call (larger camera sets are packed in chunks and added in order)
@@ -148,14 +148,6 @@ class _RenderRows(torch.autograd.Function):
             return _pack(arenas, P, D, dev), None, None
 
 
-def _settings(cam, bg, scaling_modifier, sh_degree, debug) -> GaussianRasterizationSettings:
-    return GaussianRasterizationSettings(
-        image_height=int(cam.image_height), image_width=int(cam.image_width),
-        tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5), bg=bg, scale_modifier=scaling_modifier,
-        viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, sh_degree=sh_degree,
-        campos=cam.camera_center, prefiltered=False, debug=debug)
-
-
 def render_rows(cameras, rows: torch.Tensor, pipe, bg: torch.Tensor, scaling_modifier: float = 1.0, sh_degree=None) -> dict:
     """Renders float32 rows [P, 3 K + 14] (K in 1, 4, 9, 16) on a HIP device under every camera of `cameras` (the objects render()
     takes; they may differ in size).  Returns {"renders": list of B images [3, H_b, W_b], "radii": [B, P] int32,
@@ -183,7 +175,7 @@ def render_rows(cameras, rows: torch.Tensor, pipe, bg: torch.Tensor, scaling_mod
     if not isinstance(sh_degree, int) or not 0 <= sh_degree <= deg:
         raise _lib.GsrError(f"{who}: sh_degree={sh_degree!r} not in 0..{deg}, the degree D={int(rows.shape[1])} columns hold")
     _check_device(who, "rows", rows)
-    settings = tuple(_settings(cam, bg, scaling_modifier, sh_degree, bool(pipe.debug)) for cam in cameras)
+    settings = tuple(camera_settings(cam, bg, scaling_modifier, sh_degree, pipe.debug) for cam in cameras)
     if torch.is_grad_enabled() and rows.requires_grad:
         *images, radii = _RenderRows.apply(rows, K, settings)
     else:

@@ -389,7 +389,7 @@ def test_no_grad_keeps_nothing(case26):
 def test_one_coefficient_rows_end_to_end():
     """D = 17 (K = 1: no f_rest buffer, no f_rest block in the arenas), which render_fused does not take: against the same backend calls
     made by hand on unflatten_gaussians(rows) made contiguous, the arenas packed by tests/rows_ref.py."""
-    from gaussian_transformer_amd.rasterizer import get_backend
+    from gaussian_transformer_amd.rasterizer import camera_settings, get_backend
     cs_rows = flatten_gaussians(GaussianParams.from_synthetic(synth.make_scene(300, 128, 80, sh_degree=0, seed=45), DEV, requires_grad=False)).contiguous()
     from gaussian_transformer_amd import rows as R
     P, D = cs_rows.shape
@@ -408,7 +408,7 @@ def test_one_coefficient_rows_end_to_end():
         (got,) = torch.autograd.grad(out["renders"], leaf, G)
         arenas = []
         for b, cam in enumerate(cams):
-            rs = R._settings(cam, bg, 1.0, 0, False)
+            rs = camera_settings(cam, bg, 1.0, 0, False)
             n, color, radii, geom, binning, img = be.forward(rs, xyz, dc, empty, op, sc, rot, empty, shs_rest=None, raw_params=True)
             assert torch.equal(color, out["renders"][b]) and torch.equal(radii, out["radii"][b]) and float(color.abs().max()) > 0
             gm3, _gm2, gsh, _gc, gop, gsc, grot, _gcov = be.backward(rs, n, G[b], xyz, radii, dc, empty, sc, rot, empty, geom, binning, img,

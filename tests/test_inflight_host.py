@@ -2,7 +2,8 @@
 stand-in (orders A, C and D; expectations 1 and 3), and the expectations must reject three planted faults -- a stand-in that hands
 render i the gradients of render i - 1, one that drops a render's contribution, one that leaves a NaN row where no gradient
 exists.  The proof that the GPU test can fail; no library is built or run.  Also on the CPU: case F's step (one GaussianParams,
-judged in raw-parameter space) with every camera through render(), and the bookkeeping of gradient-arena claims."""
+judged in raw-parameter space) with every camera through render(), the bookkeeping of gradient-arena claims, and the check that
+decides whether a gradient arena can hold a render's gradients."""
 import numpy as np
 import pytest
 import torch
@@ -99,6 +100,31 @@ def test_arena_claims_overlap_release_and_expiry():
     del g3                                               # the owner's graph is gone: it never ran backward, and never will
     be._claim_arena(flat[:8], g1)
     assert len(be._arena_claims) == 2
+
+
+@pytest.mark.parametrize("has_sr", (True, False))
+@pytest.mark.parametrize("M", (0, 1, 16))
+def test_arena_is_accepted_from_exactly_arena_floats_elements_float32_and_dense(M, has_sr):
+    """The one check behind HipBackend.forward (which only stops announcing), backward and depth_backward (which raise): the
+    boundary is arena_floats(P, M, has_sr) = P (3 + 3 M + 1 + 7 with scales and rotations) elements, one short is refused."""
+    from gaussian_transformer_amd import _lib
+    P = 5
+    n = P * (4 + 3 * M + (7 if has_sr else 0))
+    assert rasterizer.arena_floats(P, M, has_sr) == n
+    cpu = torch.device("cpu")
+    fits = lambda t: rasterizer._arena_fits(t, cpu, P, M, has_sr)
+    assert fits(torch.zeros(n)) and fits(torch.zeros(n + 3)) and not fits(torch.zeros(n - 1))
+    assert not fits(torch.zeros(n, dtype=torch.float64)) and not fits(torch.zeros(n, dtype=torch.float16))
+    assert not fits(torch.zeros(2 * n)[::2]) and fits(torch.zeros(2 * n)[n:])          # a strided view; a dense slice
+    assert not fits(torch.zeros(n, device="meta"))                                     # another device than the render's
+    for bad in (torch.zeros(n - 1), torch.zeros(n, dtype=torch.float64), torch.zeros(2 * n)[::2]):
+        with rasterizer.gradient_arena(bad):
+            with pytest.raises(_lib.GsrError, match=f"gradient arena must be a contiguous float32 tensor on the render device with at least {n} elements"):
+                rasterizer._usable_arena(cpu, P, M, has_sr)
+    good = torch.zeros(n)
+    with rasterizer.gradient_arena(good):
+        assert rasterizer._usable_arena(cpu, P, M, has_sr) is good
+    assert rasterizer._usable_arena(cpu, P, M, has_sr) is None                         # none set: nothing to refuse
 
 
 # ---- planted faults -----------------------------------------------------------------------------------------------------------
