@@ -68,16 +68,14 @@ static hipError_t carve_plan_ws(void *base, int P, int N, PlanWs &w) {
     hipError_t e = rocprim::exclusive_scan(nullptr, tb, rocprim::make_transform_iterator((const uint8_t *)nullptr, FlagToRank()), (Rank5 *)nullptr,
                                            Rank5{0, 0, 0, 0, 0}, np, RankAdd(), (hipStream_t)0, false);
     if (e != hipSuccess) return e;
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += align_up(bytes); return r; };
-    w.counts = (uint32_t *)take(C_WORDS * 4);
-    w.flags = (uint8_t *)take(np);
-    w.ranks = (Rank5 *)take(np * sizeof(Rank5));
-    w.map = (uint32_t *)take(np * (size_t)(N + 1) * 4);
-    w.temp = take(tb > 0 ? tb : 1);
+    Bump b = {(char *)base, 0};
+    w.counts = b.take<uint32_t>(C_WORDS);
+    w.flags = b.take<uint8_t>(np);
+    w.ranks = b.take<Rank5>(np);
+    w.map = b.take<uint32_t>(np * (size_t)(N + 1));
+    w.temp = b.take<char>(tb > 0 ? tb : 1);
     w.temp_bytes = tb;
-    w.total = off;
+    w.total = b.off;
     return hipSuccess;
 }
 

@@ -285,11 +285,16 @@ __global__ __launch_bounds__(256) void depth_finish_kernel(FinishArgs f) {
 }
 
 // ---- host side ----
-#define GSR_TRY(expr) do { const int32_t _rc = (expr); if (_rc != GSR_OK) return _rc; } while (0)
-inline int grid_dim(int px) { return (int)(((long long)px + GSR_TILE_HOST - 1) / GSR_TILE_HOST); }
-inline size_t acc_bytes(int P) { return align_up(acc_rows(P) * GSR_ACC_FLOATS * sizeof(float)); }
-inline size_t stage_floats(int P) { return (size_t)(P > 0 ? P : 0) * 20; }      // rots 4 | means2D 3 | means3D 3 | opacity 1 | scales 3 | cov3D 6
-inline size_t workspace_bytes(int P) { return acc_bytes(P) + align_up(stage_floats(P) * sizeof(float)); }
+// gsr_depth_backward's workspace: the accumulator rows where gsr_backward's has them, then the staging area `accumulate` sends the
+// per-Gaussian stage's results through, one piece of 20 floats per Gaussian: rots 4 | means2D 3 | means3D 3 | opacity 1 | scales 3 | cov3D 6
+struct DepthWs { float *acc, *t_rots, *t_m2, *t_m3, *t_op, *t_sc, *t_cov; size_t total_bytes; };
+DepthWs carve_depth_ws(void *ws, int P) {
+    const BackwardView rows = carve_backward(ws, P, 0);
+    const size_t n = (size_t)(P > 0 ? P : 0);
+    Bump w = {(char *)ws, rows.vis_off};
+    float *const st = w.take<float>(20 * n);
+    return {rows.acc, st, st + 4 * n, st + 7 * n, st + 10 * n, st + 11 * n, st + 14 * n, w.off};
+}
 
 int32_t sizes_and_mode(const char *who, int P, int W, int H, long long R, int mode) {
     if (P < 0 || W <= 0 || H <= 0 || R < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
@@ -299,21 +304,8 @@ int32_t sizes_and_mode(const char *who, int P, int W, int H, long long R, int mo
     return GSR_OK;
 }
 
-// the three workspaces of the gsr_forward before this call, as gsr_api.hip carves them
+// the three workspaces of the gsr_forward before this call (gsr_internal.h: view_geom, view_image, view_lists, refused in this order)
 struct Views { GeomView g; ImageView im; BinningView b; };
-int32_t carve(Views &v, int P, int W, int H, long long R, const void *geom_ws, size_t geom_bytes, const void *binning_ws, size_t binning_bytes,
-              const void *img_ws, size_t img_bytes) {
-    size_t stb = 0, dtb = 0;
-    HIP_TRY(scan_temp_bytes(P, &stb), "scan temp query");
-    HIP_TRY(depth_sort_temp_bytes(P, &dtb), "depth sort temp query");
-    v.g = carve_geom(const_cast<void *>(geom_ws), P, stb, dtb);
-    v.im = carve_image(const_cast<void *>(img_ws), W, H);
-    v.b = carve_binning(const_cast<void *>(binning_ws), R, 0);
-    if (geom_bytes < v.g.total_bytes) return fail(GSR_ERR_WORKSPACE, "geom workspace %zu < %zu", geom_bytes, v.g.total_bytes);
-    if (img_bytes < v.im.total_bytes) return fail(GSR_ERR_WORKSPACE, "image workspace %zu < %zu", img_bytes, v.im.total_bytes);
-    if (binning_bytes < v.b.list_bytes) return fail(GSR_ERR_WORKSPACE, "binning workspace too small for R=%lld (%zu < %zu)", R, binning_bytes, v.b.list_bytes);
-    return GSR_OK;
-}
 DepthArgs walk_args(const Views &v, int P, int W, int H, long long R, int mode) {
     DepthArgs a;
     memset(&a, 0, sizeof a);
@@ -333,7 +325,7 @@ extern "C" {
 
 int32_t gsr_depth_workspace_bytes(int32_t P, size_t *bytes) {
     if (P < 0 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_depth_workspace_bytes: bad argument");
-    *bytes = workspace_bytes(P);
+    *bytes = carve_depth_ws(nullptr, P).total_bytes;
     return GSR_OK;
 }
 
@@ -351,7 +343,9 @@ int32_t gsr_depth_forward(gsr_stream_t stream, int32_t P, int32_t W, int32_t H, 
     }
     if (!geom_ws || !binning_ws || !img_ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_depth_forward: missing workspace");
     Views v;
-    GSR_TRY(carve(v, P, W, H, (long long)R, geom_ws, geom_bytes, binning_ws, binning_bytes, img_ws, img_bytes));
+    GSR_TRY(view_geom(geom_ws, geom_bytes, P, &v.g));
+    GSR_TRY(view_image(img_ws, img_bytes, W, H, &v.im));
+    GSR_TRY(view_lists(binning_ws, binning_bytes, R, &v.b));
     DepthArgs a = walk_args(v, P, W, H, (long long)R, mode);
     a.out_depth = out_depth; a.out_alpha = out_alpha;
     hipLaunchKernelGGL(depth_fwd_kernel, dim3(walk_blocks(a)), dim3(256), 0, s, a);
@@ -381,7 +375,8 @@ int32_t gsr_depth_backward(gsr_stream_t stream, int32_t P, int32_t W, int32_t H,
     int32_t det = 0;
     GSR_TRY(gsr_get_option("deterministic_bwd", &det));
     if (det) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: not available while the option deterministic_bwd is on (this pass sums with float atomics and has no slot form)", who);
-    if (ws_bytes < workspace_bytes(P)) return fail(GSR_ERR_WORKSPACE, "depth workspace %zu < %zu", ws_bytes, workspace_bytes(P));
+    const DepthWs dw = carve_depth_ws(ws, P);
+    if (ws_bytes < dw.total_bytes) return fail(GSR_ERR_WORKSPACE, "depth workspace %zu < %zu", ws_bytes, dw.total_bytes);
     if (acc_rows(P) >= (1u << 28)) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: P too large for the 28-bit accumulator row index", who);
     float *const d_scales = scales ? dL_dscales : nullptr, *const d_rots = scales ? dL_drots : nullptr;      // the form that was not given is not written
     if (R == 0) {                                       // nothing was composited: every gradient is zero
@@ -395,38 +390,36 @@ int32_t gsr_depth_backward(gsr_stream_t stream, int32_t P, int32_t W, int32_t H,
         return GSR_OK;
     }
     Views v;
-    GSR_TRY(carve(v, P, W, H, (long long)R, geom_ws, geom_bytes, binning_ws, binning_bytes, img_ws, img_bytes));
+    GSR_TRY(view_geom(geom_ws, geom_bytes, P, &v.g));
+    GSR_TRY(view_image(img_ws, img_bytes, W, H, &v.im));
+    GSR_TRY(view_lists(binning_ws, binning_bytes, R, &v.b));
 
     // 1. clear the rows that can be added into; 2. the reverse walk
-    float *acc = (float *)ws;
-    HIP_TRY(launch_zero_marked_rows(P, v.g.touched, v.g.touch_mark, acc, acc_rows(P), v.im.seg, 0, 0, s), "zero depth accumulators");
+    HIP_TRY(launch_zero_marked_rows(P, v.g.touched, v.g.touch_mark, dw.acc, acc_rows(P), v.im.seg, 0, 0, s), "zero depth accumulators");
     DepthArgs a = walk_args(v, P, W, H, (long long)R, mode);
-    a.gD = dL_ddepth; a.gA = dL_dalpha; a.acc = acc; a.acc_rows = acc_rows(P);
+    a.gD = dL_ddepth; a.gA = dL_dalpha; a.acc = dw.acc; a.acc_rows = acc_rows(P);
     hipLaunchKernelGGL(depth_bwd_kernel, dim3(walk_blocks(a)), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError(), "depth backward launch");
 
     // 3. the per-Gaussian chain S11-S13 on these rows: pergauss_bwd.hip's streaming kernel, no colour input, into the caller's buffers or
     //    -- with accumulate -- into the staging area behind the rows
-    float *st = (float *)((char *)ws + acc_bytes(P));
-    const size_t n = (size_t)P;
-    float *const t_rots = st, *const t_m2 = st + 4 * n, *const t_m3 = st + 7 * n, *const t_op = st + 10 * n, *const t_sc = st + 11 * n, *const t_cov = st + 14 * n;
     PergaussBwdArgs pa;
     memset(&pa, 0, sizeof pa);
     pa.P = P; pa.W = W; pa.H = H; pa.rec = v.g.rec; pa.means3D = means3D; pa.scales = scales; pa.rotations = rotations; pa.cov3D_precomp = cov3D_precomp;
     pa.opac = v.g.opac; pa.viewmatrix = viewmatrix; pa.projmatrix = projmatrix; pa.campos = campos;
     pa.scale_modifier = scale_modifier; pa.tanfovx = tanfovx; pa.tanfovy = tanfovy; pa.radii = radii; pa.clamped = v.g.clamped;
-    pa.acc = acc; pa.hot = v.g.hot; pa.touched = v.g.touched; pa.touch_mark = v.g.touch_mark;
-    pa.dL_dmeans2D = accumulate ? t_m2 : dL_dmeans2D; pa.dL_dopacity = accumulate ? t_op : dL_dopacity; pa.dL_dmeans3D = accumulate ? t_m3 : dL_dmeans3D;
-    pa.dL_dcov3D = dL_dcov3D ? (accumulate ? t_cov : dL_dcov3D) : nullptr;
-    pa.dL_dscales = d_scales ? (accumulate ? t_sc : d_scales) : nullptr; pa.dL_drots = d_rots ? (accumulate ? t_rots : d_rots) : nullptr;
+    pa.acc = dw.acc; pa.hot = v.g.hot; pa.touched = v.g.touched; pa.touch_mark = v.g.touch_mark;
+    pa.dL_dmeans2D = accumulate ? dw.t_m2 : dL_dmeans2D; pa.dL_dopacity = accumulate ? dw.t_op : dL_dopacity; pa.dL_dmeans3D = accumulate ? dw.t_m3 : dL_dmeans3D;
+    pa.dL_dcov3D = dL_dcov3D ? (accumulate ? dw.t_cov : dL_dcov3D) : nullptr;
+    pa.dL_dscales = d_scales ? (accumulate ? dw.t_sc : d_scales) : nullptr; pa.dL_drots = d_rots ? (accumulate ? dw.t_rots : d_rots) : nullptr;
     HIP_TRY(launch_pergauss_bwd(pa, s), "per-Gaussian backward launch");
 
     // 4. dL/dv -> dL/dmeans3D, and the accumulation
     FinishArgs f;
     memset(&f, 0, sizeof f);
     f.P = P; f.mode = mode; f.accumulate = accumulate ? 1 : 0; f.means3D = means3D; f.viewmatrix = viewmatrix; f.radii = radii;
-    f.touched = v.g.touched; f.clamped = v.g.clamped; f.touch_mark = v.g.touch_mark; f.hot = v.g.hot; f.acc = acc;
-    f.t_means2D = t_m2; f.t_opacity = t_op; f.t_means3D = t_m3; f.t_cov3D = t_cov; f.t_scales = t_sc; f.t_rots = t_rots;
+    f.touched = v.g.touched; f.clamped = v.g.clamped; f.touch_mark = v.g.touch_mark; f.hot = v.g.hot; f.acc = dw.acc;
+    f.t_means2D = dw.t_m2; f.t_opacity = dw.t_op; f.t_means3D = dw.t_m3; f.t_cov3D = dw.t_cov; f.t_scales = dw.t_sc; f.t_rots = dw.t_rots;
     f.dL_dmeans2D = dL_dmeans2D; f.dL_dopacity = dL_dopacity; f.dL_dmeans3D = dL_dmeans3D; f.dL_dcov3D = dL_dcov3D; f.dL_dscales = d_scales; f.dL_drots = d_rots;
     hipLaunchKernelGGL(depth_finish_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, f);
     HIP_TRY(hipGetLastError(), "depth finish launch");

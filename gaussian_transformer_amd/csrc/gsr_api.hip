@@ -179,7 +179,6 @@ struct Plan {
     int lpt_span;             // > 0: image and options allow the reverse pass's half tiles in order of decreasing length (composite_bwd_lpt_kernel)
     bool dense_wanted;        // dense_pergauss says the per-Gaussian stage runs on the Gaussians with a gradient only
 };
-static inline int grid_dim(int px) { return (int)(((long long)px + GSR_TILE_HOST - 1) / GSR_TILE_HOST); }      // (the plan is made before W and H are checked)
 static Plan make_plan(const Options &o, int P, int W, int H) {
     Plan p;
     p.gridx = grid_dim(W); p.gridy = grid_dim(H);
@@ -209,13 +208,7 @@ int fail(int code, const char *fmt, ...) {      // gsr_host.h: every entry point
     va_end(ap);
     return code;
 }
-#define GSR_TRY(expr) do { const int32_t _rc = (expr); if (_rc != GSR_OK) return _rc; } while (0)
 static int32_t hip_rc(hipError_t e, const char *what) { HIP_TRY(e, what); return GSR_OK; }      // the last HIP call of a function
-
-struct Bump {      // hands out consecutive 256-byte-aligned pieces of a workspace; base NULL: only the sizes are wanted
-    char *base; size_t off;
-    template <class T> T *take(size_t count) { char *r = base ? base + off : nullptr; off += align_up(count * sizeof(T)); return (T *)r; }
-};
 
 GeomView carve_geom(void *base, int P, size_t scan_tb, size_t dsort_tb) {
     GeomView g;
@@ -241,12 +234,12 @@ GeomView carve_geom(void *base, int P, size_t scan_tb, size_t dsort_tb) {
     g.total_bytes = w.off;
     return g;
 }
-static int32_t geom_view(const void *ws, int P, GeomView *g) {      // the geometry workspace as every entry point sees it (rocPRIM says the temp sizes)
+int32_t view_geom(const void *ws, size_t bytes, int P, GeomView *g) {
     size_t stb = 0, dtb = 0;
     HIP_TRY(scan_temp_bytes(P, &stb), "scan temp query");
     HIP_TRY(depth_sort_temp_bytes(P, &dtb), "depth sort temp query");
     *g = carve_geom(const_cast<void *>(ws), P, stb, dtb);
-    return GSR_OK;
+    return bytes < g->total_bytes ? fail(GSR_ERR_WORKSPACE, "geom workspace %zu < %zu", bytes, g->total_bytes) : GSR_OK;
 }
 
 ImageView carve_image(void *base, int W, int H) {
@@ -264,6 +257,10 @@ ImageView carve_image(void *base, int W, int H) {
     v.total_bytes = w.off;
     return v;
 }
+int32_t view_image(const void *ws, size_t bytes, int W, int H, ImageView *im) {
+    *im = carve_image(const_cast<void *>(ws), W, H);
+    return bytes < im->total_bytes ? fail(GSR_ERR_WORKSPACE, "image workspace %zu < %zu", bytes, im->total_bytes) : GSR_OK;
+}
 
 BinningView carve_binning(void *base, int64_t N, size_t sort_tb) {
     BinningView b;
@@ -277,6 +274,23 @@ BinningView carve_binning(void *base, int64_t N, size_t sort_tb) {
     b.sort_temp = w.take<char>(sort_tb); b.sort_temp_bytes = sort_tb;
     b.total_bytes = w.off;
     return b;
+}
+int32_t view_lists(const void *ws, size_t bytes, int64_t R, BinningView *b) {
+    *b = carve_binning(const_cast<void *>(ws), R, 0);
+    return R > 0 && bytes < b->list_bytes ? fail(GSR_ERR_WORKSPACE, "binning workspace too small for R=%lld (%zu < %zu)", (long long)R, bytes, b->list_bytes) : GSR_OK;
+}
+
+BackwardView carve_backward(void *ws, int P, size_t det_bytes) {
+    BackwardView v;
+    Bump w = {(char *)ws, 0};
+    const size_t acc_floats = acc_rows(P) * GSR_ACC_FLOATS;
+    v.acc = w.take<float>(acc_floats); v.acc_bytes = acc_floats * sizeof(float);
+    v.det_end = w.off + det_bytes; v.det = det_bytes ? (float *)w.take<char>(det_bytes) : nullptr;
+    v.vis_off = w.off; v.vis_cap = pergauss_vis_cap(P);
+    v.vis_count = w.take<uint32_t>(1); v.vis_list = w.take<uint32_t>((size_t)P);      // the counter on a line of its own
+    v.vis_rec = w.take_last<float4>((size_t)v.vis_cap * 15);                           // [vis_cap / 64][15][64]
+    v.total_bytes = w.off;
+    return v;
 }
 
 TileListView carve_tile_lists(void *base, const TileListPlan &pl, int64_t E) {
@@ -383,7 +397,7 @@ struct StageTimer {   // hipEvent pairs on the caller's stream; active only unde
 };
 
 // One gsr_forward or gsr_backward call: what its stages share.  The device state is looked up, the options are read and the plan is
-// made once, here; the views are carved by carve_views() once the arguments have passed their checks.
+// made once, here; the views are taken (view_geom, view_image) once the arguments have passed their checks.
 struct Call {
     hipStream_t s;
     int P, W, H, debug;
@@ -391,7 +405,7 @@ struct Call {
     const Options o;
     const Plan pl;
     StageTimer tm;
-    GeomView g; ImageView im;                // carve_views
+    GeomView g; ImageView im;                // view_geom, view_image
     // gsr_forward only: the caller's allocator for the binning workspace with its argument, and where it wants N (may be NULL)
     gsr_alloc_fn alloc = nullptr; void *alloc_user = nullptr; int64_t *num_rendered = nullptr;
     DeviceState::Prefill pre;                // the announcement this render fills (prefill_take)
@@ -404,13 +418,6 @@ struct Call {
         : s((hipStream_t)stream), P(P_), W(W_), H(H_), debug(debug_), ds(dev_state()), pl(make_plan(o, P_, W_, H_)),
           tm(s, o.profiling != 0, ds) {}
 };
-static int32_t carve_views(Call &c, const void *geom_ws, size_t geom_bytes, const void *img_ws, size_t img_bytes) {
-    GSR_TRY(geom_view(geom_ws, c.P, &c.g));
-    c.im = carve_image(const_cast<void *>(img_ws), c.W, c.H);
-    if (geom_bytes < c.g.total_bytes) return fail(GSR_ERR_WORKSPACE, "geom workspace %zu < %zu", geom_bytes, c.g.total_bytes);
-    if (img_bytes < c.im.total_bytes) return fail(GSR_ERR_WORKSPACE, "image workspace %zu < %zu", img_bytes, c.im.total_bytes);
-    return GSR_OK;
-}
 
 // Reads back the four totals {overflow, Pv or largest bin, N, E} of the kernels `launch(host_out, seq)` queues: they store them into a
 // pinned slot and the host polls its sequence word, so that neither a copy nor a barrier sits between those kernels and the ones queued
@@ -578,8 +585,8 @@ static int32_t fwd_composite(Call &c, const float *bg, float *out_color) {
 struct Reverse {
     PergaussBwdArgs pa;            // inputs and gradient outputs as the per-Gaussian stage takes them: the checks and every stage read them here
     int64_t R;                     // pairs the forward pass rendered
-    void *ws;                      // backward workspace: accumulator rows (acc_bytes) | deterministic mode's slots (det_bytes) | dense stage's list and records
-    size_t ws_bytes, acc_bytes, det_bytes;
+    void *ws; size_t ws_bytes;     // the backward workspace as the caller gave it
+    BackwardView w;                // and carved for this call's mode (bwd_workspaces)
     BinningView b; CompositeCounters *counters;   // the forward pass's lists; the instrumented reverse kernel's counters, or NULL
     bool det, persistent, lpt, dense, prefilled;
     int bwd_asm, pk_grid, fill_chunk;
@@ -602,16 +609,15 @@ static int32_t bwd_check(const Reverse &r, const float *bg, const float *dL_dpix
     if (r.R > 0 && !binning_ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: binning workspace missing");
     return GSR_OK;
 }
+static size_t det_slot_bytes(const Options &o, int64_t R) { return (size_t)R * (size_t)(4 / o.bwd_npx) * GSR_ACC_FLOATS * sizeof(float); }      // deterministic mode: one row per (list entry, wave of the tile)
 static int32_t bwd_workspaces(const Call &c, Reverse &r, const void *binning_ws, size_t binning_bytes) {
-    r.b = carve_binning(const_cast<void *>(binning_ws), r.R, 0);
-    if (r.R > 0 && binning_bytes < r.b.list_bytes) return fail(GSR_ERR_WORKSPACE, "binning workspace too small for R=%lld (%zu < %zu)", (long long)r.R, binning_bytes, r.b.list_bytes);
+    GSR_TRY(view_lists(binning_ws, binning_bytes, r.R, &r.b));
     if (acc_rows(c.P) >= (1u << 28)) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: P too large for the 28-bit accumulator row index");
-    r.acc_bytes = acc_rows(c.P) * GSR_ACC_FLOATS * sizeof(float);
-    if (r.ws_bytes < r.acc_bytes) return fail(GSR_ERR_WORKSPACE, "backward workspace %zu < %zu", r.ws_bytes, r.acc_bytes);
     r.det = c.o.deterministic_bwd != 0 && r.R > 0;
-    r.det_bytes = r.det ? (size_t)r.R * (size_t)(4 / c.o.bwd_npx) * GSR_ACC_FLOATS * sizeof(float) : 0;
-    if (r.det && r.ws_bytes < align_up(r.acc_bytes) + r.det_bytes)
-        return fail(GSR_ERR_WORKSPACE, "deterministic_bwd: backward workspace %zu < %zu (size it with gsr_backward_workspace_bytes)", r.ws_bytes, align_up(r.acc_bytes) + r.det_bytes);
+    r.w = carve_backward(r.ws, c.P, r.det ? det_slot_bytes(c.o, r.R) : 0);
+    if (r.ws_bytes < r.w.acc_bytes) return fail(GSR_ERR_WORKSPACE, "backward workspace %zu < %zu", r.ws_bytes, r.w.acc_bytes);
+    if (r.det && r.ws_bytes < r.w.det_end)
+        return fail(GSR_ERR_WORKSPACE, "deterministic_bwd: backward workspace %zu < %zu (size it with gsr_backward_workspace_bytes)", r.ws_bytes, r.w.det_end);
     return GSR_OK;
 }
 static void bwd_plan(Call &c, Reverse &r) {      // which of the three reverse compositing kernels runs, and with what; the per-Gaussian stage's view of the workspaces
@@ -630,13 +636,10 @@ static void bwd_plan(Call &c, Reverse &r) {      // which of the three reverse c
 // Dense per-Gaussian stage: the zeros of every gradient output are written by a kernel of their own on the device's second stream,
 // forked by bwd_fork and joined in front of pergauss_bwd: it runs beside the compositing kernel (FP32-issue-bound, the memory system idle).
 static void bwd_dense_setup(Call &c, Reverse &r) {
-    const size_t vis_off = align_up(r.acc_bytes) + align_up(r.det_bytes);
     r.dense = r.R > 0 && r.fill_chunk == 0 && c.pl.dense_wanted && pergauss_dense_eligible(r.pa) &&
-              r.ws_bytes >= vis_off + pergauss_vis_bytes(c.P);            // (a workspace sized before this stage existed: the streaming kernel)
+              r.ws_bytes >= r.w.total_bytes;            // (a workspace sized before this stage existed: the streaming kernel)
     if (!r.dense) return;
-    char *vis = (char *)r.ws + vis_off;
-    r.pa.vis_count = (uint32_t *)vis; r.pa.vis_list = (uint32_t *)(vis + 256);
-    r.pa.vis_rec = (float4 *)(vis + 256 + (((size_t)c.P * 4 + 255) / 256 * 256)); r.pa.vis_cap = pergauss_vis_cap(c.P);
+    r.pa.vis_count = r.w.vis_count; r.pa.vis_list = r.w.vis_list; r.pa.vis_rec = r.w.vis_rec; r.pa.vis_cap = r.w.vis_cap;
     std::lock_guard<std::mutex> lk(c.ds.mu);
     if (!side_stream(c.ds)) r.dense = false;
 }
@@ -669,9 +672,9 @@ static int32_t bwd_fork_and_clear(Call &c, const Reverse &r) {
     const int fork_late = c.o.dense_fork == 2 ? (c.P < GSR_DENSE_FORK_EARLY_P ? 1 : 0) : c.o.dense_fork;
     if (r.dense && !fork_late) GSR_TRY(bwd_fork(c, r));
     if (r.det) {
-        HIP_TRY(hipMemsetAsync(r.ws, 0, align_up(r.acc_bytes) + r.det_bytes, c.s), "zero accumulators");
-        if (r.persistent) HIP_TRY(launch_zero_marked_rows(c.P, c.g.touched, c.g.touch_mark, (float *)r.ws, 0, c.im.seg, r.pk_grid, r.fill_chunk, c.s), "unit lists");
-    } else HIP_TRY(launch_zero_marked_rows(c.P, c.g.touched, c.g.touch_mark, (float *)r.ws, acc_rows(c.P), c.im.seg, r.persistent ? r.pk_grid : (r.lpt ? 1 : 0), r.fill_chunk, c.s), "zero accumulators");
+        HIP_TRY(hipMemsetAsync(r.ws, 0, r.w.det_end, c.s), "zero accumulators");
+        if (r.persistent) HIP_TRY(launch_zero_marked_rows(c.P, c.g.touched, c.g.touch_mark, r.w.acc, 0, c.im.seg, r.pk_grid, r.fill_chunk, c.s), "unit lists");
+    } else HIP_TRY(launch_zero_marked_rows(c.P, c.g.touched, c.g.touch_mark, r.w.acc, acc_rows(c.P), c.im.seg, r.persistent ? r.pk_grid : (r.lpt ? 1 : 0), r.fill_chunk, c.s), "zero accumulators");
     return r.dense && fork_late ? bwd_fork(c, r) : GSR_OK;
 }
 static int32_t bwd_composite(Call &c, const Reverse &r, const float *bg, const float *dL_dpix) {
@@ -681,8 +684,7 @@ static int32_t bwd_composite(Call &c, const Reverse &r, const float *bg, const f
     ca.W = c.W; ca.H = c.H; ca.gridx = c.pl.gridx; ca.gridy = c.pl.gridy; ca.ranges = c.im.ranges; ca.point_list = r.b.point_list;
     ca.contrib = r.b.contrib; ca.contrib_stride = (size_t)r.R;
     ca.rec = c.g.rec; ca.bg = bg; ca.final_T = c.im.final_T; ca.n_contrib = c.im.n_contrib; ca.dL_dpix = dL_dpix;
-    ca.acc = (float *)r.ws; ca.counters = r.counters; ca.count_mode = c.o.count_lanes;
-    ca.det = r.det ? (float *)((char *)r.ws + align_up(r.acc_bytes)) : nullptr;
+    ca.acc = r.w.acc; ca.det = r.w.det; ca.counters = r.counters; ca.count_mode = c.o.count_lanes;
     ca.P = c.P; ca.rect = c.g.rect; ca.tiles = c.g.tiles; ca.depth_bits = reinterpret_cast<const uint32_t *>(c.g.depth);
     ca.seg = c.im.seg; ca.asm_walk = r.bwd_asm;
     ca.fill.P = c.P; ca.fill.M = a.M; ca.fill.chunk = r.fill_chunk; ca.fill.radii = a.radii; ca.fill.touched = c.g.touched; ca.fill.mark = c.g.touch_mark;
@@ -784,20 +786,18 @@ int32_t gsr_workspace_sizes(int32_t P, int32_t W, int32_t H, size_t *geom_bytes,
     if (P < 0 || W <= 0 || H <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_workspace_sizes: P=%d W=%d H=%d", P, W, H);
     if (W > 65535 * GSR_TILE_HOST || H > 65535 * GSR_TILE_HOST) return fail(GSR_ERR_INVALID_ARGUMENT, "image too large");
     GeomView g;
-    GSR_TRY(geom_view(nullptr, P, &g));
+    GSR_TRY(view_geom(nullptr, SIZE_MAX, P, &g));
     if (geom_bytes) *geom_bytes = g.total_bytes;
     if (img_bytes) *img_bytes = carve_image(nullptr, W, H).total_bytes;
-    if (bwd_bytes) *bwd_bytes = align_up(acc_rows(P) * GSR_ACC_FLOATS * sizeof(float));
+    if (bwd_bytes) *bwd_bytes = carve_backward(nullptr, P, 0).vis_off;      // the rows, rounded up: neither slots nor vis block
     return GSR_OK;
 }
 
 int32_t gsr_backward_workspace_bytes(int32_t P, int64_t R, size_t *bytes) {
     if (P < 0 || R < 0 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_workspace_bytes: bad argument");
     const Options o{};
-    const size_t acc_bytes = align_up(acc_rows(P) * GSR_ACC_FLOATS * sizeof(float));
-    const size_t det_bytes = o.deterministic_bwd ? (size_t)R * (size_t)(4 / o.bwd_npx) * GSR_ACC_FLOATS * sizeof(float) : 0;
-    // + the dense per-Gaussian stage's list and record buffer (pergauss_bwd.hip), behind the accumulators
-    *bytes = acc_bytes + align_up(det_bytes) + pergauss_vis_bytes(P);
+    // with the dense per-Gaussian stage's list and record buffer (pergauss_bwd.hip), behind the accumulators
+    *bytes = carve_backward(nullptr, P, o.deterministic_bwd ? det_slot_bytes(o, R) : 0).total_bytes;
     return GSR_OK;
 }
 
@@ -830,7 +830,7 @@ int32_t gsr_forward(gsr_stream_t stream, int32_t P, int32_t D, int32_t M, int32_
     GSR_TRY(prefill_take(c.ds, c.s, fill, P, M, &c.pre));
     GSR_TRY(fwd_check(pa, bg, out_color, geom_ws, img_ws, binning_alloc));
     if (P == 0) return hip_rc(hipMemsetAsync(out_color, 0, 3 * (size_t)W * H * sizeof(float), c.s), "memset out_color");   // as upstream: a zero image, not the background
-    GSR_TRY(carve_views(c, geom_ws, geom_bytes, img_ws, img_bytes));
+    GSR_TRY(view_geom(geom_ws, geom_bytes, P, &c.g)); GSR_TRY(view_image(img_ws, img_bytes, W, H, &c.im));
     c.tm.mark(0);                                    // (the stages set the marks that fall between their own launches: 2, 3, 4, 5, 7)
     GSR_TRY(fwd_preprocess(c, pa));
     c.tm.mark(1);
@@ -880,7 +880,7 @@ int32_t gsr_backward(gsr_stream_t stream, int32_t P, int32_t D, int32_t M, int64
     GSR_TRY(bwd_check(r, bg, dL_dpix, geom_ws, img_ws, binning_ws));
     if (P == 0) return GSR_OK;
     Call c(stream, P, W, H, debug);
-    GSR_TRY(carve_views(c, geom_ws, geom_bytes, img_ws, img_bytes));
+    GSR_TRY(view_geom(geom_ws, geom_bytes, P, &c.g)); GSR_TRY(view_image(img_ws, img_bytes, W, H, &c.im));
     GSR_TRY(bwd_workspaces(c, r, binning_ws, binning_bytes));
     bwd_plan(c, r);
     c.tm.mark(8);
@@ -906,8 +906,7 @@ int32_t gsr_composited_mask(gsr_stream_t stream, int32_t P, const void *geom_ws,
     if (P < 0 || (P > 0 && (!geom_ws || !out))) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_composited_mask: bad argument");
     if (P == 0) return GSR_OK;
     GeomView g;
-    GSR_TRY(geom_view(geom_ws, P, &g));
-    if (geom_bytes < g.total_bytes) return fail(GSR_ERR_WORKSPACE, "geom workspace %zu < %zu", geom_bytes, g.total_bytes);
+    GSR_TRY(view_geom(geom_ws, geom_bytes, P, &g));
     return hip_rc(launch_composited_mask(P, g.touched, g.touch_mark, out, (hipStream_t)stream), "composited mask launch");
 }
 
@@ -916,7 +915,7 @@ int32_t gsr_debug_read_geom(gsr_stream_t stream, int32_t P, const void *geom_ws,
     hipStream_t s = (hipStream_t)stream;
     if (P <= 0) return GSR_OK;
     GeomView g;
-    GSR_TRY(geom_view(geom_ws, P, &g));
+    GSR_TRY(view_geom(geom_ws, SIZE_MAX, P, &g));
     HIP_TRY(hipStreamSynchronize(s), "sync");
     float *rec = (float *)malloc((size_t)P * GSR_REC_FLOATS * sizeof(float));
     uint8_t *cl = (uint8_t *)malloc((size_t)P);
@@ -942,7 +941,7 @@ int32_t gsr_debug_read_binning(gsr_stream_t stream, int64_t N, int32_t W, int32_
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipStreamSynchronize(s), "sync");
     if (N > 0 && binning_ws) {
-        BinningView b = carve_binning(const_cast<void *>(binning_ws), N, 0);
+        BinningView b; GSR_TRY(view_lists(binning_ws, SIZE_MAX, N, &b));
         // the 64-bit tile<<32|depth keys only exist in global-sort mode (the other layouts may not even span that region)
         if (keys_sorted) {
             if (g_two_level_sort.load() == 0) HIP_TRY(hipMemcpy(keys_sorted, b.keys_sorted, (size_t)N * 8, hipMemcpyDeviceToHost), "copy keys");
@@ -951,7 +950,7 @@ int32_t gsr_debug_read_binning(gsr_stream_t stream, int64_t N, int32_t W, int32_
         if (point_list) HIP_TRY(hipMemcpy(point_list, b.point_list, (size_t)N * 4, hipMemcpyDeviceToHost), "copy point list");
     }
     if (ranges && img_ws) {
-        ImageView im = carve_image(const_cast<void *>(img_ws), W, H);
+        ImageView im; GSR_TRY(view_image(img_ws, SIZE_MAX, W, H, &im));
         const size_t T = (size_t)grid_dim(W) * grid_dim(H);
         HIP_TRY(hipMemcpy(ranges, im.ranges, T * sizeof(uint2), hipMemcpyDeviceToHost), "copy ranges");
         if (point_list && N > 0) {
@@ -1017,11 +1016,11 @@ int32_t gsr_debug_read_bound_errors(gsr_stream_t stream, int32_t P, const void *
     HIP_TRY(hipStreamSynchronize(s), "sync");
     if (geom_ws && P > 0) {
         GeomView g;
-        GSR_TRY(geom_view(geom_ws, P, &g));
+        GSR_TRY(view_geom(geom_ws, SIZE_MAX, P, &g));
         HIP_TRY(hipMemcpy(out, g.dord.hdr + GSR_DBG_GEOM_WORD, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost), "copy bound words");
     }
     if (img_ws && W > 0 && H > 0) {
-        const ImageView im = carve_image(const_cast<void *>(img_ws), W, H);
+        ImageView im; GSR_TRY(view_image(img_ws, SIZE_MAX, W, H, &im));
         HIP_TRY(hipMemcpy(out + 4, im.seg.hdr + GSR_DBG_SEG_WORD, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost), "copy bound words");
         // self test of the mechanism, on words of its own (seg.hdr[8..11])
         HIP_TRY(hipMemsetAsync(im.seg.hdr + 8, 0, 4 * sizeof(uint32_t), s), "clear self-test words");
@@ -1038,7 +1037,7 @@ int32_t gsr_debug_read_segments(gsr_stream_t stream, int32_t W, int32_t H, const
     hipStream_t s = (hipStream_t)stream;
     if (!img_ws || !summary || W <= 0 || H <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_debug_read_segments: bad argument");
     HIP_TRY(hipStreamSynchronize(s), "sync");
-    ImageView im = carve_image(const_cast<void *>(img_ws), W, H);
+    ImageView im; GSR_TRY(view_image(img_ws, SIZE_MAX, W, H, &im));
     uint32_t *h = (uint32_t *)malloc(GSR_SEG_HDR_WORDS * sizeof(uint32_t));
     if (!h) return fail(GSR_ERR_ALLOC, "host malloc");
     const hipError_t e = hipMemcpy(h, im.seg.hdr, GSR_SEG_HDR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost);
@@ -1060,7 +1059,7 @@ int32_t gsr_debug_read_image_state(gsr_stream_t stream, int32_t W, int32_t H, co
                                    uint32_t *n_contrib) {
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipStreamSynchronize(s), "sync");
-    ImageView im = carve_image(const_cast<void *>(img_ws), W, H);
+    ImageView im; GSR_TRY(view_image(img_ws, SIZE_MAX, W, H, &im));
     const size_t HW = (size_t)W * H;
     if (final_T) HIP_TRY(hipMemcpy(final_T, im.final_T, HW * 4, hipMemcpyDeviceToHost), "copy final_T");
     if (n_contrib) HIP_TRY(hipMemcpy(n_contrib, im.n_contrib, HW * 4, hipMemcpyDeviceToHost), "copy n_contrib");

@@ -41,3 +41,5 @@ inline void with_flag(bool b, F &&f) {
         hipError_t _e = (expr);                                                                               \
         if (_e != hipSuccess) return gsr::fail(GSR_ERR_HIP, "%s: %s (%d)", what, hipGetErrorString(_e), (int)_e); \
     } while (0)
+// a nested check that has left its text already: the caller returns the bare code
+#define GSR_TRY(expr) do { const int32_t _rc = (expr); if (_rc != GSR_OK) return _rc; } while (0)

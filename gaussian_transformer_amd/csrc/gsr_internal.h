@@ -1,7 +1,8 @@
 // gsr_internal.h -- workspace layouts and kernel launchers of the rasterizer (include/gsr.h), shared between gsr_api.hip and the
 // translation units with its kernels.  Nothing here is part of the public ABI.  The other headers' features (loss, Adam, density
-// control, kNN, Chamfer, sequence preparation, rows) keep their launchers file-local, next to their own entry points; they include
-// this file for its helpers (align_up, ceil_log2_u32, GSR_TILE_HOST) only.
+// control, kNN, Chamfer, sequence preparation, rows) keep their launchers and workspace layouts file-local, next to their own entry
+// points, and include this file for its helpers (align_up, ceil_log2_u32, grid_dim, GSR_TILE_HOST) and for Bump, the one carver every
+// layout is written with; depth_maps.hip and pose_grad.hip also view a forward call's workspaces and the accumulator rows through it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -36,6 +37,12 @@ enum { GSR_BOUND_SS_BIG_LIST = 1, GSR_BOUND_SS_ENTRIES = 2, GSR_BOUND_SS_BIN_SIZ
 
 static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline int ceil_log2_u32(uint32_t x) { int b = 0; while ((1u << b) < x && b < 31) b++; return b; }
+static inline int grid_dim(int px) { return (int)(((long long)px + GSR_TILE_HOST - 1) / GSR_TILE_HOST); }      // tiles along an image edge (64-bit: callers ask before W and H are checked)
+struct Bump {      // hands out consecutive 256-byte-aligned pieces of a workspace; base NULL: only the sizes are wanted
+    char *base; size_t off;
+    template <class T> T *take(size_t count) { T *r = take_last<T>(count); off = align_up(off); return r; }
+    template <class T> T *take_last(size_t count) { char *r = base ? base + off : nullptr; off += count * sizeof(T); return (T *)r; }      // a last piece whose end is not rounded up
+};
 
 // Per-Gaussian record gathered by the compositing kernels: 12 floats = 3 x float4.
 //   [0] px  [1] py  [2] conic.xx  [3] conic.xy | [4] conic.yy [5] opacity [6] r [7] g | [8] b [9] depth [10] cull tau [11] replica code of the accumulator rows (bits; 0 = none)
@@ -397,9 +404,23 @@ static inline uint32_t pergauss_vis_cap(int P) {
     const long long c = (long long)P / 4 > 131072 ? (long long)P / 4 : 131072;
     return (uint32_t)(((c < (long long)P ? c : (long long)P) + 63) / 64 * 64);
 }
-static inline size_t pergauss_vis_bytes(int P) {
-    return 256 + (((size_t)P * 4 + 255) / 256 * 256) + (size_t)pergauss_vis_cap(P) * 15 * 16;
-}
+// The backward workspace: accumulator rows | deterministic mode's slots (det_bytes of them; none: det NULL) | the dense variant's vis
+// block.  gsr_depth_backward's workspace starts with the same rows and gsr_pose_backward reads them: both ask this function (det_bytes 0).
+struct BackwardView {
+    float *acc, *det;        // [acc_rows(P)][GSR_ACC_FLOATS] each row
+    size_t acc_bytes;        // of the accumulator rows exactly, not rounded up: what a call that runs neither mode needs of the workspace
+    size_t det_end;          // up to the end of the slots, not rounded up: what deterministic mode needs, and clears
+    size_t vis_off;          // where the vis block starts: the rows and the slots, each rounded up
+    uint32_t *vis_count, *vis_list; float4 *vis_rec; uint32_t vis_cap;      // PergaussBwdArgs's fields of these names
+    size_t total_bytes;      // the end of the records, not rounded up
+};
+BackwardView carve_backward(void *ws, int P, size_t det_bytes);
+
+// ---- a forward call's three workspaces as a later call sees them: carved, and refused (GSR_ERR_WORKSPACE, each text in gsr_api.hip only) when
+// `bytes` is too small.  SIZE_MAX: the caller has no size to hold against (size queries with ws NULL, the debug readers). ----
+int32_t view_geom(const void *ws, size_t bytes, int P, GeomView *g);              // asks rocPRIM for the two temp sizes first (GSR_ERR_HIP)
+int32_t view_image(const void *ws, size_t bytes, int W, int H, ImageView *im);
+int32_t view_lists(const void *ws, size_t bytes, int64_t R, BinningView *b);      // point_list + contrib (list_bytes): what the forward pass leaves; R == 0: nothing to hold
 
 // ssim_loss.hip's per-launch view limit (include/gsr_loss.h: GSR_VIEWS_LOSS_MAX_B, checked equal there)
 #define GSR_VIEWS_MAX_B 16   // == GSR_VIEWS_LOSS_MAX_B: views whose pointers one launch carries in its kernel arguments

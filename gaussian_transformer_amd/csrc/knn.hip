@@ -45,14 +45,12 @@ static hipError_t knn_sort_temp(int N, size_t *bytes) {
 static KnnView carve_knn(void *base, int N, size_t sort_tb) {
     KnnView v;
     const size_t n = (size_t)(N > 0 ? N : 1), nbox = (n + KNN_BOX - 1) / KNN_BOX;
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += align_up(bytes); return r; };
-    v.bbox = (float *)take(6 * sizeof(float));
-    v.codes = (uint32_t *)take(n * 4); v.codes_sorted = (uint32_t *)take(n * 4); v.idx_sorted = (uint32_t *)take(n * 4);
-    v.box_min = (float *)take(nbox * 3 * 4); v.box_max = (float *)take(nbox * 3 * 4);
-    v.sort_temp = take(sort_tb); v.sort_temp_bytes = sort_tb;
-    v.total_bytes = off;
+    Bump w = {(char *)base, 0};
+    v.bbox = w.take<float>(6);
+    v.codes = w.take<uint32_t>(n); v.codes_sorted = w.take<uint32_t>(n); v.idx_sorted = w.take<uint32_t>(n);
+    v.box_min = w.take<float>(nbox * 3); v.box_max = w.take<float>(nbox * 3);
+    v.sort_temp = w.take<char>(sort_tb); v.sort_temp_bytes = sort_tb;
+    v.total_bytes = w.off;
     return v;
 }
 

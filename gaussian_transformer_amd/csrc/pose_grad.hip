@@ -239,14 +239,10 @@ int32_t gsr_pose_backward(gsr_stream_t stream, int32_t kind, int32_t P, int32_t 
         if (shs && (!campos || D < 0 || D > 3 || M < (D + 1) * (D + 1))) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: SH inputs inconsistent", who);
     }
     if ((reinterpret_cast<uintptr_t>(acc_ws) | reinterpret_cast<uintptr_t>(ws)) & 15) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: workspaces must be 16-byte aligned", who);
-    const size_t need_acc = acc_rows(P) * GSR_ACC_FLOATS * sizeof(float);
-    if (acc_bytes < need_acc) return fail(GSR_ERR_WORKSPACE, "accumulator workspace %zu < %zu", acc_bytes, need_acc);
+    const BackwardView rows = carve_backward(const_cast<void *>(acc_ws), P, 0);      // the backward (or depth) workspace a reverse pass has filled
+    if (acc_bytes < rows.acc_bytes) return fail(GSR_ERR_WORKSPACE, "accumulator workspace %zu < %zu", acc_bytes, rows.acc_bytes);
     if (ws_bytes < workspace_bytes(P)) return fail(GSR_ERR_WORKSPACE, "pose workspace %zu < %zu", ws_bytes, workspace_bytes(P));
-    size_t stb = 0, dtb = 0;
-    HIP_TRY(scan_temp_bytes(P, &stb), "scan temp query");
-    HIP_TRY(depth_sort_temp_bytes(P, &dtb), "depth sort temp query");
-    const GeomView g = carve_geom(const_cast<void *>(geom_ws), P, stb, dtb);
-    if (geom_bytes < g.total_bytes) return fail(GSR_ERR_WORKSPACE, "geom workspace %zu < %zu", geom_bytes, g.total_bytes);
+    GeomView g; GSR_TRY(view_geom(geom_ws, geom_bytes, P, &g));
 
     PoseArgs a;
     memset(&a, 0, sizeof a);
@@ -255,7 +251,7 @@ int32_t gsr_pose_backward(gsr_stream_t stream, int32_t kind, int32_t P, int32_t 
     a.viewmatrix = viewmatrix; a.projmatrix = projmatrix; a.campos = campos;
     a.scale_modifier = scale_modifier; a.tanfovx = tanfovx; a.tanfovy = tanfovy;
     a.radii = radii; a.clamped = g.clamped; a.touched = g.touched; a.touch_mark = g.touch_mark; a.hot = g.hot;
-    a.acc = (const float *)acc_ws; a.rows = (double *)ws;
+    a.acc = rows.acc; a.rows = (double *)ws;
     const dim3 grid((unsigned)pose_rows(P)), block(256);
     if (!sh) hipLaunchKernelGGL((pose_terms_kernel<0, false>), grid, block, 0, s, a);
     else with_sh_degree(D, [&](auto DD) { hipLaunchKernelGGL((pose_terms_kernel<decltype(DD)::value, true>), grid, block, 0, s, a); });

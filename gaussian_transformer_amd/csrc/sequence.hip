@@ -11,6 +11,7 @@
 
 #include "../../include/gsr_sequence.h"
 #include "gsr_host.h"
+#include "gsr_internal.h"
 #include "pergauss_chain.h"
 
 namespace gsr {
@@ -92,15 +93,11 @@ static hipError_t carve_box_ws(void *base, int P, int n, BoxWs &w) {
                                              rocprim::counting_iterator<uint32_t>(0), (uint32_t *)nullptr, np, 0u,
                                              (unsigned)box_bits(n), (hipStream_t)0, false);
     if (e != hipSuccess) return e;
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += align_up(bytes); return r; };
-    w.keys = (uint32_t *)take(np * 4);
-    w.skeys = (uint32_t *)take(np * 4);
-    w.sidx = (uint32_t *)take(np * 4);
-    w.temp = take(tb > 0 ? tb : 1);
+    Bump b = {(char *)base, 0};
+    w.keys = b.take<uint32_t>(np); w.skeys = b.take<uint32_t>(np); w.sidx = b.take<uint32_t>(np);
+    w.temp = b.take<char>(tb > 0 ? tb : 1);
     w.temp_bytes = tb;
-    w.total = off;
+    w.total = b.off;
     return hipSuccess;
 }
 

@@ -292,22 +292,20 @@ static hipError_t launch_l1_ssim_backward(int C, int H, int W, const float *img,
 
 // ---- B views in one launch (gsr_views_loss_*) ----
 // workspace: dmaps [3][B*3][H][W] | partial [B*3*tiles][3] | view_sums [B][3] double | ticket (one int on a line of its own)
-struct ViewsWs { float *dmaps, *partial; double *view_sums; int *ticket; };
-static inline size_t views_tiles(int H, int W) { return (size_t)((W + SSIM_T - 1) / SSIM_T) * ((H + SSIM_T - 1) / SSIM_T); }
-static inline ViewsWs views_carve(void *ws, int B, int H, int W, size_t *bytes) {
-    ViewsWs v;
-    size_t off = 0;
-    v.dmaps = (float *)((char *)ws + off); off += align_up((size_t)9 * B * H * W * sizeof(float));
-    v.partial = (float *)((char *)ws + off); off += align_up((size_t)9 * B * views_tiles(H, W) * sizeof(float));
-    v.view_sums = (double *)((char *)ws + off); off += align_up((size_t)3 * B * sizeof(double));
-    v.ticket = (int *)((char *)ws + off); off += 256;
-    if (bytes) *bytes = off;
-    return v;
+struct ViewsWs { float *dmaps, *partial; double *view_sums; int *ticket; size_t total_bytes; };
+static inline size_t ssim_tiles(int H, int W) { return (size_t)((W + SSIM_T - 1) / SSIM_T) * ((H + SSIM_T - 1) / SSIM_T); }      // blocks per image plane
+static inline ViewsWs views_carve(void *ws, int B, int H, int W) {
+    Bump w = {(char *)ws, 0};
+    float *const dmaps = w.take<float>((size_t)9 * B * H * W), *const partial = w.take<float>((size_t)9 * B * ssim_tiles(H, W));
+    double *const view_sums = w.take<double>((size_t)3 * B); int *const ticket = w.take<int>(1);      // the ticket's piece is a 256-byte line: nothing shares it
+    return {dmaps, partial, view_sums, ticket, w.off};
 }
-static size_t views_loss_workspace_bytes(int B, int H, int W) {
-    size_t n = 0;
-    views_carve(nullptr, B, H, W, &n);
-    return n;
+// one image (gsr_l1_ssim_*): dmaps [3][C][H][W] (the backward pass reads them: first) | partial [C*tiles][2]
+struct L1Ws { float *dmaps, *partial; size_t total_bytes; };
+static inline L1Ws l1_carve(void *ws, int C, int H, int W) {
+    Bump w = {(char *)ws, 0};
+    float *const dmaps = w.take<float>((size_t)3 * C * H * W), *const partial = w.take<float>(ssim_tiles(H, W) * C * 2);
+    return {dmaps, partial, w.off};
 }
 
 struct ViewsFwdArgs {
@@ -422,10 +420,10 @@ __global__ __launch_bounds__(256) void views_loss_bwd_kernel(ViewsBwdArgs a) {
     }
 }
 
-// B, H, W >= 1 and no NULL among imgs / gts (checked by gsr_views_loss_forward); ws holds views_loss_workspace_bytes(B, H, W)
+// B, H, W >= 1 and no NULL among imgs / gts (checked by gsr_views_loss_forward); ws holds views_carve(., B, H, W).total_bytes
 static hipError_t launch_views_loss_forward(int B, int H, int W, const float *const *imgs, const float *const *gts, float w_l1, float w_ssim,
                                      int sanitize, float *out3, float *terms, void *ws, hipStream_t s) {
-    const ViewsWs w = views_carve(ws, B, H, W, nullptr);
+    const ViewsWs w = views_carve(ws, B, H, W);
     ViewsFwdArgs a;
     a.dmaps = w.dmaps; a.partial = w.partial; a.ticket = w.ticket; a.H = H; a.W = W; a.n_all = (size_t)3 * B * H * W;
     a.wts = make_view_weights();
@@ -445,7 +443,7 @@ static hipError_t launch_views_loss_forward(int B, int H, int W, const float *co
 
 static hipError_t launch_views_loss_backward(int B, int H, int W, const float *const *imgs, const float *const *gts, float w_l1, float w_ssim,
                                       int sanitize, const float *grad_loss, const void *ws, float *const *grad_imgs, hipStream_t s) {
-    const ViewsWs w = views_carve(const_cast<void *>(ws), B, H, W, nullptr);
+    const ViewsWs w = views_carve(const_cast<void *>(ws), B, H, W);
     ViewsBwdArgs a;
     a.dmaps = w.dmaps; a.grad_loss = grad_loss; a.H = H; a.W = W; a.n_all = (size_t)3 * B * H * W;
     a.w_l1 = w_l1; a.w_ssim = w_ssim; a.inv_n = 1.0 / ((double)3 * B * H * W);
@@ -475,11 +473,9 @@ using namespace gsr;
 extern "C" {
 
 // ---- fused training loss (include/gsr_loss.h) ----
-static inline size_t loss_blocks(int C, int H, int W) { return (size_t)((W + 15) / 16) * ((H + 15) / 16) * C; }
-
 int32_t gsr_l1_ssim_workspace(int32_t C, int32_t H, int32_t W, size_t *bytes) {
     if (C <= 0 || H <= 0 || W <= 0 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_l1_ssim_workspace: bad argument");
-    *bytes = align_up((size_t)3 * C * H * W * sizeof(float)) + align_up(loss_blocks(C, H, W) * 2 * sizeof(float));
+    *bytes = l1_carve(nullptr, C, H, W).total_bytes;
     return GSR_OK;
 }
 
@@ -489,9 +485,8 @@ int32_t gsr_l1_ssim_forward(gsr_stream_t stream, int32_t C, int32_t H, int32_t W
     if (gsr_l1_ssim_workspace(C, H, W, &need) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
     if (!img || !gt || !out3 || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_l1_ssim_forward: null pointer");
     if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "loss workspace %zu < %zu", ws_bytes, need);
-    float *dmaps = (float *)ws;
-    float *partial = (float *)((char *)ws + align_up((size_t)3 * C * H * W * sizeof(float)));
-    HIP_TRY(launch_l1_ssim_forward(C, H, W, img, gt, lambda_dssim, dmaps, partial, out3, (hipStream_t)stream), "l1+ssim forward launch");
+    const L1Ws w = l1_carve(ws, C, H, W);
+    HIP_TRY(launch_l1_ssim_forward(C, H, W, img, gt, lambda_dssim, w.dmaps, w.partial, out3, (hipStream_t)stream), "l1+ssim forward launch");
     return GSR_OK;
 }
 
@@ -501,7 +496,7 @@ int32_t gsr_l1_ssim_backward(gsr_stream_t stream, int32_t C, int32_t H, int32_t 
     if (gsr_l1_ssim_workspace(C, H, W, &need) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
     if (!img || !gt || !ws || !grad_img) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_l1_ssim_backward: null pointer");
     if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "loss workspace %zu < %zu", ws_bytes, need);
-    HIP_TRY(launch_l1_ssim_backward(C, H, W, img, gt, lambda_dssim, (const float *)ws, grad_loss, grad_img, (hipStream_t)stream),
+    HIP_TRY(launch_l1_ssim_backward(C, H, W, img, gt, lambda_dssim, l1_carve(const_cast<void *>(ws), C, H, W).dmaps, grad_loss, grad_img, (hipStream_t)stream),
             "l1+ssim backward launch");
     return GSR_OK;
 }
@@ -522,9 +517,9 @@ static int views_loss_check(const char *who, int32_t B, int32_t H, int32_t W, co
 
 int32_t gsr_views_loss_workspace(int32_t B, int32_t H, int32_t W, size_t *bytes) {
     if (B < 1 || H < 1 || W < 1 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_workspace: bad argument (B=%d H=%d W=%d)", B, H, W);
-    if ((H + 15) / 16 > 65535 || (size_t)3 * loss_blocks(1, H, W) > (size_t)INT32_MAX)
+    if ((H + 15) / 16 > 65535 || (size_t)3 * ssim_tiles(H, W) > (size_t)INT32_MAX)
         return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_workspace: image %d x %d too large", W, H);
-    *bytes = views_loss_workspace_bytes(B, H, W);
+    *bytes = views_carve(nullptr, B, H, W).total_bytes;
     return GSR_OK;
 }
 

@@ -41,3 +41,11 @@ def test_workspace_sizes_are_what_they_were():
             assert lib.gsr_workspace_sizes(P, W, H, C.byref(g), C.byref(i), C.byref(b)) == 0
             assert (g.value, i.value, b.value) == (geom[P], img[W, H], bwd[P]), (P, W, H)
             assert lib.gsr_binning_bytes(P, W, H, C.byref(n)) == 0 and n.value == binning[P], (P, W, H)
+    # likewise the three other queries that ask rocPRIM, recorded on an MI355X from the library before kNN's, the box sort's and the
+    # densify plan's carve functions took that allocator over from their own (the queries without rocPRIM: tests/test_workspace_sizes_host.py)
+    for name, want in (("gsr_knn_workspace", {(1,): 1792, (1024,): 13312, (1025,): 22272, (100000,): 2003200}),                 # N
+                       ("gsr_densify_plan_workspace", {(1, 1): 4352, (1024, 2): 37376, (100000, 2): 3309056}),                # (P, N)
+                       ("gsr_box_sort_workspace", {(1, 1): 1024, (1024, 8): 12544, (100000, 128): 2000384})):                # (P, n)
+        for args, bytes_ in want.items():
+            n = C.c_size_t()
+            assert getattr(lib, name)(*args, C.byref(n)) == 0 and n.value == bytes_, (name, args, n.value)
