@@ -196,6 +196,63 @@ def check(rc: int, what: str) -> None:
         raise GsrError(f"{what} failed (code {rc}): {msg.decode(errors='replace') if msg else ''}")
 
 
+# ---- the one way to call the library.  torch is imported inside: this module loads without it. ----
+
+def call(name: str, *args) -> None:
+    """The native function `name` on `args`, checked.  `load` is looked up per call (the host tests replace it)."""
+    check(getattr(load(), name)(*args), name)
+
+
+def stream(dev):
+    """The raw handle of the current stream on `dev`."""
+    import torch
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def ptr(t):
+    """The device pointer of a dense tensor; NULL for None and for an empty tensor."""
+    if t is None or t.numel() == 0:
+        return None
+    if not t.is_contiguous():      # the C ABI takes dense row-major buffers; the public entry points make them so
+        raise GsrError(f"non-contiguous tensor of shape {tuple(t.shape)} passed to the native rasterizer")
+    return t.data_ptr()
+
+
+def ptr_array(ptrs):
+    """A host array of device pointers (None: NULL)."""
+    return (C.c_void_p * len(ptrs))(*ptrs)
+
+
+def workspace_bytes(sizer: str, *sizes) -> int:
+    """What the library's `sizer` (a gsr_*_workspace or gsr_*_workspace_bytes) asks for at these sizes."""
+    n = C.c_size_t()
+    check(getattr(load(), sizer)(*sizes, C.byref(n)), sizer)
+    return n.value
+
+
+def workspace(sizer: str, dev, *sizes):
+    """A uint8 tensor on `dev` of as many bytes as `sizer` asks for, and of one byte where it asks for none: a workspace always has
+    an address, so every call site passes ptr(ws), ws.numel().  (Only gsr_chamfer_workspace can say 0, for an empty batch, and
+    gsr_chamfer_forward returns before it looks at the workspace then.)"""
+    import torch
+    return torch.empty((max(workspace_bytes(sizer, *sizes), 1),), dtype=torch.uint8, device=dev)
+
+
+def require_tensor(who: str, name: str, t, dtype=None) -> None:
+    """`t` is a torch.Tensor of `dtype` (None: float32), or GsrError naming the argument."""
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    if not isinstance(t, torch.Tensor):
+        raise GsrError(f"{who}: {name} must be a torch.Tensor, got {type(t).__name__}")
+    if t.dtype != dtype:
+        raise GsrError(f"{who}: {name} must be {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
+
+
+def require_hip(who: str, name: str, t) -> None:
+    if t.device.type != "cuda":
+        raise GsrError(f"{who}: {name} must be on a HIP device, got {t.device} (no CPU fallback)")
+
+
 def set_option(name: str, value: int) -> None:
     """Process-wide tuning knob of the native library (include/gsr.h: gsr_set_option)."""
     check(load().gsr_set_option(name.encode(), int(value)), f"gsr_set_option({name})")

@@ -10,8 +10,6 @@ on rows of 26 floats, then back-propagates (:245).  Squared Euclidean distance o
 (1..64), nearest row of the other set and its index, both ways; the lowest index wins a tie.  No CPU fallback."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -24,8 +22,7 @@ def _validate(xyz1, xyz2) -> None:
     for name, t in (("xyz1", xyz1), ("xyz2", xyz2)):
         if not isinstance(t, torch.Tensor):
             raise _lib.GsrError(f"ChamferDistance: {name} must be a torch.Tensor, got {type(t).__name__}")
-        if t.device.type != "cuda":
-            raise _lib.GsrError(f"ChamferDistance: {name} must be on a HIP device, got {t.device} (no CPU fallback)")
+        _lib.require_hip("ChamferDistance", name, t)
         if t.dim() != 3:
             raise _lib.GsrError(f"ChamferDistance: {name} must have shape [B, N, D], got {tuple(t.shape)}")
         if not t.is_floating_point():
@@ -44,10 +41,6 @@ def _validate_shapes(s1, s2) -> None:
         raise _lib.GsrError(f"ChamferDistance: xyz1 has D={s1[2]} features per row, supported: 1..{MAX_D}")
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None and t.numel() else None
-
-
 class ChamferDistanceFunction(torch.autograd.Function):
     """float32 tensors on one HIP device in, (dist1 [B,N], dist2 [B,M], idx1 [B,N] int32, idx2 [B,M] int32) out."""
 
@@ -56,7 +49,7 @@ class ChamferDistanceFunction(torch.autograd.Function):
         _validate(xyz1, xyz2)
         if xyz1.dtype != torch.float32 or xyz2.dtype != torch.float32:
             raise _lib.GsrError("ChamferDistanceFunction: xyz1 and xyz2 must be float32 (ChamferDistance casts for you)")
-        lib = _lib.load()
+        ptr = _lib.ptr
         x1, x2 = xyz1.detach().contiguous(), xyz2.detach().contiguous()
         (B, N, D), M = x1.shape, int(x2.shape[1])
         dev = x1.device
@@ -64,13 +57,10 @@ class ChamferDistanceFunction(torch.autograd.Function):
         dist2 = torch.empty((B, M), dtype=torch.float32, device=dev)
         idx1 = torch.empty((B, N), dtype=torch.int32, device=dev)
         idx2 = torch.empty((B, M), dtype=torch.int32, device=dev)
-        nb = C.c_size_t()
-        _lib.check(lib.gsr_chamfer_workspace(B, N, M, C.byref(nb)), "gsr_chamfer_workspace")
         with torch.cuda.device(dev):
-            ws = torch.empty((max(nb.value, 1),), dtype=torch.uint8, device=dev)
-            _lib.check(lib.gsr_chamfer_forward(torch.cuda.current_stream(dev).cuda_stream, B, N, M, D, _ptr(x1), _ptr(x2),
-                                               _ptr(dist1), _ptr(dist2), _ptr(idx1), _ptr(idx2), ws.data_ptr(), ws.numel()),
-                       "gsr_chamfer_forward")
+            ws = _lib.workspace("gsr_chamfer_workspace", dev, B, N, M)
+            _lib.call("gsr_chamfer_forward", _lib.stream(dev), B, N, M, D, ptr(x1), ptr(x2), ptr(dist1), ptr(dist2), ptr(idx1), ptr(idx2),
+                      ptr(ws), ws.numel())
         ctx.save_for_backward(x1, x2, idx1, idx2)
         ctx.mark_non_differentiable(idx1, idx2)
         ctx.set_materialize_grads(False)          # an unused dist arrives as None and goes down as NULL (= zeros)
@@ -80,16 +70,14 @@ class ChamferDistanceFunction(torch.autograd.Function):
     def backward(ctx, g1, g2, _gi1, _gi2):
         x1, x2, idx1, idx2 = ctx.saved_tensors
         (B, N, D), M = x1.shape, int(x2.shape[1])
-        dev = x1.device
-        lib = _lib.load()
+        dev, ptr = x1.device, _lib.ptr
         g1 = None if g1 is None else g1.to(torch.float32).contiguous()
         g2 = None if g2 is None else g2.to(torch.float32).contiguous()
         dx1 = torch.empty_like(x1) if ctx.needs_input_grad[0] else None      # fully written by the call
         dx2 = torch.empty_like(x2) if ctx.needs_input_grad[1] else None
         with torch.cuda.device(dev):
-            _lib.check(lib.gsr_chamfer_backward(torch.cuda.current_stream(dev).cuda_stream, B, N, M, D, _ptr(x1), _ptr(x2),
-                                                _ptr(idx1), _ptr(idx2), _ptr(g1), _ptr(g2), _ptr(dx1), _ptr(dx2)),
-                       "gsr_chamfer_backward")
+            _lib.call("gsr_chamfer_backward", _lib.stream(dev), B, N, M, D, ptr(x1), ptr(x2), ptr(idx1), ptr(idx2), ptr(g1), ptr(g2),
+                      ptr(dx1), ptr(dx2))
         return dx1, dx2
 
 

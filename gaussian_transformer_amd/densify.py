@@ -13,7 +13,6 @@ data-parallel ranks that seed it identically split identically (the reference us
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from dataclasses import dataclass
 from typing import Callable, Dict, Optional
@@ -284,11 +283,11 @@ class FusedDensityController(DensityController):
             raise _lib.GsrError("FusedDensityController.record: radii / visibility must have P rows on the gradient's device")
         if P == 0:
             return
+        ptr = _lib.ptr
         with torch.cuda.device(grad.device):
-            stream = torch.cuda.current_stream(grad.device).cuda_stream
-            _lib.check(_lib.load().gsr_density_record(stream, P, grad.data_ptr(), max(int(grad.stride(0)), 2), radii.data_ptr(),
-                                                      visibility.data_ptr() if visibility is not None else None,
-                                                      accum.data_ptr(), denom.data_ptr(), mx.data_ptr()), "gsr_density_record")
+            # grad.data_ptr(), not ptr(grad): the one strided tensor that crosses the boundary, handed over with its row stride
+            _lib.call("gsr_density_record", _lib.stream(grad.device), P, grad.data_ptr(), max(int(grad.stride(0)), 2), ptr(radii),
+                      ptr(visibility), ptr(accum), ptr(denom), ptr(mx))
 
     def _reset_statistics(self, P: int, dev) -> None:
         m = self.model
@@ -310,22 +309,20 @@ class FusedDensityController(DensityController):
         if P == 0:
             self._reset_statistics(0, dev)
             return {"cloned": 0, "split": 0, "pruned": 0}
-        lib = _lib.load()
         f32 = lambda v: float(np.float32(v))       # torch compares a float32 tensor with float32(number)
+        ptr = _lib.ptr
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
-            need = C.c_size_t(0)
-            _lib.check(lib.gsr_densify_plan_workspace(P, N, C.byref(need)), "gsr_densify_plan_workspace")
-            if self._ws is None or self._ws.numel() < need.value or self._ws.device != dev:
-                self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+            stream = torch.cuda.current_stream(dev)        # the object, not only _lib.stream(dev): it is waited for below
+            need = _lib.workspace_bytes("gsr_densify_plan_workspace", P, N)
+            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)        # kept across calls: not _lib.workspace()
             if self._counts is None:
                 self._counts = torch.zeros(4, dtype=torch.int32).pin_memory()
             ws = self._ws
             # 1. plan
-            _lib.check(lib.gsr_densify_plan(stream.cuda_stream, P, olds["opacity"].data_ptr(), olds["scaling"].data_ptr(), accum.data_ptr(),
-                                            denom.data_ptr(), f32(max_grad), f32(min_opacity), f32(self.opt.percent_dense * extent),
-                                            f32(0.1 * extent) if max_screen_size else -1.0, N, self._counts.data_ptr(), ws.data_ptr(),
-                                            ws.numel()), "gsr_densify_plan")
+            _lib.call("gsr_densify_plan", _lib.stream(dev), P, ptr(olds["opacity"]), ptr(olds["scaling"]), ptr(accum), ptr(denom),
+                      f32(max_grad), f32(min_opacity), f32(self.opt.percent_dense * extent),
+                      f32(0.1 * extent) if max_screen_size else -1.0, N, ptr(self._counts), ptr(ws), ws.numel())
             # 2. the only host wait of the call
             stream.synchronize()
             n_clone, n_split, n_pruned, P_new = (int(v) for v in self._counts.tolist())
@@ -345,17 +342,15 @@ class FusedDensityController(DensityController):
                 new[n] = torch.empty(shape, device=dev)
                 states[n] = (torch.empty(shape, device=dev), torch.empty(shape, device=dev)) if has else None
                 width = old[0].numel()
-                ptr = lambda t: t.data_ptr() if t.numel() else None
                 if width:
-                    descs.append(_lib.DensityGroup(old.data_ptr(), state["exp_avg"].data_ptr() if has else None,
-                                                   state["exp_avg_sq"].data_ptr() if has else None, ptr(new[n]),
-                                                   ptr(states[n][0]) if has else None, ptr(states[n][1]) if has else None, width, _ROLE.get(n, _lib.DENSITY_COPY)))
+                    moments = ((state["exp_avg"], state["exp_avg_sq"]) + states[n]) if has else (None,) * 4
+                    descs.append(_lib.DensityGroup(ptr(old), ptr(moments[0]), ptr(moments[1]), ptr(new[n]), ptr(moments[2]), ptr(moments[3]),
+                                                   width, _ROLE.get(n, _lib.DENSITY_COPY)))
             # 5. apply
             if P_new:
                 arr = (_lib.DensityGroup * len(descs))(*descs)
-                _lib.check(lib.gsr_densify_apply(stream.cuda_stream, P, N, n_split, P_new, len(descs), arr, olds["scaling"].data_ptr(),
-                                                 olds["rotation"].data_ptr(), noise.data_ptr() if noise.numel() else None, ws.data_ptr(), ws.numel()),
-                           "gsr_densify_apply")
+                _lib.call("gsr_densify_apply", _lib.stream(dev), P, N, n_split, P_new, len(descs), arr, ptr(olds["scaling"]),
+                          ptr(olds["rotation"]), ptr(noise), ptr(ws), ws.numel())
         # 6. install, as _remap does
         for g in self.optimizer.param_groups:
             n, old = g["name"], g["params"][0]

@@ -13,6 +13,8 @@ import math
 import torch
 import torch.nn.functional as F
 
+from . import _lib
+
 LAMBDA_DSSIM = 0.2
 
 _window_cache = {}
@@ -68,9 +70,6 @@ class _FusedL1SSIM(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, image, gt_image, lambda_dssim):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
         dev = image.device
         if dev.type != "cuda":
             raise _lib.GsrError(f"fused_l1_ssim_loss needs tensors on a HIP device, got {dev} (use training_loss for the torch path)")
@@ -78,13 +77,11 @@ class _FusedL1SSIM(torch.autograd.Function):
             raise _lib.GsrError("fused_l1_ssim_loss: image and gt_image must be float32 [C,H,W] tensors of equal shape")
         img = image.contiguous(); gt = gt_image.to(dev).contiguous()
         Cn, H, W = (int(x) for x in img.shape)
-        nb = C.c_size_t()
-        _lib.check(lib.gsr_l1_ssim_workspace(Cn, H, W, C.byref(nb)), "gsr_l1_ssim_workspace")
         with torch.cuda.device(dev):
-            ws = torch.empty((nb.value,), dtype=torch.uint8, device=dev)
+            ws = _lib.workspace("gsr_l1_ssim_workspace", dev, Cn, H, W)
             out = torch.empty((3,), dtype=torch.float32, device=dev)
-            _lib.check(lib.gsr_l1_ssim_forward(torch.cuda.current_stream(dev).cuda_stream, Cn, H, W, img.data_ptr(), gt.data_ptr(),
-                                               float(lambda_dssim), out.data_ptr(), ws.data_ptr(), nb.value), "gsr_l1_ssim_forward")
+            _lib.call("gsr_l1_ssim_forward", _lib.stream(dev), Cn, H, W, _lib.ptr(img), _lib.ptr(gt), float(lambda_dssim), _lib.ptr(out),
+                      _lib.ptr(ws), ws.numel())
         ctx.save_for_backward(img, gt, ws)
         ctx.lambda_dssim = float(lambda_dssim)
         ctx.terms = out
@@ -92,17 +89,14 @@ class _FusedL1SSIM(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss):
-        from . import _lib
-        lib = _lib.load()
         img, gt, ws = ctx.saved_tensors
         dev = img.device
         Cn, H, W = (int(x) for x in img.shape)
         with torch.cuda.device(dev):
             g = grad_loss.to(device=dev, dtype=torch.float32).contiguous().reshape(1)
             grad = torch.empty_like(img)
-            _lib.check(lib.gsr_l1_ssim_backward(torch.cuda.current_stream(dev).cuda_stream, Cn, H, W, img.data_ptr(), gt.data_ptr(),
-                                                ctx.lambda_dssim, g.data_ptr(), ws.data_ptr(), ws.numel(), grad.data_ptr()),
-                       "gsr_l1_ssim_backward")
+            _lib.call("gsr_l1_ssim_backward", _lib.stream(dev), Cn, H, W, _lib.ptr(img), _lib.ptr(gt), ctx.lambda_dssim, _lib.ptr(g),
+                      _lib.ptr(ws), ws.numel(), _lib.ptr(grad))
         return grad, None, None
 
 
@@ -125,10 +119,8 @@ STACKED_W_SSIM = 0.2 * 0.1
 def _as_view_inputs(who: str, name: str, x):
     """`x` as a list of tensors, each [3,H,W] (one view) or [k,3,H,W] (k views): a sequence of B images or one [B,3,H,W] tensor.
     Types, dtypes and shapes only; returns (tensors, number of views, (H, W))."""
-    from . import _lib
     if isinstance(x, torch.Tensor):
-        if x.dtype != torch.float32:
-            raise _lib.GsrError(f"{who}: {name} must be float32, got {str(x.dtype).replace('torch.', '')}")
+        _lib.require_tensor(who, name, x)
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1 or x.shape[2] < 1 or x.shape[3] < 1:
             raise _lib.GsrError(f"{who}: {name} must be a sequence of [3,H,W] tensors or one [B,3,H,W] tensor with B >= 1, got shape {tuple(x.shape)}")
         return [x], int(x.shape[0]), (int(x.shape[2]), int(x.shape[3]))
@@ -137,10 +129,7 @@ def _as_view_inputs(who: str, name: str, x):
     if len(x) == 0:
         raise _lib.GsrError(f"{who}: {name} is empty (at least one view is needed)")
     for i, t in enumerate(x):
-        if not isinstance(t, torch.Tensor):
-            raise _lib.GsrError(f"{who}: {name}[{i}] must be a torch.Tensor, got {type(t).__name__}")
-        if t.dtype != torch.float32:
-            raise _lib.GsrError(f"{who}: {name}[{i}] must be float32, got {str(t.dtype).replace('torch.', '')}")
+        _lib.require_tensor(who, f"{name}[{i}]", t)
         if t.dim() != 3 or t.shape[0] != 3 or t.shape[1] < 1 or t.shape[2] < 1:
             raise _lib.GsrError(f"{who}: {name}[{i}] must have shape [3,H,W], got {tuple(t.shape)}")
         if tuple(t.shape) != tuple(x[0].shape):
@@ -150,7 +139,6 @@ def _as_view_inputs(who: str, name: str, x):
 
 def _validate_views(who: str, images, targets):
     """Types, dtypes, shapes, equal view sizes and matching counts first, devices last (a CPU test can check every message)."""
-    from . import _lib
     imgs, B, hw = _as_view_inputs(who, "images", images)
     gts, Bt, hwt = _as_view_inputs(who, "targets", targets)
     if B != Bt:
@@ -160,8 +148,7 @@ def _validate_views(who: str, images, targets):
     for name, ts in (("images", imgs), ("targets", gts)):
         for i, t in enumerate(ts):
             label = f"{name}[{i}]" if t.dim() == 3 else name
-            if t.device.type != "cuda":
-                raise _lib.GsrError(f"{who}: {label} must be on a HIP device, got {t.device} (no CPU fallback)")
+            _lib.require_hip(who, label, t)
             if t.device != imgs[0].device:
                 raise _lib.GsrError(f"{who}: all views must be on one device: {label} is on {t.device}, the first image on {imgs[0].device}")
     return imgs, gts, B, hw
@@ -172,34 +159,23 @@ def _view_pointers(tensors):
     ptrs = []
     for t in tensors:
         if t.dim() == 3:
-            ptrs.append(t.data_ptr())
+            ptrs.append(_lib.ptr(t))
         else:
-            step = t.stride(0) * t.element_size()
-            ptrs.extend(t.data_ptr() + b * step for b in range(t.shape[0]))
+            base, step = _lib.ptr(t), t.stride(0) * t.element_size()
+            ptrs.extend(base + b * step for b in range(t.shape[0]))
     return ptrs
-
-
-def _pointer_array(ptrs):
-    import ctypes as C
-    return (C.c_void_p * len(ptrs))(*ptrs)
 
 
 def _views_forward(imgs, gts, B, hw, w_l1, w_ssim, sanitize):
     """imgs, gts: contiguous tensors on one HIP device.  Returns (out3, terms [B,3], workspace), enqueued on the current stream."""
-    import ctypes as C
-    from . import _lib
-    lib = _lib.load()
     dev = imgs[0].device
-    nb = C.c_size_t()
-    _lib.check(lib.gsr_views_loss_workspace(B, hw[0], hw[1], C.byref(nb)), "gsr_views_loss_workspace")
     with torch.cuda.device(dev):
-        ws = torch.empty((nb.value,), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace("gsr_views_loss_workspace", dev, B, hw[0], hw[1])
         out = torch.empty((3,), dtype=torch.float32, device=dev)
         terms = torch.empty((B, 3), dtype=torch.float32, device=dev)
-        _lib.check(lib.gsr_views_loss_forward(torch.cuda.current_stream(dev).cuda_stream, B, hw[0], hw[1],
-                                              _pointer_array(_view_pointers(imgs)), _pointer_array(_view_pointers(gts)),
-                                              float(w_l1), float(w_ssim), 1 if sanitize else 0, out.data_ptr(), terms.data_ptr(),
-                                              ws.data_ptr(), nb.value), "gsr_views_loss_forward")
+        _lib.call("gsr_views_loss_forward", _lib.stream(dev), B, hw[0], hw[1],
+                  _lib.ptr_array(_view_pointers(imgs)), _lib.ptr_array(_view_pointers(gts)),
+                  float(w_l1), float(w_ssim), 1 if sanitize else 0, _lib.ptr(out), _lib.ptr(terms), _lib.ptr(ws), ws.numel())
     return out, terms, ws
 
 
@@ -220,8 +196,6 @@ class _MultiViewLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss, _grad_terms):
-        from . import _lib
-        lib = _lib.load()
         w_l1, w_ssim, sanitize, n_img, B, hw = ctx.cfg
         ws, *rest = ctx.saved_tensors
         imgs, gts = rest[:n_img], rest[n_img:]
@@ -238,10 +212,9 @@ class _MultiViewLoss(torch.autograd.Function):
                     grads.append(None)
                     gptrs.extend([None] * k)                 # NULL: the kernel stores nothing for this view
             if any(p is not None for p in gptrs):
-                _lib.check(lib.gsr_views_loss_backward(torch.cuda.current_stream(dev).cuda_stream, B, hw[0], hw[1],
-                                                       _pointer_array(_view_pointers(imgs)), _pointer_array(_view_pointers(gts)),
-                                                       w_l1, w_ssim, 1 if sanitize else 0, g.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                       _pointer_array(gptrs)), "gsr_views_loss_backward")
+                _lib.call("gsr_views_loss_backward", _lib.stream(dev), B, hw[0], hw[1],
+                          _lib.ptr_array(_view_pointers(imgs)), _lib.ptr_array(_view_pointers(gts)),
+                          w_l1, w_ssim, 1 if sanitize else 0, _lib.ptr(g), _lib.ptr(ws), ws.numel(), _lib.ptr_array(gptrs))
         return (None,) * 6 + tuple(grads) + (None,) * len(gts)
 
 

@@ -9,8 +9,6 @@ HipSparseAdam is the opt-in variant whose step takes the iteration's visibility 
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -31,8 +29,7 @@ class HipAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = _lib.load()
-        name = type(self).__name__
+        name, ptr = type(self).__name__, _lib.ptr
         by_hyper = {}
         keep = []                                   # tensors that must outlive the launch call
         for g in self.param_groups:
@@ -59,22 +56,20 @@ class HipAdam(torch.optim.Optimizer):
                 keep.append(grad)
                 key = (p.device, tuple(g["betas"]), float(g["eps"]))
                 by_hyper.setdefault(key, []).append(
-                    _lib.AdamGroup(p.data_ptr(), grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                                   p.numel(), float(g["lr"]), st["step"]))
+                    _lib.AdamGroup(ptr(p), ptr(grad), ptr(st["exp_avg"]), ptr(st["exp_avg_sq"]), p.numel(), float(g["lr"]), st["step"]))
         if visibility is not None:
             kind = _lib.ADAM_MASK_RADII if visibility.dtype == torch.int32 else _lib.ADAM_MASK_BYTES
-            P, mask = int(visibility.shape[0]), (visibility.data_ptr() or None)
+            P, mask = int(visibility.shape[0]), ptr(visibility)
         for (dev, betas, eps), groups in by_hyper.items():
             with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
+                stream = _lib.stream(dev)
                 for i in range(0, len(groups), _lib.ADAM_MAX_GROUPS):
                     chunk = groups[i:i + _lib.ADAM_MAX_GROUPS]
                     arr = (_lib.AdamGroup * len(chunk))(*chunk)
                     if visibility is None:
-                        _lib.check(lib.gsr_adam_step(stream, len(chunk), arr, betas[0], betas[1], eps), "gsr_adam_step")
+                        _lib.call("gsr_adam_step", stream, len(chunk), arr, betas[0], betas[1], eps)
                     else:
-                        _lib.check(lib.gsr_adam_step_masked(stream, len(chunk), arr, betas[0], betas[1], eps, P, mask, kind),
-                                   "gsr_adam_step_masked")
+                        _lib.call("gsr_adam_step_masked", stream, len(chunk), arr, betas[0], betas[1], eps, P, mask, kind)
         return loss
 
 

@@ -17,6 +17,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._lib import ptr
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -32,14 +33,6 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: torch.Tensor
     prefiltered: bool
     debug: bool
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    if t is None or t.numel() == 0:
-        return None
-    if not t.is_contiguous():      # the C ABI takes dense row-major buffers; the public entry points make them so
-        raise _lib.GsrError(f"non-contiguous tensor of shape {tuple(t.shape)} passed to the native rasterizer")
-    return t.data_ptr()
 
 
 def _f32c(t: torch.Tensor, name: str, device) -> torch.Tensor:
@@ -62,13 +55,6 @@ def camera_settings(cam, bg, scale_modifier, sh_degree, debug) -> GaussianRaster
 
 def _camera(rs: GaussianRasterizationSettings, dev):
     return _f32c(rs.viewmatrix, "viewmatrix", dev), _f32c(rs.projmatrix, "projmatrix", dev), _f32c(rs.campos, "campos", dev)
-
-
-def _workspace(lib, sizer: str, dev, *sizes) -> torch.Tensor:
-    """A uint8 tensor of as many bytes as the library's `sizer` (one of the gsr_*_workspace_bytes) asks for at these sizes."""
-    n = C.c_size_t()
-    _lib.check(getattr(lib, sizer)(*sizes, C.byref(n)), sizer)
-    return torch.empty((n.value,), dtype=torch.uint8, device=dev)
 
 
 def _arena_fits(arena: torch.Tensor, dev, P: int, M: int, has_sr: bool) -> bool:
@@ -119,7 +105,7 @@ class HipBackend:
         v = self._ws_cache.get(key)
         if v is None:
             g, i, b = C.c_size_t(), C.c_size_t(), C.c_size_t()
-            _lib.check(self.lib.gsr_workspace_sizes(P, W, H, C.byref(g), C.byref(i), C.byref(b)), "gsr_workspace_sizes")
+            _lib.call("gsr_workspace_sizes", P, W, H, C.byref(g), C.byref(i), C.byref(b))       # three outputs: not a workspace() sizer
             v = (g.value, i.value, b.value)
             if len(self._ws_cache) > 64:
                 self._ws_cache.clear()
@@ -168,7 +154,7 @@ class HipBackend:
         if shs_rest is not None:
             M += int(shs_rest.shape[1])
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
+            stream = torch.cuda.current_stream(dev).cuda_stream      # _lib.stream(dev), inline: the hot path (profiles/host/bindings_refactor.txt)
             gb, ib, _ = self._sizes(P, W, H)
             u8 = dict(dtype=torch.uint8, device=dev)
             color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
@@ -211,14 +197,15 @@ class HipBackend:
                 if announce_backward and shs_rest is None and P > 0:
                     grads = self._gradient_outputs(dev, P, M, 0, scales.numel() > 0, colors_precomp.numel() > 0, cov3D_precomp.numel() > 0, arena)
                     g_means3D, g_means2D, g_sh, g_colors, g_opacity, g_scales, g_rots, g_cov3D, _ = grads
-                    _lib.check(self.lib.gsr_backward_prefill(P, M, _ptr(g_means2D), _ptr(g_opacity), _ptr(g_colors), _ptr(g_means3D), _ptr(g_cov3D),
-                                                             _ptr(g_sh), _ptr(g_scales), _ptr(g_rots), None), "gsr_backward_prefill")
+                    _lib.call("gsr_backward_prefill", P, M, ptr(g_means2D), ptr(g_opacity), ptr(g_colors), ptr(g_means3D), ptr(g_cov3D),
+                              ptr(g_sh), ptr(g_scales), ptr(g_rots), None)
+                # not _lib.call: the return code is needed before `stale` is dropped, the announcement withdrawn and the claim released
                 rc = self.lib.gsr_forward(
-                    stream, P, int(rs.sh_degree), M, W, H, _ptr(bg), _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
-                    _ptr(opacities), _ptr(scales), float(rs.scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                    _ptr(vm), _ptr(pm), _ptr(cp), float(rs.tanfovx), float(rs.tanfovy), int(bool(rs.prefiltered)),
-                    int(bool(rs.debug)), color.data_ptr(), _ptr(radii), geom.data_ptr(), gb, cb, None, img.data_ptr(), ib,
-                    C.byref(n), _ptr(shs_rest), int(bool(raw_params)))
+                    stream, P, int(rs.sh_degree), M, W, H, ptr(bg), ptr(means3D), ptr(shs), ptr(colors_precomp),
+                    ptr(opacities), ptr(scales), float(rs.scale_modifier), ptr(rotations), ptr(cov3D_precomp),
+                    ptr(vm), ptr(pm), ptr(cp), float(rs.tanfovx), float(rs.tanfovy), int(bool(rs.prefiltered)),
+                    int(bool(rs.debug)), color.data_ptr(), ptr(radii), geom.data_ptr(), gb, cb, None, img.data_ptr(), ib,      # allocated above: dense
+                    C.byref(n), ptr(shs_rest), int(bool(raw_params)))          # n: num_rendered, the call's one output word
             except BaseException:
                 if claimed:
                     self._release_arena(geom)           # no render came of it: nothing waits for a backward call
@@ -247,11 +234,10 @@ class HipBackend:
         P, H, W = int(means3D.shape[0]), int(rs.image_height), int(rs.image_width)
         M = int(shs.shape[1]) if shs.numel() else 0
         Mrest = int(shs_rest.shape[1]) if shs_rest is not None else 0
-        f32 = dict(dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
+            stream = torch.cuda.current_stream(dev).cuda_stream      # _lib.stream(dev), inline, as in forward()
             # depends on the pair count while the deterministic mode is on
-            bwd_ws = _workspace(self.lib, "gsr_backward_workspace_bytes", dev, P, int(num_rendered))
+            bwd_ws = _lib.workspace("gsr_backward_workspace_bytes", dev, P, int(num_rendered))
             has_sr = scales.numel() > 0
             arena = _usable_arena(dev, P, M + Mrest, has_sr)
             self._release_arena(geom)      # the arena claimed at forward time is the caller's again after this call
@@ -265,14 +251,15 @@ class HipBackend:
             bg = _f32c(rs.bg, "bg", dev)
             vm, pm, cp = _camera(rs, dev)
             dL = _f32c(dL_dpix, "grad of rendered image", dev)
+            # not _lib.call: the return code is in hand before the announced tensors (`ann`) are dropped and before the check raises
             rc = self.lib.gsr_backward(
-                stream, P, int(rs.sh_degree), M + Mrest, int(num_rendered), W, H, _ptr(bg), _ptr(means3D), _ptr(radii),
-                _ptr(shs), _ptr(colors_precomp), _ptr(scales), float(rs.scale_modifier), _ptr(rotations),
-                _ptr(cov3D_precomp), _ptr(vm), _ptr(pm), _ptr(cp), float(rs.tanfovx), float(rs.tanfovy), _ptr(dL),
-                _ptr(geom), geom.numel(), _ptr(binning), binning.numel(), _ptr(img), img.numel(), _ptr(bwd_ws),
-                bwd_ws.numel(), _ptr(g_means2D), _ptr(g_opacity), _ptr(g_colors), _ptr(g_means3D), _ptr(g_cov3D),
-                _ptr(g_sh), _ptr(g_scales), _ptr(g_rots), int(bool(rs.debug)), _ptr(shs_rest), int(bool(raw_params)),
-                _ptr(g_sh_rest))
+                stream, P, int(rs.sh_degree), M + Mrest, int(num_rendered), W, H, ptr(bg), ptr(means3D), ptr(radii),
+                ptr(shs), ptr(colors_precomp), ptr(scales), float(rs.scale_modifier), ptr(rotations),
+                ptr(cov3D_precomp), ptr(vm), ptr(pm), ptr(cp), float(rs.tanfovx), float(rs.tanfovy), ptr(dL),
+                ptr(geom), geom.numel(), ptr(binning), binning.numel(), ptr(img), img.numel(), ptr(bwd_ws),
+                bwd_ws.numel(), ptr(g_means2D), ptr(g_opacity), ptr(g_colors), ptr(g_means3D), ptr(g_cov3D),
+                ptr(g_sh), ptr(g_scales), ptr(g_rots), int(bool(rs.debug)), ptr(shs_rest), int(bool(raw_params)),
+                ptr(g_sh_rest))
             del ann
             _lib.check(rc, "gsr_backward")
         out = (g_means3D, g_means2D, g_sh, g_colors, g_opacity, g_scales, g_rots, g_cov3D)
@@ -287,10 +274,8 @@ class HipBackend:
         depth = torch.empty((H, W), dtype=torch.float32, device=dev)
         alpha = torch.empty((H, W), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            rc = self.lib.gsr_depth_forward(torch.cuda.current_stream(dev).cuda_stream, P, W, H, int(num_rendered), int(mode),
-                                            _ptr(geom), geom.numel(), _ptr(binning), binning.numel(), _ptr(img), img.numel(),
-                                            depth.data_ptr(), alpha.data_ptr())
-            _lib.check(rc, "gsr_depth_forward")
+            _lib.call("gsr_depth_forward", _lib.stream(dev), P, W, H, int(num_rendered), int(mode),
+                      ptr(geom), geom.numel(), ptr(binning), binning.numel(), ptr(img), img.numel(), ptr(depth), ptr(alpha))
         return depth, alpha
 
     def arena_fill_in_flight(self, geom):
@@ -311,7 +296,6 @@ class HipBackend:
         P, H, W = int(means3D.shape[0]), int(rs.image_height), int(rs.image_width)
         has_sr, has_cov = scales.numel() > 0, cov3D_precomp.numel() > 0
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
             if into is None:
                 M = sh_floats // 3
                 arena = _usable_arena(dev, P, M, has_sr)
@@ -322,17 +306,16 @@ class HipBackend:
                     g_sh.zero_()
             else:
                 g_means3D, g_means2D, g_opacity, g_scales, g_rots, g_cov3D = into
-            ws = _workspace(self.lib, "gsr_depth_workspace_bytes", dev, P)
+            ws = _lib.workspace("gsr_depth_workspace_bytes", dev, P)
             vm, pm, cp = _camera(rs, dev)
             gD = None if dL_ddepth is None else _f32c(dL_ddepth, "grad of the depth map", dev)
             gA = None if dL_dalpha is None else _f32c(dL_dalpha, "grad of the alpha map", dev)
-            rc = self.lib.gsr_depth_backward(
-                stream, P, W, H, int(num_rendered), int(mode), _ptr(means3D), _ptr(radii), _ptr(scales), float(rs.scale_modifier),
-                _ptr(rotations), _ptr(cov3D_precomp), _ptr(vm), _ptr(pm), _ptr(cp), float(rs.tanfovx), float(rs.tanfovy),
-                _ptr(gD), _ptr(gA), _ptr(geom), geom.numel(), _ptr(binning), binning.numel(), _ptr(img), img.numel(),
-                _ptr(ws), ws.numel(), 0 if into is None else 1,
-                _ptr(g_means2D), _ptr(g_opacity), _ptr(g_means3D), _ptr(g_cov3D), _ptr(g_scales), _ptr(g_rots))
-            _lib.check(rc, "gsr_depth_backward")
+            _lib.call(
+                "gsr_depth_backward", _lib.stream(dev), P, W, H, int(num_rendered), int(mode), ptr(means3D), ptr(radii), ptr(scales),
+                float(rs.scale_modifier), ptr(rotations), ptr(cov3D_precomp), ptr(vm), ptr(pm), ptr(cp), float(rs.tanfovx), float(rs.tanfovy),
+                ptr(gD), ptr(gA), ptr(geom), geom.numel(), ptr(binning), binning.numel(), ptr(img), img.numel(),
+                ptr(ws), ws.numel(), 0 if into is None else 1,
+                ptr(g_means2D), ptr(g_opacity), ptr(g_means3D), ptr(g_cov3D), ptr(g_scales), ptr(g_rots))
         out = (g_means3D, g_means2D, g_opacity, g_scales, g_rots, g_cov3D)
         return out + (ws,) if return_ws else out
 
@@ -351,16 +334,15 @@ class HipBackend:
         g_proj = torch.empty((4, 4), **f32) if want[1] else None
         g_campos = torch.empty((3,), **f32) if want[2] else None
         with torch.cuda.device(dev):
-            ws = _workspace(self.lib, "gsr_pose_workspace_bytes", dev, P)
+            ws = _lib.workspace("gsr_pose_workspace_bytes", dev, P)
             vm, pm, cp = _camera(rs, dev)
             colour = int(kind) == _lib.POSE_COLOR
-            rc = self.lib.gsr_pose_backward(
-                torch.cuda.current_stream(dev).cuda_stream, int(kind), P, int(rs.sh_degree), M, W, H, int(num_rendered),
-                _ptr(means3D), _ptr(radii), _ptr(shs) if colour else None, _ptr(colors_precomp) if colour else None,
-                _ptr(scales), float(rs.scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(vm), _ptr(pm), _ptr(cp),
-                float(rs.tanfovx), float(rs.tanfovy), _ptr(geom), geom.numel(), _ptr(acc_ws), acc_ws.numel(), _ptr(ws), ws.numel(),
-                _ptr(g_view), _ptr(g_proj), _ptr(g_campos))
-            _lib.check(rc, "gsr_pose_backward")
+            _lib.call(
+                "gsr_pose_backward", _lib.stream(dev), int(kind), P, int(rs.sh_degree), M, W, H, int(num_rendered),
+                ptr(means3D), ptr(radii), ptr(shs) if colour else None, ptr(colors_precomp) if colour else None,
+                ptr(scales), float(rs.scale_modifier), ptr(rotations), ptr(cov3D_precomp), ptr(vm), ptr(pm), ptr(cp),
+                float(rs.tanfovx), float(rs.tanfovy), ptr(geom), geom.numel(), ptr(acc_ws), acc_ws.numel(), ptr(ws), ws.numel(),
+                ptr(g_view), ptr(g_proj), ptr(g_campos))
         return g_view, g_proj, g_campos
 
     def composited_mask(self, geom, P):
@@ -369,8 +351,7 @@ class HipBackend:
         dev = geom.device
         out = torch.empty((P,), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            rc = self.lib.gsr_composited_mask(torch.cuda.current_stream(dev).cuda_stream, P, _ptr(geom), geom.numel(), _ptr(out))
-            _lib.check(rc, "gsr_composited_mask")
+            _lib.call("gsr_composited_mask", _lib.stream(dev), P, ptr(geom), geom.numel(), ptr(out))
         return out.bool()
 
     def mark_visible(self, positions, viewmatrix, projmatrix):
@@ -382,8 +363,7 @@ class HipBackend:
         with torch.cuda.device(dev):
             pos = _f32c(positions, "positions", dev); vm = _f32c(viewmatrix, "viewmatrix", dev)
             pm = _f32c(projmatrix, "projmatrix", dev)
-            rc = self.lib.gsr_mark_visible(torch.cuda.current_stream(dev).cuda_stream, P, _ptr(pos), _ptr(vm), _ptr(pm), _ptr(out))
-            _lib.check(rc, "gsr_mark_visible")
+            _lib.call("gsr_mark_visible", _lib.stream(dev), P, ptr(pos), ptr(vm), ptr(pm), ptr(out))
         return out.bool()
 
 

@@ -15,7 +15,6 @@ float32 on a HIP device raise GsrError.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
@@ -23,7 +22,6 @@ import torch
 from . import _lib
 from .model import GaussianParams
 from .rasterizer import _remember_forward, arena_floats, camera_settings, get_backend, gradient_arena
-from .sequence import _check_device, _check_tensor
 
 MAX_B = 64           # GSR_ROWS_MAX_B: arenas per native pack call (larger camera sets are packed in chunks and added in order)
 _ALIGN = 16          # floats: every unpacked buffer starts on a 64-byte boundary
@@ -31,7 +29,7 @@ _ALIGN = 16          # floats: every unpacked buffer starts on a 64-byte boundar
 
 def _check_rows(who: str, rows) -> int:
     """Type, dtype, rank and width (checkable on any tensor; callers check the device last).  Returns K, the SH coefficients per row."""
-    _check_tensor(who, "rows", rows)
+    _lib.require_tensor(who, "rows", rows)
     if rows.dim() != 2:
         raise _lib.GsrError(f"{who}: rows must have shape [P, D], got {tuple(rows.shape)}")
     D = int(rows.shape[1])
@@ -44,8 +42,7 @@ def _check_rows(who: str, rows) -> int:
 def _unpack(rows: torch.Tensor, K: int):
     """rows: contiguous, detached, validated.  Returns (xyz, f_dc, f_rest or None, opacity, scaling, rotation), slices of one
     allocation, written by one launch on the current stream."""
-    lib = _lib.load()
-    P, dev = int(rows.shape[0]), rows.device
+    P, dev, ptr = int(rows.shape[0]), rows.device, _lib.ptr
     shapes = [(P, 3), (P, 1, 3), (P, K - 1, 3), (P, 1), (P, 3), (P, 4)]
     offs, total = [], 0
     for s in shapes:
@@ -54,9 +51,8 @@ def _unpack(rows: torch.Tensor, K: int):
     with torch.cuda.device(dev):
         store = torch.empty((max(total, 1),), dtype=torch.float32, device=dev)
         xyz, dc, rest, op, sc, rot = (store[o:o + math.prod(s)].view(s) for o, s in zip(offs, shapes))
-        ptr = lambda t: t.data_ptr() if t.numel() else None
-        _lib.check(lib.gsr_rows_unpack(torch.cuda.current_stream(dev).cuda_stream, P, int(rows.shape[1]), ptr(rows), ptr(xyz), ptr(dc),
-                                       ptr(rest) if K > 1 else None, ptr(op), ptr(sc), ptr(rot)), "gsr_rows_unpack")
+        _lib.call("gsr_rows_unpack", _lib.stream(dev), P, int(rows.shape[1]), ptr(rows), ptr(xyz), ptr(dc), ptr(rest), ptr(op), ptr(sc),
+                  ptr(rot))                  # K == 1: rest is empty, NULL
     return xyz, dc, (rest if K > 1 else None), op, sc, rot
 
 
@@ -65,7 +61,7 @@ def unpack_rows(rows: torch.Tensor) -> GaussianParams:
     what `unflatten_gaussians(rows)` holds as strided views, bit for bit, written by one launch into one allocation (each tensor
     on a 64-byte boundary).  The SH degree follows from the row width, as there."""
     K = _check_rows("unpack_rows", rows)
-    _check_device("unpack_rows", "rows", rows)
+    _lib.require_hip("unpack_rows", "rows", rows)
     xyz, dc, rest, op, sc, rot = _unpack(rows.detach().contiguous(), K)
     g = GaussianParams(int(round(math.sqrt(K))) - 1)
     g._xyz, g._features_dc, g._opacity, g._scaling, g._rotation = xyz, dc, op, sc, rot
@@ -91,14 +87,12 @@ def _forward_all(settings, rows: torch.Tensor, K: int):
 
 def _pack(arenas, P: int, D: int, dev) -> torch.Tensor:
     """dL/drows [P, D] from the cameras' arenas, summed in order: one launch per MAX_B arenas, chunk results added in order."""
-    lib = _lib.load()
     total = None
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    stream = _lib.stream(dev)
     for b0 in range(0, len(arenas), MAX_B):
         chunk = arenas[b0:b0 + MAX_B]
         out = torch.empty((P, D), dtype=torch.float32, device=dev)
-        ptrs = (C.c_void_p * len(chunk))(*[a.data_ptr() for a in chunk])
-        _lib.check(lib.gsr_rows_grad_pack(stream, P, D, len(chunk), ptrs, out.data_ptr()), "gsr_rows_grad_pack")
+        _lib.call("gsr_rows_grad_pack", stream, P, D, len(chunk), _lib.ptr_array([_lib.ptr(a) for a in chunk]), _lib.ptr(out))
         total = out if total is None else total + out
     return total
 
@@ -174,7 +168,7 @@ def render_rows(cameras, rows: torch.Tensor, pipe, bg: torch.Tensor, scaling_mod
         sh_degree = deg
     if not isinstance(sh_degree, int) or not 0 <= sh_degree <= deg:
         raise _lib.GsrError(f"{who}: sh_degree={sh_degree!r} not in 0..{deg}, the degree D={int(rows.shape[1])} columns hold")
-    _check_device(who, "rows", rows)
+    _lib.require_hip(who, "rows", rows)
     settings = tuple(camera_settings(cam, bg, scaling_modifier, sh_degree, pipe.debug) for cam in cameras)
     if torch.is_grad_enabled() and rows.requires_grad:
         *images, radii = _RenderRows.apply(rows, K, settings)

@@ -88,24 +88,12 @@ def pad_gaussian(D: int = 26, device=None) -> torch.Tensor:
 
 # ---------------------------------------------------------------- box sort ----------------------------------------------------------------
 
-def _check_tensor(who: str, name: str, t, dtype=torch.float32) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise _lib.GsrError(f"{who}: {name} must be a torch.Tensor, got {type(t).__name__}")
-    if t.dtype != dtype:
-        raise _lib.GsrError(f"{who}: {name} must be {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
-
-
-def _check_device(who: str, name: str, t) -> None:
-    if t.device.type != "cuda":
-        raise _lib.GsrError(f"{who}: {name} must be on a HIP device, got {t.device} (no CPU fallback)")
-
-
 def _validate_box(rows, xyz_col, interval_num) -> None:
-    _check_tensor("box_sort_rows", "rows", rows)
+    _lib.require_tensor("box_sort_rows", "rows", rows)
     if rows.dim() != 2:
         raise _lib.GsrError(f"box_sort_rows: rows must have shape [P, D], got {tuple(rows.shape)}")
     _validate_box_sizes(int(rows.shape[1]), xyz_col, interval_num)
-    _check_device("box_sort_rows", "rows", rows)
+    _lib.require_hip("box_sort_rows", "rows", rows)
 
 
 def _validate_box_sizes(D: int, xyz_col, interval_num) -> None:
@@ -125,20 +113,17 @@ def box_sort_rows(rows: torch.Tensor, xyz_col: int, interval_num: int):
     original index; perm names their original rows.  Rows with a coordinate < 0, >= 1 or NaN belong to no box (the reference
     drops them silently): out_rows is zero and perm -1 in [count, P)."""
     _validate_box(rows, xyz_col, interval_num)
-    lib = _lib.load()
     rows = rows.detach().contiguous()
     P, D = int(rows.shape[0]), int(rows.shape[1])
     dev = rows.device
     out_rows = torch.empty_like(rows)
     perm = torch.empty((P,), dtype=torch.int32, device=dev)
     count = torch.empty((1,), dtype=torch.int32, device=dev)
-    nb = C.c_size_t()
-    _lib.check(lib.gsr_box_sort_workspace(P, interval_num, C.byref(nb)), "gsr_box_sort_workspace")
+    ptr = _lib.ptr
     with torch.cuda.device(dev):
-        ws = torch.empty((max(nb.value, 1),), dtype=torch.uint8, device=dev)
-        _lib.check(lib.gsr_box_sort(torch.cuda.current_stream(dev).cuda_stream, P, D, rows.data_ptr() if P else None, xyz_col,
-                                    interval_num, out_rows.data_ptr() if P else None, perm.data_ptr() if P else None,
-                                    count.data_ptr(), ws.data_ptr(), ws.numel()), "gsr_box_sort")
+        ws = _lib.workspace("gsr_box_sort_workspace", dev, P, interval_num)
+        _lib.call("gsr_box_sort", _lib.stream(dev), P, D, ptr(rows), xyz_col, interval_num, ptr(out_rows), ptr(perm), ptr(count),
+                  ptr(ws), ws.numel())
     return out_rows, perm, count
 
 
@@ -203,7 +188,7 @@ def _validate_visible(means3D, scales, rotations, cov3D_precomp, raw_params, n_c
     who = "visible_union"
     if n_cameras < 1:
         raise _lib.GsrError(f"{who}: cameras must hold at least one camera")
-    _check_tensor(who, "means3D", means3D)
+    _lib.require_tensor(who, "means3D", means3D)
     if means3D.dim() != 2 or means3D.shape[1] != 3:
         raise _lib.GsrError(f"{who}: means3D must have shape [P, 3], got {tuple(means3D.shape)}")
     P = int(means3D.shape[0])
@@ -213,12 +198,12 @@ def _validate_visible(means3D, scales, rotations, cov3D_precomp, raw_params, n_c
         raise _lib.GsrError(f"{who}: raw_params needs scales and rotations, not cov3D_precomp")
     given = [(n, t, w) for n, t, w in (("scales", scales, 3), ("rotations", rotations, 4), ("cov3D_precomp", cov3D_precomp, 6)) if t is not None]
     for name, t, w in given:
-        _check_tensor(who, name, t)
+        _lib.require_tensor(who, name, t)
         if tuple(t.shape) != (P, w):
             raise _lib.GsrError(f"{who}: {name} must have shape [{P}, {w}], got {tuple(t.shape)}")
-    _check_device(who, "means3D", means3D)
+    _lib.require_hip(who, "means3D", means3D)
     for name, t, _ in given:
-        _check_device(who, name, t)
+        _lib.require_hip(who, name, t)
         if t.device != means3D.device:
             raise _lib.GsrError(f"{who}: {name} is on {t.device} but means3D on {means3D.device}")
 
@@ -244,18 +229,16 @@ def visible_union_tensors(cameras, means3D, scales=None, rotations=None, cov3D_p
     the host never waits for the device; cameras holding numpy matrices cost one blocking upload of all their matrices per call."""
     cameras = list(cameras)
     _validate_visible(means3D, scales, rotations, cov3D_precomp, raw_params, len(cameras))
-    lib = _lib.load()
-    dev = means3D.device
+    dev, ptr = means3D.device, _lib.ptr
     P, B = int(means3D.shape[0]), len(cameras)
     c = lambda t: None if t is None else t.detach().contiguous()
     means3D, scales, rotations, cov3D_precomp = c(means3D), c(scales), c(rotations), c(cov3D_precomp)
-    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
     view, proj = _camera_matrices(cameras, dev)
     radii = torch.empty((B, P), dtype=torch.int32, device=dev) if want_radii else None
     counts = torch.empty((B,), dtype=torch.int32, device=dev) if want_counts else None
     visible = None
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _lib.stream(dev)
         for b0 in range(0, B, MAX_B):
             nb = min(MAX_B, B - b0)
             chunk = cameras[b0:b0 + nb]
@@ -264,11 +247,9 @@ def visible_union_tensors(cameras, means3D, scales=None, rotations=None, cov3D_p
             ws_ = (C.c_int32 * nb)(*[int(cam.image_width) for cam in chunk])
             hs_ = (C.c_int32 * nb)(*[int(cam.image_height) for cam in chunk])
             vis = torch.empty((P,), dtype=torch.uint8, device=dev) if want_visible else None
-            _lib.check(lib.gsr_visible_union(stream, P, nb, ptr(means3D), ptr(scales), float(scale_modifier), ptr(rotations),
-                                             ptr(cov3D_precomp), 1 if raw_params else 0, view[b0:].data_ptr(), proj[b0:].data_ptr(),
-                                             tfx, tfy, ws_, hs_,
-                                             ptr(radii[b0:]) if want_radii else None, ptr(vis),
-                                             counts[b0:].data_ptr() if want_counts else None), "gsr_visible_union")
+            _lib.call("gsr_visible_union", stream, P, nb, ptr(means3D), ptr(scales), float(scale_modifier), ptr(rotations),
+                      ptr(cov3D_precomp), 1 if raw_params else 0, ptr(view[b0:]), ptr(proj[b0:]), tfx, tfy, ws_, hs_,
+                      ptr(radii[b0:]) if want_radii else None, ptr(vis), ptr(counts[b0:]) if want_counts else None)
             if want_visible:
                 visible = vis if visible is None else visible | vis
     return (visible.bool() if want_visible else None), radii, counts
