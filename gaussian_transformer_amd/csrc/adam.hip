@@ -1,7 +1,7 @@
 // adam.hip -- one launch for the Adam step of all parameter groups (include/gsr_optim.h).  Pure streaming:
 // 16 bytes read + 12 written per element, float4 wide where the group's length and pointers allow.
-// Below it the visibility-masked step (gsr_adam_step_masked): the same update through the same adam_one, on the visible rows only.
-// Both entry points are at the end of the file.
+// Below it the visibility-masked step (gsr_adam_step_masked): the same update through the same adam_four / adam_at, on the visible
+// rows only, over the same group plan (adam_plan).  Both entry points are at the end of the file.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -37,12 +37,23 @@ __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, 
     p = p - step_size * (m / denom);
 }
 
+// the update of one float4 of each array, lane by lane
+__device__ __forceinline__ void adam_four(float4 &p, const float4 &g, float4 &m, float4 &v, const AdamArgs &a, const AdamGroupDev &G) {
+    adam_one(p.x, g.x, m.x, v.x, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
+    adam_one(p.y, g.y, m.y, v.y, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
+    adam_one(p.z, g.z, m.z, v.z, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
+    adam_one(p.w, g.w, m.w, v.w, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
+}
+// element j of group G: load, update, store
+template <class Index>
+__device__ __forceinline__ void adam_at(const AdamArgs &a, const AdamGroupDev &G, Index j) {
+    float p = G.p[j], m = G.m[j], v = G.v[j];
+    adam_one(p, G.g[j], m, v, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
+    G.p[j] = p; G.m[j] = m; G.v[j] = v;
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
-    int gi = 0;
-#pragma unroll 1
-    for (int k = 1; k < a.n_groups; k++)
-        if (blockIdx.x >= a.grp[k].first_block) gi = k;          // block-uniform
-    const AdamGroupDev &G = a.grp[gi];
+    const AdamGroupDev &G = a.grp[group_of_block(a)];
     const long long base = (long long)(blockIdx.x - G.first_block) * ADAM_PER_BLOCK;
     if (G.vec4) {
 #pragma unroll
@@ -50,36 +61,25 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
             const long long i = base + ((long long)it * 256 + threadIdx.x) * 4;
             if (i + 3 < G.n) {
                 float4 p = *reinterpret_cast<float4 *>(G.p + i), m = *reinterpret_cast<float4 *>(G.m + i), v = *reinterpret_cast<float4 *>(G.v + i);
-                const float4 g = *reinterpret_cast<const float4 *>(G.g + i);
-                adam_one(p.x, g.x, m.x, v.x, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
-                adam_one(p.y, g.y, m.y, v.y, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
-                adam_one(p.z, g.z, m.z, v.z, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
-                adam_one(p.w, g.w, m.w, v.w, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
+                adam_four(p, *reinterpret_cast<const float4 *>(G.g + i), m, v, a, G);
                 *reinterpret_cast<float4 *>(G.p + i) = p; *reinterpret_cast<float4 *>(G.m + i) = m; *reinterpret_cast<float4 *>(G.v + i) = v;
             } else {
-                for (long long j = i; j < G.n && j < i + 4; j++) {
-                    float p = G.p[j], m = G.m[j], v = G.v[j];
-                    adam_one(p, G.g[j], m, v, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
-                    G.p[j] = p; G.m[j] = m; G.v[j] = v;
-                }
+                for (long long j = i; j < G.n && j < i + 4; j++) adam_at(a, G, j);
             }
         }
     } else {
         for (int it = 0; it < 16; it++) {
             const long long j = base + (long long)it * 256 + threadIdx.x;
-            if (j < G.n) {
-                float p = G.p[j], m = G.m[j], v = G.v[j];
-                adam_one(p, G.g[j], m, v, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
-                G.p[j] = p; G.m[j] = m; G.v[j] = v;
-            }
+            if (j < G.n) adam_at(a, G, j);
         }
     }
 }
 
-static hipError_t launch_adam(int n_groups, const gsr_adam_group_t *groups, double beta1, double beta2, double eps, hipStream_t s) {
-    AdamArgs a;
+// The launch plan of both entry points: the groups that hold an element, in order, each with its bias corrections, its float4
+// eligibility and its first block.  Returns the number of blocks (0: nothing to launch).
+static unsigned adam_plan(int n_groups, const gsr_adam_group_t *groups, double beta1, double beta2, double eps, AdamArgs &a) {
     a.n_groups = 0; a.beta2 = (float)beta2; a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps;
-    unsigned blocks = 0;
+    unsigned blocks = 0;                         // at most 16 groups of 2^19 blocks in the masked step, whose n < 2^31
     for (int k = 0; k < n_groups; k++) {
         const gsr_adam_group_t &h = groups[k];
         if (h.n <= 0) continue;
@@ -92,6 +92,12 @@ static hipError_t launch_adam(int n_groups, const gsr_adam_group_t *groups, doub
         d.vec4 = ((((uintptr_t)h.param | (uintptr_t)h.grad | (uintptr_t)h.exp_avg | (uintptr_t)h.exp_avg_sq) & 15) == 0) ? 1 : 0;
         blocks += (unsigned)((h.n + ADAM_PER_BLOCK - 1) / ADAM_PER_BLOCK);
     }
+    return blocks;
+}
+
+static hipError_t launch_adam(int n_groups, const gsr_adam_group_t *groups, double beta1, double beta2, double eps, hipStream_t s) {
+    AdamArgs a;
+    const unsigned blocks = adam_plan(n_groups, groups, beta1, beta2, eps, a);
     if (blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();
@@ -118,10 +124,7 @@ __device__ __forceinline__ bool row_visible(const void *mask, unsigned row) {
 template <int KIND>
 __global__ __launch_bounds__(256) void adam_masked_kernel(AdamMaskedArgs A) {
     const AdamArgs &a = A.a;
-    int gi = 0;
-#pragma unroll 1
-    for (int k = 1; k < a.n_groups; k++)
-        if (blockIdx.x >= a.grp[k].first_block) gi = k;          // block-uniform
+    const int gi = group_of_block(a);
     const AdamGroupDev &G = a.grp[gi];
     const unsigned w = (unsigned)A.w[gi], q_step = (unsigned)A.q_step[gi], r_step = (unsigned)A.r_step[gi];
     const unsigned n = (unsigned)G.n;                            // n <= 2^31 - 1 (checked on the host)
@@ -163,10 +166,7 @@ __global__ __launch_bounds__(256) void adam_masked_kernel(AdamMaskedArgs A) {
                 const float4 p0 = *reinterpret_cast<float4 *>(G.p + i), m0 = *reinterpret_cast<float4 *>(G.m + i), v0 = *reinterpret_cast<float4 *>(G.v + i);
                 const float4 g = *reinterpret_cast<const float4 *>(G.g + i);
                 float4 p = p0, m = m0, v = v0;
-                adam_one(p.x, g.x, m.x, v.x, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
-                adam_one(p.y, g.y, m.y, v.y, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
-                adam_one(p.z, g.z, m.z, v.z, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
-                adam_one(p.w, g.w, m.w, v.w, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
+                adam_four(p, g, m, v, a, G);
                 if (!(bits & 1)) { p.x = p0.x; m.x = m0.x; v.x = v0.x; }
                 if (!(bits & 2)) { p.y = p0.y; m.y = m0.y; v.y = v0.y; }
                 if (!(bits & 4)) { p.z = p0.z; m.z = m0.z; v.z = v0.z; }
@@ -175,11 +175,7 @@ __global__ __launch_bounds__(256) void adam_masked_kernel(AdamMaskedArgs A) {
             } else {
 #pragma unroll 1
                 for (unsigned c = 0; c < 4 && i + c < n; c++) {
-                    if (!(bits >> c & 1)) continue;
-                    const unsigned j = i + c;
-                    float p = G.p[j], m = G.m[j], v = G.v[j];
-                    adam_one(p, G.g[j], m, v, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
-                    G.p[j] = p; G.m[j] = m; G.v[j] = v;
+                    if (bits >> c & 1) adam_at(a, G, i + c);
                 }
             }
         }
@@ -192,11 +188,7 @@ __global__ __launch_bounds__(256) void adam_masked_kernel(AdamMaskedArgs A) {
             row += q_step; rem += r_step;
             if (rem >= w) { rem -= w; row++; }
             if (__ballot(on) == 0) continue;                     // wave-uniform
-            if (on) {
-                float p = G.p[j], m = G.m[j], v = G.v[j];
-                adam_one(p, G.g[j], m, v, a.omb1, a.beta2, a.omb2, a.eps, G.step_size, G.inv_sqrt_bc2);
-                G.p[j] = p; G.m[j] = m; G.v[j] = v;
-            }
+            if (on) adam_at(a, G, j);
         }
     }
 }
@@ -244,33 +236,20 @@ int32_t gsr_adam_step_masked(gsr_stream_t stream, int32_t n_groups, const gsr_ad
     if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: betas", who);
 
     AdamMaskedArgs A;
-    AdamArgs &a = A.a;
-    a.n_groups = 0; a.beta2 = (float)beta2; a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps;
-    A.mask = mask;
-    unsigned blocks = 0;                         // at most 16 groups of 2^19 blocks
-    for (int k = 0; k < n_groups; k++) {
-        const gsr_adam_group_t &h = groups[k];
-        if (h.n <= 0) continue;
-        const int s = a.n_groups++;
-        AdamGroupDev &d = a.grp[s];
-        d.p = h.param; d.g = h.grad; d.m = h.exp_avg; d.v = h.exp_avg_sq; d.n = h.n;
-        const double bc1 = 1.0 - pow(beta1, (double)h.step), bc2 = 1.0 - pow(beta2, (double)h.step);      // as launch_adam, to the letter
-        d.step_size = (float)((double)h.lr / bc1);
-        d.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-        d.first_block = blocks;
-        d.vec4 = ((((uintptr_t)h.param | (uintptr_t)h.grad | (uintptr_t)h.exp_avg | (uintptr_t)h.exp_avg_sq) & 15) == 0) ? 1 : 0;
-        const long long w = h.n / P, step = d.vec4 ? 1024 : 256;
-        A.w[s] = (int)w; A.q_step[s] = (int)(step / w); A.r_step[s] = (int)(step % w);
-        blocks += (unsigned)((h.n + ADAM_PER_BLOCK - 1) / ADAM_PER_BLOCK);
-    }
-    for (int s = a.n_groups; s < GSR_ADAM_MAX_GROUPS; s++) A.w[s] = A.q_step[s] = A.r_step[s] = 0;
+    const unsigned blocks = adam_plan(n_groups, groups, beta1, beta2, eps, A.a);
     if (blocks == 0) return GSR_OK;
+    A.mask = mask;
+    for (int s = 0; s < GSR_ADAM_MAX_GROUPS; s++) {
+        A.w[s] = A.q_step[s] = A.r_step[s] = 0;
+        if (s >= A.a.n_groups) continue;
+        const long long w = A.a.grp[s].n / P, step = A.a.grp[s].vec4 ? 1024 : 256;      // P >= 1: a group with elements is a multiple of it
+        A.w[s] = (int)w; A.q_step[s] = (int)(step / w); A.r_step[s] = (int)(step % w);
+    }
     if (mask_kind == GSR_ADAM_MASK_RADII)
         hipLaunchKernelGGL(adam_masked_kernel<GSR_ADAM_MASK_RADII>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, A);
     else
         hipLaunchKernelGGL(adam_masked_kernel<GSR_ADAM_MASK_BYTES>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, A);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GSR_ERR_HIP, "masked adam launch: %s (%d)", hipGetErrorString(e), (int)e);
+    HIP_TRY(hipGetLastError(), "masked adam launch");
     return GSR_OK;
 }
 

@@ -208,11 +208,7 @@ __device__ __forceinline__ float child_xyz(const ApplyArgs &a, const float *__re
 __global__ __launch_bounds__(256) void densify_apply_kernel(ApplyArgs a) {
     // the plan in the workspace must be the one the caller sized the outputs for (uniform)
     if (a.counts[C_PNEW] != a.p_new || a.counts[C_NSPLIT] != a.n_split) return;
-    int gi = 0;
-#pragma unroll 1
-    for (int k = 1; k < a.n_groups; k++)
-        if (blockIdx.x >= a.grp[k].first_block) gi = k;          // block-uniform
-    const ApplyGroupDev &G = a.grp[gi];
+    const ApplyGroupDev &G = a.grp[group_of_block(a)];
     const uint32_t w = G.w;
     const uint64_t total = (uint64_t)a.p_new * w;               // < 2^32 (checked by the caller)
     const uint64_t base = (uint64_t)(blockIdx.x - G.first_block) * APPLY_PER_BLOCK;

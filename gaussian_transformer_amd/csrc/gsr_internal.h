@@ -44,6 +44,17 @@ struct Bump {      // hands out consecutive 256-byte-aligned pieces of a workspa
     template <class T> T *take_last(size_t count) { char *r = base ? base + off : nullptr; off += count * sizeof(T); return (T *)r; }      // a last piece whose end is not rounded up
 };
 
+// One launch over several groups of elements (adam.hip, density.hip): group k owns the blocks [grp[k].first_block, grp[k + 1].first_block).
+// The group of this block (block-uniform); Args: any kernel-argument struct with n_groups and grp[].first_block.
+template <class Args>
+__device__ __forceinline__ int group_of_block(const Args &a) {
+    int gi = 0;
+#pragma unroll 1
+    for (int k = 1; k < a.n_groups; k++)
+        if (blockIdx.x >= a.grp[k].first_block) gi = k;
+    return gi;
+}
+
 // Per-Gaussian record gathered by the compositing kernels: 12 floats = 3 x float4.
 //   [0] px  [1] py  [2] conic.xx  [3] conic.xy | [4] conic.yy [5] opacity [6] r [7] g | [8] b [9] depth [10] cull tau [11] replica code of the accumulator rows (bits; 0 = none)
 #define GSR_REC_FLOATS 12

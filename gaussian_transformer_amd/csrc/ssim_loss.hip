@@ -12,7 +12,11 @@
 //             dL/dx = (1-lambda)/N sign(x-y) - lambda/N (G*A + 2x G*B + y G*C), scaled by the upstream scalar.
 // HBM-bound: forward reads 8 and writes 12 bytes per map entry, backward reads 20 and writes 4.
 //
-// The multi-view form (gsr_views_loss_*, include/gsr_loss.h; the image loss of train_stacked_transformer.py:203-222) runs the same
+// Each direction is ONE tile body, ssim_fwd_tile / ssim_bwd_tile, templated on the sanitising, the number of partial sums and the
+// window's type; the four kernels around them only find their plane's pointers (and the multi-view forward resets the ticket).  The
+// two finishing kernels share ssim_sum_partials and differ in what they make of the totals.
+//
+// The multi-view form (gsr_views_loss_*, include/gsr_loss.h; the image loss of train_stacked_transformer.py:203-222) runs that
 // tile code over B views of 3 planes each: the plane index b * 3 + c is the grid's z, the B prediction / target / gradient pointers
 // travel by value in the kernel arguments (GSR_VIEWS_LOSS_MAX_B views per launch, the launcher loops over larger B), the sanitising
 // s(x) = clamp(nan_to_num(x), 0, 1) is applied while the tile is staged into LDS, and the backward masks its final store with the
@@ -162,53 +166,73 @@ __device__ __forceinline__ float ssim_block_sum(float v, float *red, int tid) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int C, int H, int W, const float *__restrict__ img,
-                                                          const float *__restrict__ gt, SsimWeights wts,
-                                                          float *__restrict__ dmaps /*[3][C][H][W]*/,
-                                                          float *__restrict__ partial /*[blocks][2]*/) {
+// The forward pass of one block, for both forward kernels: this block's tile of the plane img / gt ([H][W] each) staged and blurred, the
+// plane's three derivative-map entries written (d f / d mu1 at dm, the other two `stride` and 2 `stride` floats behind it), and the
+// block's sums of |d|, SSIM and (NPART == 3) d^2, d = x - y as staged, stored by thread 0 at slot[0 .. NPART).
+template <bool SAN, int NPART, class Weights>
+__device__ __forceinline__ void ssim_fwd_tile(const float *__restrict__ img, const float *__restrict__ gt, int H, int W, const Weights &wts,
+                                              float *__restrict__ dm, size_t stride, float *__restrict__ slot) {
     __shared__ SsimTile sx, sy;
     __shared__ SsimRows hz[5];
-    __shared__ float red[2][4];
+    __shared__ float red[NPART][4];
     const int tid = threadIdx.x, lx = tid & 15, ly = tid >> 4;
-    const int c = blockIdx.z, x0 = blockIdx.x * SSIM_T, y0 = blockIdx.y * SSIM_T;
-    const size_t plane = (size_t)H * W, base = (size_t)c * plane;
-    ssim_stage_pair<false>(sx, sy, img + base, gt + base, H, W, x0, y0, tid);
+    const int x0 = blockIdx.x * SSIM_T, y0 = blockIdx.y * SSIM_T;
+    ssim_stage_pair<SAN>(sx, sy, img, gt, H, W, x0, y0, tid);
     const SsimMoments m = ssim_blur_moments(sx, sy, hz, wts, tid, lx, ly);
     const int x = x0 + lx, y = y0 + ly;
-    const bool in = x < W && y < H;
-    float l1 = 0.f, ss = 0.f;
-    if (in) {
-        const size_t p = base + (size_t)y * W + x, CHW = (size_t)C * plane;
-        ss = ssim_entry(m, dmaps + p, dmaps + CHW + p, dmaps + 2 * CHW + p);
-        l1 = fabsf(sx[ly + SSIM_R][lx + SSIM_R] - sy[ly + SSIM_R][lx + SSIM_R]);
+    float part[3] = {0.f, 0.f, 0.f};                       // |d|, SSIM, d^2
+    if (x < W && y < H) {
+        const size_t p = (size_t)y * W + x;
+        part[1] = ssim_entry(m, dm + p, dm + stride + p, dm + 2 * stride + p);
+        const float d = sx[ly + SSIM_R][lx + SSIM_R] - sy[ly + SSIM_R][lx + SSIM_R];
+        part[0] = fabsf(d);
+        part[2] = d * d;
     }
-    l1 = ssim_block_sum(l1, red[0], tid);
-    ss = ssim_block_sum(ss, red[1], tid);
-    if (tid == 0) {
-        const size_t b = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        partial[2 * b] = l1;
-        partial[2 * b + 1] = ss;
+    for (int k = 0; k < NPART; k++) part[k] = ssim_block_sum(part[k], red[k], tid);
+    if (tid == 0)
+        for (int k = 0; k < NPART; k++) slot[k] = part[k];
+}
+
+// grid (tiles x, tiles y, C)
+__global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int C, int H, int W, const float *__restrict__ img, const float *__restrict__ gt,
+                                                          SsimWeights wts, float *__restrict__ dmaps /*[3][C][H][W]*/,
+                                                          float *__restrict__ partial /*[blocks][2]*/) {
+    const size_t plane = (size_t)H * W, base = (size_t)blockIdx.z * plane;
+    const size_t b = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    ssim_fwd_tile<false, 2>(img + base, gt + base, H, W, wts, dmaps + base, (size_t)C * plane, partial + 2 * b);
+}
+
+// Sums n interleaved partials p[n][NPART] over the 1024 threads of the block, in double and in a fixed order (strided accumulate,
+// shuffles, 16 LDS slots per value added in index order); the totals are valid in thread 0, t[0 .. NPART).
+template <int NPART>
+__device__ __forceinline__ void ssim_sum_partials(const float *__restrict__ p, int n, double *t) {
+    __shared__ double r[NPART][16];
+    double s[NPART];
+    for (int k = 0; k < NPART; k++) s[k] = 0.0;
+    for (int i = threadIdx.x; i < n; i += 1024)
+        for (int k = 0; k < NPART; k++) s[k] += (double)p[NPART * i + k];
+    for (int m = 32; m > 0; m >>= 1)
+        for (int k = 0; k < NPART; k++) s[k] += __shfl_xor(s[k], m);
+    if ((threadIdx.x & 63) == 0)
+        for (int k = 0; k < NPART; k++) r[k][threadIdx.x >> 6] = s[k];
+    __syncthreads();
+    for (int k = 0; k < NPART; k++) {
+        t[k] = 0.0;
+        if (threadIdx.x == 0)
+            for (int i = 0; i < 16; i++) t[k] += r[k][i];
     }
 }
 
 // out[0] = loss, out[1] = L1 mean, out[2] = SSIM mean
 __global__ __launch_bounds__(1024) void l1_ssim_finish_kernel(int nblocks, double inv_n, float lambda,
                                                               const float *__restrict__ partial, float *__restrict__ out) {
-    __shared__ double r0[16], r1[16];
-    double a = 0.0, b = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += 1024) { a += (double)partial[2 * i]; b += (double)partial[2 * i + 1]; }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) { a += __shfl_xor(a, m); b += __shfl_xor(b, m); }
-    if ((threadIdx.x & 63) == 0) { r0[threadIdx.x >> 6] = a; r1[threadIdx.x >> 6] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double sa = 0.0, sb = 0.0;
-        for (int i = 0; i < 16; i++) { sa += r0[i]; sb += r1[i]; }
-        const float l1 = (float)(sa * inv_n), ssim = (float)(sb * inv_n);
-        out[0] = (1.f - lambda) * l1 + lambda * (1.f - ssim);
-        out[1] = l1;
-        out[2] = ssim;
-    }
+    double t[2];
+    ssim_sum_partials<2>(partial, nblocks, t);
+    if (threadIdx.x != 0) return;
+    const float l1 = (float)(t[0] * inv_n), ssim = (float)(t[1] * inv_n);
+    out[0] = (1.f - lambda) * l1 + lambda * (1.f - ssim);
+    out[1] = l1;
+    out[2] = ssim;
 }
 
 // the three derivative maps of one plane (zero outside the image) into LDS, then their separable blur at this thread's pixel
@@ -248,44 +272,56 @@ __device__ __forceinline__ SsimBlurred ssim_blur_dmaps(SsimTile *sm /*[3]*/, Ssi
     return {gA, gB, gC};
 }
 
-__global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int C, int H, int W, const float *__restrict__ img,
-                                                          const float *__restrict__ gt, SsimWeights wts,
-                                                          const float *__restrict__ dmaps, float lambda, float inv_n,
-                                                          const float *__restrict__ grad_loss /*[1] or null*/,
-                                                          float *__restrict__ grad_img) {
+// The reverse pass of one block, for both backward kernels: the blurred derivative maps of the plane that starts at dm[base] (strides
+// as ssim_blur_dmaps) and, at this thread's pixel of the planes img / gt / grad,
+//   dL/dx = up * inv_n * (w_l1 sign(x - y) - w_ssim (G*A + 2 x G*B + y G*C)),   x, y sanitised first when SAN,
+// rounded to float32 once.  Both weights and inv_n are doubles: the single-image kernel's 1 - lambda is no float32 number.
+template <bool SAN, class Weights>
+__device__ __forceinline__ void ssim_bwd_tile(const float *__restrict__ img, const float *__restrict__ gt, float *__restrict__ grad, int H, int W,
+                                              const Weights &wts, const float *__restrict__ dm, size_t base, size_t stride, double w_l1,
+                                              double w_ssim, double inv_n, const float *__restrict__ grad_loss /*[1] or null (= 1)*/) {
     __shared__ SsimTile sm[3];
     __shared__ SsimRows hz[3];
     const int tid = threadIdx.x, lx = tid & 15, ly = tid >> 4;
-    const int c = blockIdx.z, x0 = blockIdx.x * SSIM_T, y0 = blockIdx.y * SSIM_T;
-    const size_t plane = (size_t)H * W, base = (size_t)c * plane, CHW = (size_t)C * plane;
-    const SsimBlurred g = ssim_blur_dmaps(sm, hz, dmaps, base, CHW, wts, H, W, x0, y0, tid, lx, ly);
-    const double gA = g.gA, gB = g.gB, gC = g.gC;
+    const int x0 = blockIdx.x * SSIM_T, y0 = blockIdx.y * SSIM_T;
+    const SsimBlurred bl = ssim_blur_dmaps(sm, hz, dm, base, stride, wts, H, W, x0, y0, tid, lx, ly);
     const int x = x0 + lx, y = y0 + ly;
     if (x < W && y < H) {
-        const size_t p = base + (size_t)y * W + x;
-        const float xv = img[p], yv = gt[p];
+        const size_t p = (size_t)y * W + x;
+        const float raw = img[p];
+        const float xv = SAN ? ssim_sanitize(raw) : raw, yv = SAN ? ssim_sanitize(gt[p]) : gt[p];
         const float d = xv - yv;
         const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);           // torch.abs backward: sign(0) = 0
         const float up = grad_loss ? grad_loss[0] : 1.f;
-        grad_img[p] = (float)((double)up * inv_n * ((1.0 - lambda) * sgn - (double)lambda * (gA + 2.0 * xv * gB + (double)yv * gC)));
+        const float g = (float)((double)up * inv_n * (w_l1 * sgn - w_ssim * (bl.gA + 2.0 * xv * bl.gB + (double)yv * bl.gC)));
+        // clamp passes its gradient on [0, 1], bounds included, nan_to_num where the input is finite: exactly 0 elsewhere
+        grad[p] = (!SAN || (raw >= 0.f && raw <= 1.f)) ? g : 0.f;
     }
 }
 
+__global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int C, int H, int W, const float *__restrict__ img, const float *__restrict__ gt,
+                                                          SsimWeights wts, const float *__restrict__ dmaps, float lambda, float inv_n,
+                                                          const float *__restrict__ grad_loss /*[1] or null*/, float *__restrict__ grad_img) {
+    const size_t plane = (size_t)H * W, base = (size_t)blockIdx.z * plane;
+    ssim_bwd_tile<false>(img + base, gt + base, grad_img + base, H, W, wts, dmaps, base, (size_t)C * plane, 1.0 - lambda, (double)lambda,
+                         (double)inv_n, grad_loss);
+}
+
+// the tile grid of `planes` image planes, for the launchers and the workspace layouts
+static inline dim3 ssim_grid(int H, int W, int planes) { return dim3((W + SSIM_T - 1) / SSIM_T, (H + SSIM_T - 1) / SSIM_T, planes); }
+static inline size_t ssim_tiles(int H, int W) { const dim3 g = ssim_grid(H, W, 1); return (size_t)g.x * g.y; }      // blocks per image plane
+
 static hipError_t launch_l1_ssim_forward(int C, int H, int W, const float *img, const float *gt, float lambda, float *dmaps,
                                   float *partial, float *out, hipStream_t s) {
-    const SsimWeights w = make_weights();
-    const dim3 grid((W + SSIM_T - 1) / SSIM_T, (H + SSIM_T - 1) / SSIM_T, C);
-    hipLaunchKernelGGL(l1_ssim_fwd_kernel, grid, dim3(256), 0, s, C, H, W, img, gt, w, dmaps, partial);
-    const int nblocks = (int)(grid.x * grid.y * grid.z);
-    hipLaunchKernelGGL(l1_ssim_finish_kernel, dim3(1), dim3(1024), 0, s, nblocks, 1.0 / ((double)C * H * W), lambda, partial, out);
+    hipLaunchKernelGGL(l1_ssim_fwd_kernel, ssim_grid(H, W, C), dim3(256), 0, s, C, H, W, img, gt, make_weights(), dmaps, partial);
+    hipLaunchKernelGGL(l1_ssim_finish_kernel, dim3(1), dim3(1024), 0, s, (int)(ssim_tiles(H, W) * C), 1.0 / ((double)C * H * W), lambda,
+                       partial, out);
     return hipGetLastError();
 }
 
 static hipError_t launch_l1_ssim_backward(int C, int H, int W, const float *img, const float *gt, float lambda, const float *dmaps,
                                    const float *grad_loss, float *grad_img, hipStream_t s) {
-    const SsimWeights w = make_weights();
-    const dim3 grid((W + SSIM_T - 1) / SSIM_T, (H + SSIM_T - 1) / SSIM_T, C);
-    hipLaunchKernelGGL(l1_ssim_bwd_kernel, grid, dim3(256), 0, s, C, H, W, img, gt, w, dmaps, lambda,
+    hipLaunchKernelGGL(l1_ssim_bwd_kernel, ssim_grid(H, W, C), dim3(256), 0, s, C, H, W, img, gt, make_weights(), dmaps, lambda,
                        (float)(1.0 / ((double)C * H * W)), grad_loss, grad_img);
     return hipGetLastError();
 }
@@ -293,7 +329,6 @@ static hipError_t launch_l1_ssim_backward(int C, int H, int W, const float *img,
 // ---- B views in one launch (gsr_views_loss_*) ----
 // workspace: dmaps [3][B*3][H][W] | partial [B*3*tiles][3] | view_sums [B][3] double | ticket (one int on a line of its own)
 struct ViewsWs { float *dmaps, *partial; double *view_sums; int *ticket; size_t total_bytes; };
-static inline size_t ssim_tiles(int H, int W) { return (size_t)((W + SSIM_T - 1) / SSIM_T) * ((H + SSIM_T - 1) / SSIM_T); }      // blocks per image plane
 static inline ViewsWs views_carve(void *ws, int B, int H, int W) {
     Bump w = {(char *)ws, 0};
     float *const dmaps = w.take<float>((size_t)9 * B * H * W), *const partial = w.take<float>((size_t)9 * B * ssim_tiles(H, W));
@@ -320,34 +355,12 @@ struct ViewsFwdArgs {
 // grid (tiles x, tiles y, 3 * views of this launch)
 template <bool SAN>
 __global__ __launch_bounds__(256) void views_loss_fwd_kernel(ViewsFwdArgs a) {
-    __shared__ SsimTile sx, sy;
-    __shared__ SsimRows hz[5];
-    __shared__ float red[3][4];
-    const int tid = threadIdx.x, lx = tid & 15, ly = tid >> 4;
-    const int v = blockIdx.z / 3, c = blockIdx.z - 3 * v, x0 = blockIdx.x * SSIM_T, y0 = blockIdx.y * SSIM_T;
-    const int H = a.H, W = a.W;
-    const size_t plane = (size_t)H * W, gplane = (size_t)(a.plane0 + blockIdx.z);
-    if (tid == 0 && (blockIdx.x | blockIdx.y | blockIdx.z) == 0) *a.ticket = 0;    // the finishing kernel counts its blocks in it
-    ssim_stage_pair<SAN>(sx, sy, a.img[v] + (size_t)c * plane, a.gt[v] + (size_t)c * plane, H, W, x0, y0, tid);
-    const SsimMoments m = ssim_blur_moments(sx, sy, hz, a.wts, tid, lx, ly);
-    const int x = x0 + lx, y = y0 + ly;
-    float l1 = 0.f, ss = 0.f, sq = 0.f;
-    if (x < W && y < H) {
-        const size_t p = gplane * plane + (size_t)y * W + x;
-        ss = ssim_entry(m, a.dmaps + p, a.dmaps + a.n_all + p, a.dmaps + 2 * a.n_all + p);
-        const float d = sx[ly + SSIM_R][lx + SSIM_R] - sy[ly + SSIM_R][lx + SSIM_R];
-        l1 = fabsf(d);
-        sq = d * d;
-    }
-    l1 = ssim_block_sum(l1, red[0], tid);
-    ss = ssim_block_sum(ss, red[1], tid);
-    sq = ssim_block_sum(sq, red[2], tid);
-    if (tid == 0) {
-        const size_t b = (gplane * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        a.partial[3 * b] = l1;
-        a.partial[3 * b + 1] = ss;
-        a.partial[3 * b + 2] = sq;
-    }
+    const int v = blockIdx.z / 3, c = blockIdx.z - 3 * v;
+    const size_t plane = (size_t)a.H * a.W, gplane = (size_t)(a.plane0 + blockIdx.z);
+    if (threadIdx.x == 0 && (blockIdx.x | blockIdx.y | blockIdx.z) == 0) *a.ticket = 0;    // the finishing kernel counts its blocks in it
+    const size_t b = (gplane * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    ssim_fwd_tile<SAN, 3>(a.img[v] + (size_t)c * plane, a.gt[v] + (size_t)c * plane, a.H, a.W, a.wts, a.dmaps + gplane * plane, a.n_all,
+                          a.partial + 3 * b);
 }
 
 // One block per view: terms[b] = (mean |d|, mean SSIM, mean d^2) of view b from its 3 * tiles partials, in a fixed order.  The block
@@ -355,19 +368,11 @@ __global__ __launch_bounds__(256) void views_loss_fwd_kernel(ViewsFwdArgs a) {
 __global__ __launch_bounds__(1024) void views_loss_finish_kernel(int B, int per_view, double inv_nv, float w_l1, float w_ssim,
                                                                  const float *__restrict__ partial, double *view_sums, int *ticket,
                                                                  float *__restrict__ out, float *__restrict__ terms) {
-    __shared__ double r[3][16];
     const int b = blockIdx.x;
-    const float *p = partial + (size_t)3 * per_view * b;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int i = threadIdx.x; i < per_view; i += 1024) { s0 += (double)p[3 * i]; s1 += (double)p[3 * i + 1]; s2 += (double)p[3 * i + 2]; }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) { s0 += __shfl_xor(s0, m); s1 += __shfl_xor(s1, m); s2 += __shfl_xor(s2, m); }
-    if ((threadIdx.x & 63) == 0) { r[0][threadIdx.x >> 6] = s0; r[1][threadIdx.x >> 6] = s1; r[2][threadIdx.x >> 6] = s2; }
-    __syncthreads();
+    double t[3];
+    ssim_sum_partials<3>(partial + (size_t)3 * per_view * b, per_view, t);
     if (threadIdx.x != 0) return;
-    double t[3] = {0.0, 0.0, 0.0};
     for (int k = 0; k < 3; k++) {
-        for (int i = 0; i < 16; i++) t[k] += r[k][i];
         terms[3 * b + k] = (float)(t[k] * inv_nv);
         view_sums[3 * b + k] = t[k];
     }
@@ -396,27 +401,29 @@ struct ViewsBwdArgs {
 
 template <bool SAN>
 __global__ __launch_bounds__(256) void views_loss_bwd_kernel(ViewsBwdArgs a) {
-    __shared__ SsimTile sm[3];
-    __shared__ SsimRows hz[3];
     const int v = blockIdx.z / 3, c = blockIdx.z - 3 * v;
-    float *__restrict__ grad = a.grad[v];
-    if (!grad) return;                                 // the whole block
-    const int tid = threadIdx.x, lx = tid & 15, ly = tid >> 4;
-    const int x0 = blockIdx.x * SSIM_T, y0 = blockIdx.y * SSIM_T, H = a.H, W = a.W;
-    const size_t plane = (size_t)H * W, gbase = (size_t)(a.plane0 + blockIdx.z) * plane;
-    const SsimBlurred bl = ssim_blur_dmaps(sm, hz, a.dmaps, gbase, a.n_all, a.wts, H, W, x0, y0, tid, lx, ly);
-    const double gA = bl.gA, gB = bl.gB, gC = bl.gC;
-    const int x = x0 + lx, y = y0 + ly;
-    if (x < W && y < H) {
-        const size_t p = (size_t)c * plane + (size_t)y * W + x;
-        const float raw = a.img[v][p];
-        const float xv = SAN ? ssim_sanitize(raw) : raw, yv = SAN ? ssim_sanitize(a.gt[v][p]) : a.gt[v][p];
-        const float d = xv - yv;
-        const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-        const float up = a.grad_loss ? a.grad_loss[0] : 1.f;
-        const float g = (float)((double)up * a.inv_n * ((double)a.w_l1 * sgn - (double)a.w_ssim * (gA + 2.0 * xv * gB + (double)yv * gC)));
-        // clamp passes its gradient on [0, 1], bounds included, nan_to_num where the input is finite: exactly 0 elsewhere
-        grad[p] = (!SAN || (raw >= 0.f && raw <= 1.f)) ? g : 0.f;
+    if (!a.grad[v]) return;                            // the whole block
+    const size_t plane = (size_t)a.H * a.W, off = (size_t)c * plane;
+    ssim_bwd_tile<SAN>(a.img[v] + off, a.gt[v] + off, a.grad[v] + off, a.H, a.W, a.wts, a.dmaps, (size_t)(a.plane0 + blockIdx.z) * plane,
+                       a.n_all, (double)a.w_l1, (double)a.w_ssim, a.inv_n, a.grad_loss);
+}
+
+// Walks the B views in chunks of GSR_VIEWS_MAX_B, one launch each: the chunk's pointers into img / gt (and grad, the backward pass's;
+// NULL in the slots behind the last view), then launch(3 * first view, grid).  A chunk of the backward pass in which no view wants a
+// gradient is skipped.
+template <class Launch>
+static void views_in_chunks(int B, int H, int W, const float *const *imgs, const float *const *gts, float *const *grad_imgs,
+                            const float **img, const float **gt, float **grad /*NULL: forward*/, Launch &&launch) {
+    for (int b0 = 0; b0 < B; b0 += GSR_VIEWS_MAX_B) {
+        const int nb = B - b0 < GSR_VIEWS_MAX_B ? B - b0 : GSR_VIEWS_MAX_B;
+        bool any = !grad;
+        for (int i = 0; i < GSR_VIEWS_MAX_B; i++) {
+            img[i] = i < nb ? imgs[b0 + i] : nullptr; gt[i] = i < nb ? gts[b0 + i] : nullptr;
+            if (!grad) continue;
+            grad[i] = i < nb && grad_imgs ? grad_imgs[b0 + i] : nullptr;
+            any = any || grad[i];
+        }
+        if (any) launch(3 * b0, ssim_grid(H, W, 3 * nb));
     }
 }
 
@@ -427,17 +434,13 @@ static hipError_t launch_views_loss_forward(int B, int H, int W, const float *co
     ViewsFwdArgs a;
     a.dmaps = w.dmaps; a.partial = w.partial; a.ticket = w.ticket; a.H = H; a.W = W; a.n_all = (size_t)3 * B * H * W;
     a.wts = make_view_weights();
-    const unsigned gx = (W + SSIM_T - 1) / SSIM_T, gy = (H + SSIM_T - 1) / SSIM_T;
-    for (int b0 = 0; b0 < B; b0 += GSR_VIEWS_MAX_B) {
-        const int nb = B - b0 < GSR_VIEWS_MAX_B ? B - b0 : GSR_VIEWS_MAX_B;
-        for (int i = 0; i < GSR_VIEWS_MAX_B; i++) { a.img[i] = i < nb ? imgs[b0 + i] : nullptr; a.gt[i] = i < nb ? gts[b0 + i] : nullptr; }
-        a.plane0 = 3 * b0;
-        const dim3 grid(gx, gy, 3 * nb);
+    views_in_chunks(B, H, W, imgs, gts, nullptr, a.img, a.gt, nullptr, [&](int plane0, dim3 grid) {
+        a.plane0 = plane0;
         if (sanitize) hipLaunchKernelGGL(views_loss_fwd_kernel<true>, grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(views_loss_fwd_kernel<false>, grid, dim3(256), 0, s, a);
-    }
-    hipLaunchKernelGGL(views_loss_finish_kernel, dim3(B), dim3(1024), 0, s, B, (int)(3 * gx * gy), 1.0 / ((double)3 * H * W), w_l1, w_ssim,
-                       w.partial, w.view_sums, w.ticket, out3, terms);
+    });
+    hipLaunchKernelGGL(views_loss_finish_kernel, dim3(B), dim3(1024), 0, s, B, (int)(3 * ssim_tiles(H, W)), 1.0 / ((double)3 * H * W), w_l1,
+                       w_ssim, w.partial, w.view_sums, w.ticket, out3, terms);
     return hipGetLastError();
 }
 
@@ -448,21 +451,11 @@ static hipError_t launch_views_loss_backward(int B, int H, int W, const float *c
     a.dmaps = w.dmaps; a.grad_loss = grad_loss; a.H = H; a.W = W; a.n_all = (size_t)3 * B * H * W;
     a.w_l1 = w_l1; a.w_ssim = w_ssim; a.inv_n = 1.0 / ((double)3 * B * H * W);
     a.wts = make_view_weights();
-    const unsigned gx = (W + SSIM_T - 1) / SSIM_T, gy = (H + SSIM_T - 1) / SSIM_T;
-    for (int b0 = 0; b0 < B; b0 += GSR_VIEWS_MAX_B) {
-        const int nb = B - b0 < GSR_VIEWS_MAX_B ? B - b0 : GSR_VIEWS_MAX_B;
-        bool any = false;
-        for (int i = 0; i < GSR_VIEWS_MAX_B; i++) {
-            a.img[i] = i < nb ? imgs[b0 + i] : nullptr; a.gt[i] = i < nb ? gts[b0 + i] : nullptr;
-            a.grad[i] = i < nb && grad_imgs ? grad_imgs[b0 + i] : nullptr;
-            any = any || a.grad[i];
-        }
-        if (!any) continue;
-        a.plane0 = 3 * b0;
-        const dim3 grid(gx, gy, 3 * nb);
+    views_in_chunks(B, H, W, imgs, gts, grad_imgs, a.img, a.gt, a.grad, [&](int plane0, dim3 grid) {
+        a.plane0 = plane0;
         if (sanitize) hipLaunchKernelGGL(views_loss_bwd_kernel<true>, grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(views_loss_bwd_kernel<false>, grid, dim3(256), 0, s, a);
-    }
+    });
     return hipGetLastError();
 }
 
@@ -479,12 +472,19 @@ int32_t gsr_l1_ssim_workspace(int32_t C, int32_t H, int32_t W, size_t *bytes) {
     return GSR_OK;
 }
 
-int32_t gsr_l1_ssim_forward(gsr_stream_t stream, int32_t C, int32_t H, int32_t W, const float *img, const float *gt,
-                            float lambda_dssim, float *out3, void *ws, size_t ws_bytes) {
+// 0 = ok; everything the forward and the backward check alike, before anything is launched (out: out3 or grad_img)
+static int l1_ssim_check(const char *who, int32_t C, int32_t H, int32_t W, const float *img, const float *gt, const float *out, const void *ws,
+                         size_t ws_bytes) {
     size_t need = 0;
     if (gsr_l1_ssim_workspace(C, H, W, &need) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
-    if (!img || !gt || !out3 || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_l1_ssim_forward: null pointer");
+    if (!img || !gt || !out || !ws) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
     if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "loss workspace %zu < %zu", ws_bytes, need);
+    return GSR_OK;
+}
+
+int32_t gsr_l1_ssim_forward(gsr_stream_t stream, int32_t C, int32_t H, int32_t W, const float *img, const float *gt,
+                            float lambda_dssim, float *out3, void *ws, size_t ws_bytes) {
+    GSR_TRY(l1_ssim_check("gsr_l1_ssim_forward", C, H, W, img, gt, out3, ws, ws_bytes));
     const L1Ws w = l1_carve(ws, C, H, W);
     HIP_TRY(launch_l1_ssim_forward(C, H, W, img, gt, lambda_dssim, w.dmaps, w.partial, out3, (hipStream_t)stream), "l1+ssim forward launch");
     return GSR_OK;
@@ -492,10 +492,7 @@ int32_t gsr_l1_ssim_forward(gsr_stream_t stream, int32_t C, int32_t H, int32_t W
 
 int32_t gsr_l1_ssim_backward(gsr_stream_t stream, int32_t C, int32_t H, int32_t W, const float *img, const float *gt,
                              float lambda_dssim, const float *grad_loss, const void *ws, size_t ws_bytes, float *grad_img) {
-    size_t need = 0;
-    if (gsr_l1_ssim_workspace(C, H, W, &need) != GSR_OK) return GSR_ERR_INVALID_ARGUMENT;
-    if (!img || !gt || !ws || !grad_img) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_l1_ssim_backward: null pointer");
-    if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "loss workspace %zu < %zu", ws_bytes, need);
+    GSR_TRY(l1_ssim_check("gsr_l1_ssim_backward", C, H, W, img, gt, grad_img, ws, ws_bytes));
     HIP_TRY(launch_l1_ssim_backward(C, H, W, img, gt, lambda_dssim, l1_carve(const_cast<void *>(ws), C, H, W).dmaps, grad_loss, grad_img, (hipStream_t)stream),
             "l1+ssim backward launch");
     return GSR_OK;
@@ -517,7 +514,7 @@ static int views_loss_check(const char *who, int32_t B, int32_t H, int32_t W, co
 
 int32_t gsr_views_loss_workspace(int32_t B, int32_t H, int32_t W, size_t *bytes) {
     if (B < 1 || H < 1 || W < 1 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_workspace: bad argument (B=%d H=%d W=%d)", B, H, W);
-    if ((H + 15) / 16 > 65535 || (size_t)3 * ssim_tiles(H, W) > (size_t)INT32_MAX)
+    if (ssim_grid(H, W, 1).y > 65535 || (size_t)3 * ssim_tiles(H, W) > (size_t)INT32_MAX)
         return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_workspace: image %d x %d too large", W, H);
     *bytes = views_carve(nullptr, B, H, W).total_bytes;
     return GSR_OK;
@@ -525,8 +522,7 @@ int32_t gsr_views_loss_workspace(int32_t B, int32_t H, int32_t W, size_t *bytes)
 
 int32_t gsr_views_loss_forward(gsr_stream_t stream, int32_t B, int32_t H, int32_t W, const float *const *imgs, const float *const *gts,
                                float w_l1, float w_ssim, int32_t sanitize, float *out3, float *terms, void *ws, size_t ws_bytes) {
-    const int rc = views_loss_check("gsr_views_loss_forward", B, H, W, imgs, gts, ws, ws_bytes);
-    if (rc != GSR_OK) return rc;
+    GSR_TRY(views_loss_check("gsr_views_loss_forward", B, H, W, imgs, gts, ws, ws_bytes));
     if (!out3 || !terms) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_forward: null pointer (out3 or terms)");
     HIP_TRY(launch_views_loss_forward(B, H, W, imgs, gts, w_l1, w_ssim, sanitize ? 1 : 0, out3, terms, ws, (hipStream_t)stream),
             "views loss forward launch");
@@ -536,8 +532,7 @@ int32_t gsr_views_loss_forward(gsr_stream_t stream, int32_t B, int32_t H, int32_
 int32_t gsr_views_loss_backward(gsr_stream_t stream, int32_t B, int32_t H, int32_t W, const float *const *imgs, const float *const *gts,
                                 float w_l1, float w_ssim, int32_t sanitize, const float *grad_loss, const void *ws, size_t ws_bytes,
                                 float *const *grad_imgs) {
-    const int rc = views_loss_check("gsr_views_loss_backward", B, H, W, imgs, gts, ws, ws_bytes);
-    if (rc != GSR_OK) return rc;
+    GSR_TRY(views_loss_check("gsr_views_loss_backward", B, H, W, imgs, gts, ws, ws_bytes));
     if (!grad_imgs) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_views_loss_backward: null pointer (grad_imgs)");
     HIP_TRY(launch_views_loss_backward(B, H, W, imgs, gts, w_l1, w_ssim, sanitize ? 1 : 0, grad_loss, ws, grad_imgs, (hipStream_t)stream),
             "views loss backward launch");

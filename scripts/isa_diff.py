@@ -1,6 +1,6 @@
 """Compares the gfx950 assembly of translation units between a git revision and the working tree, kernel by kernel.
 
-    python scripts/isa_diff.py [--diff] <base-rev> [files...]          (default: the three compositing files)
+    python scripts/isa_diff.py [--diff] [--mix] <base-rev> [files...]          (default: the three compositing files)
 
 The gate of a refactor that must not change a shipped kernel: each named file of gaussian_transformer_amd/csrc is compiled to
 assembly (device side only) with the flags gaussian_transformer_amd/build.py gives it -- COMMON + SOURCES[file], imported, not
@@ -9,7 +9,8 @@ The listings are split per function symbol and normalised (comments, .file/.loc/
 from the source text, the function index in compiler-made labels); per kernel it prints `identical`, `reordered` or `differs` and the register,
 scratch and LDS figures of the code object's metadata from both sides.  `reordered`: another text of as many instructions, with the
 same multiset of mnemonics (first token of each line that is no label) and the same four figures.  Exit status 1 if any kernel
-differs or exists on one side only, 0 if every kernel is identical or reordered.  --diff adds a unified diff of each kernel that differs.
+differs or exists on one side only, 0 if every kernel is identical or reordered.  --diff adds a unified diff of each kernel that differs,
+--mix its instruction mix: the two instruction totals and every mnemonic whose count is not the same on both sides, with both counts.
 Host-only: needs hipcc, no GPU.  It compares text; it looks for no particular instruction.
 """
 from __future__ import annotations
@@ -111,6 +112,12 @@ def compare(base_text: str, new_text: str):
     return rows, bad
 
 
+def kernel_mix(base_text: str, new_text: str, sym: str):
+    """((instructions in base, in the working tree), [(mnemonic, count in base, in the working tree)] for the unequal counts, by name)"""
+    b, n = (_mnemonics(split_kernels(t)[sym]["body"]) for t in (base_text, new_text))
+    return (sum(b.values()), sum(n.values())), [(m, b[m], n[m]) for m in sorted(set(b) | set(n)) if b[m] != n[m]]
+
+
 def kernel_diff(base_text: str, new_text: str, sym: str) -> str:
     base, new = split_kernels(base_text), split_kernels(new_text)
     return "\n".join(difflib.unified_diff(base[sym]["body"], new[sym]["body"], "base", "working tree", lineterm="", n=2))
@@ -150,8 +157,8 @@ def _demangle(syms):
 
 
 def main(argv) -> int:
-    show = "--diff" in argv
-    argv = [a for a in argv if a != "--diff"]
+    show, mix = "--diff" in argv, "--mix" in argv
+    argv = [a for a in argv if a not in ("--diff", "--mix")]
     if len(argv) < 2 or argv[1].startswith("-"):
         print(__doc__)
         return 2
@@ -171,6 +178,9 @@ def main(argv) -> int:
         for sym, verdict, b, n in rows:
             fig = " ".join(f"{k.split('_')[0]}={(b or {}).get(k, '-')}/{(n or {}).get(k, '-')}" for k in FIGURES)
             print(f"{verdict:21s} {fig:44s} {names[sym]}")
+            if mix and verdict == "differs":
+                (tb, tn), rows_m = kernel_mix(texts[i], texts[len(files) + i], sym)
+                print(f"    instructions {tb}/{tn}; unequal counts: " + "  ".join(f"{m} {cb}/{cn}" for m, cb, cn in rows_m))
             if show and verdict == "differs":
                 print(kernel_diff(texts[i], texts[len(files) + i], sym))
         total += len(rows)

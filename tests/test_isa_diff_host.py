@@ -152,3 +152,12 @@ def test_reordered_plus_one_changed_mnemonic_or_one_changed_figure_differs():
     assert {r[0]: r[1] for r in rows} == {"_Z5alphav": "identical", "_Z5gammav": "differs"}
     g = [r for r in rows if r[0] == "_Z5gammav"][0]
     assert g[2]["vgpr_count"] == "12" and g[3]["vgpr_count"] == "13"
+
+
+def test_mix_lists_the_mnemonics_whose_counts_differ_with_both_counts_and_totals():
+    # one v_add_f32 becomes a v_sub_f32 and an s_nop is added: 6 -> 7 instructions (labels are none), three mnemonics move
+    changed = _GAMMA_REORDERED.replace("v_add_f32_e32 v5, v7, v5", "v_sub_f32_e32 v5, v7, v5").replace("\ts_endpgm", "\ts_nop 0\n\ts_endpgm")
+    base, new = _gamma_pair(changed)
+    assert isa_diff.kernel_mix(base, new, "_Z5gammav") == ((6, 7), [("s_nop", 0, 1), ("v_add_f32_e32", 2, 1), ("v_sub_f32_e32", 0, 1)])
+    # a kernel whose text is only reordered has equal totals and an empty table
+    assert isa_diff.kernel_mix(*_gamma_pair(_GAMMA_REORDERED), "_Z5gammav") == ((6, 6), [])
