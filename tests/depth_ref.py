@@ -24,6 +24,13 @@ MODES = {"expected": 0, "inverse": 1}
 # (P, W, H, s0, seed): make_scene(P, W, H, sh_degree=1, s0, seed); float32 against float64 oracle, both modes, pixels over 1e-4 vmax: 0 0 0 1 0
 SCENES = ((1, 16, 16, 0.3, 0), (64, 40, 24, 0.05, 1), (500, 64, 48, 0.05, 2), (3000, 96, 80, 0.03, 3), (4000, 64, 64, 0.08, 4))
 
+# The large image, under a name of its own (other modules index SCENES): more than 6144 tiles, so the forward pass has no pair kernel
+# and files half-tile lengths for the length-ordered reverse kernel.  make_scene(**LARGE): 101 x 63 = 6363 tiles, 5 of them with an
+# empty range, 67452 pairs, longest list 23.  float32 against float64 oracle through helpers.assert_image_certified, both modes: 2
+# pixels over tolerance, 0 uncertified, against the cap max(3, MAX_CERTIFIED_FRAC * pixels) = 16
+# (tests/test_depth_ref_host.py::test_the_large_scene_certifies_itself).
+LARGE = dict(P=600, width=1616, height=1008, sh_degree=1, s0=0.05, seed=7)
+
 
 def values(z, radii, mode):
     """v per Gaussian (float64): z or 1 / z; 0 for a culled Gaussian, whose stored depth means nothing."""

@@ -84,3 +84,32 @@ def test_planted_faults_are_told_from_the_correct_result(fault):
         assert (dD <= 1e-6).all()          # this fault lives in the alpha map alone
     if fault == "normalised":
         assert (dA <= 1e-6).all()
+
+
+@pytest.mark.parametrize("mode", ["expected", "inverse"])
+def test_the_large_scene_certifies_itself(mode):
+    """depth_ref.LARGE, the reference alone: the float64 oracle's [D / vmax, A, 0] against the float32 oracle's through the certificate
+    the GPU tests apply, and the float32 oracle's gradients in the place of a device's through assert_parity.  Measured, both modes:
+    6363 tiles, 5 empty, 67452 pairs, longest list 23; 2 pixels over tolerance, 0 uncertified, cap max(3, 1e-5 * 1628928) = 16."""
+    from oracle import ref
+    from tests.helpers import MAX_CERTIFIED_FRAC, assert_image_certified, assert_parity, build_report
+    S = oracle_scene(synth.make_scene(**dr.LARGE))
+    t32 = dr.trick_forward(S, mode, "f32", scale="vmax")
+    r64 = ref.get("f64")
+    f64 = r64.forward(t32["scene"], nthreads=r64.max_threads())
+    ranges = np.asarray(t32["base_fwd"]["state"].binning()["ranges"], np.int64)
+    lengths = ranges[:, 1] - ranges[:, 0]
+    st = assert_image_certified(f64["color"], t32["fwd"]["color"], t32["fwd"]["state"].decision_margin())
+    cap = max(3, MAX_CERTIFIED_FRAC * st["pixels"])
+    print(mode, st, "tiles", len(lengths), "empty", int((lengths == 0).sum()), "pairs", int(lengths.sum()), "longest", int(lengths.max()), "cap", cap)
+    assert st["over"] <= cap / 4, (st, cap)                   # the reference alone uses at most a quarter of what a device is allowed
+    assert (lengths == 0).any()                               # some tile is empty
+    assert len(lengths) == ((S.W + 15) // 16) * ((S.H + 15) // 16) > 6144      # past the persistent kernels' image size
+    rng = np.random.default_rng(11)
+    gD, gA = rng.normal(size=(S.H, S.W)) / (S.H * S.W), rng.normal(size=(S.H, S.W)) / (S.H * S.W)
+    g32 = dr.trick_backward(t32, S, mode, gD, gA, "f32")
+    g64 = dr.trick_backward(dict(t32, fwd=f64), S, mode, gD, gA, "f64")
+    names = (("means3D", "dL_dmeans3D"), ("means2D", "dL_dmeans2D"), ("opacities", "dL_dopacity"), ("scales", "dL_dscales"), ("rotations", "dL_drots"))
+    G32 = {k: np.asarray(g32[r], np.float64).reshape(S.means3D.shape[0], -1) for k, r in names}
+    G64 = {k: np.asarray(g64[r], np.float64).reshape(G32[k].shape) for k, r in names}
+    assert_parity(build_report(t32["scene"], t32["fwd"], f64, t32["fwd"]["color"], G32, G32, G64, radii_equal=True))
