@@ -142,6 +142,23 @@ DEPTH_SIGNATURES = {
                                   _p, _p, _p, _p, _p, _p]),                              # dL_d{means2D opacity means3D cov3D scales rots}
 }
 
+# include/gsr_features.h (likewise a table of its own)
+FEATURES_MAX_C = 64
+FEATURES_SIGNATURES = {
+    "gsr_features_workspace_bytes": (_i32, [_i32, _i32, C.POINTER(_sz)]),                # P C bytes
+    "gsr_features_forward": (_i32, [_p, _i32, _i32, _i32, _i32, C.c_int64, _p,           # stream P C W H R features
+                                    _p, _sz, _p, _sz, _p, _sz,                           # geom binning img (+bytes)
+                                    _p]),                                                # out
+    "gsr_features_backward": (_i32, [_p, _i32, _i32, _i32, _i32, C.c_int64,              # stream P C W H R
+                                     _p, _p, _p, _f, _p, _p,                             # means3D radii scales mod rotations cov3D
+                                     _p, _p, _p, _f, _f,                                 # view proj campos tanfovx tanfovy
+                                     _p, _p,                                             # features dL_dout
+                                     _p, _sz, _p, _sz, _p, _sz, _p, _sz,                 # geom binning img ws (+bytes)
+                                     _i32,                                               # accumulate
+                                     _p, _p, _p, _p, _p, _p,                             # dL_d{means2D opacity means3D cov3D scales rots}
+                                     _p]),                                               # dL_dfeatures
+}
+
 # include/gsr_pose.h (likewise a table of its own)
 POSE_COLOR, POSE_DEPTH_EXPECTED, POSE_DEPTH_INVERSE = 0, 1, 2
 POSE_SIGNATURES = {
@@ -180,7 +197,7 @@ def load() -> C.CDLL:
         except OSError as e:
             raise GsrError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES, **SEQUENCE_SIGNATURES, **ROWS_SIGNATURES, **DENSITY_SIGNATURES,
-                                   **DEPTH_SIGNATURES, **POSE_SIGNATURES}.items():
+                                   **DEPTH_SIGNATURES, **FEATURES_SIGNATURES, **POSE_SIGNATURES}.items():
             fn = getattr(lib, name)       # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

@@ -49,6 +49,9 @@ SOURCES = {
     # as composite_bwd.hip, whose staging, replica rows and LDS reduction it shares (csrc/composite_common.h) under recurrences of its own
     # for the depth and alpha maps (include/gsr_depth.h): native float atomic add, no packed f32 pairs
     "depth_maps.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],
+    # as depth_maps.hip, whose walks it restates for C channels per Gaussian (include/gsr_features.h): the alpha decisions are the colour
+    # pass's bit for bit under the same flags
+    "feature_maps.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],
     # as pergauss_bwd.hip, whose chain (csrc/pergauss_chain.h) it calls up to the terms the camera gradient shares with dL/dmeans3D
     # (include/gsr_pose.h)
     "pose_grad.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],

@@ -285,6 +285,53 @@ class HipBackend:
         ann = self._announced.get(geom.device.index)
         return ann is not None and ann[0] == geom.data_ptr() and ann[4] is not None
 
+    def _map_outputs(self, dev, P, has_sr, has_cov, geom, into, sh_floats):
+        """The six tensors a map's reverse pass (depth_backward, features_backward) writes or adds into: `into` itself, or new ones --
+        slices of the gradient arena when one is set, whose SH slice (sh_floats = 3 M per Gaussian) is then zeroed: the maps have no SH
+        gradient."""
+        if into is not None:
+            return into
+        M = sh_floats // 3
+        arena = _usable_arena(dev, P, M, has_sr)
+        self._release_arena(geom)
+        g_means3D, g_means2D, g_sh, _c, g_opacity, g_scales, g_rots, g_cov3D, _r = self._gradient_outputs(
+            dev, P, M if arena is not None else 0, 0, has_sr, False, has_cov, arena)
+        if arena is not None and g_sh.numel():
+            g_sh.zero_()
+        return g_means3D, g_means2D, g_opacity, g_scales, g_rots, g_cov3D
+
+    def features_forward(self, rs, P, num_rendered, features, geom, binning, img):
+        """The [C,H,W] map of `features` [P,C] over the render whose gsr_forward filled the three workspaces (include/gsr_features.h)."""
+        dev = geom.device
+        H, W, Cn = int(rs.image_height), int(rs.image_width), int(features.shape[1])
+        out = torch.empty((Cn, H, W), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call("gsr_features_forward", _lib.stream(dev), P, Cn, W, H, int(num_rendered), ptr(features),
+                      ptr(geom), geom.numel(), ptr(binning), binning.numel(), ptr(img), img.numel(), ptr(out))
+        return out
+
+    def features_backward(self, rs, num_rendered, features, dL_dout, means3D, radii, scales, rotations, cov3D_precomp,
+                          geom, binning, img, into=None, sh_floats=0, want_features_grad=True):
+        """Gradients of a feature map (include/gsr_features.h).  into: as depth_backward -- None: new tensors, accumulate = 0; the six
+        tensors earlier passes of the same render wrote: added to, accumulate = 1.  Returns that tuple followed by dL/dfeatures
+        [P,C], or None for it when want_features_grad is off (the library then forms none of its sums)."""
+        dev = means3D.device
+        P, H, W, Cn = int(means3D.shape[0]), int(rs.image_height), int(rs.image_width), int(features.shape[1])
+        has_sr, has_cov = scales.numel() > 0, cov3D_precomp.numel() > 0
+        with torch.cuda.device(dev):
+            g_means3D, g_means2D, g_opacity, g_scales, g_rots, g_cov3D = self._map_outputs(dev, P, has_sr, has_cov, geom, into, sh_floats)
+            g_feat = torch.empty((P, Cn), dtype=torch.float32, device=dev) if want_features_grad else None
+            ws = _lib.workspace("gsr_features_workspace_bytes", dev, P, Cn)
+            vm, pm, cp = _camera(rs, dev)
+            gF = _f32c(dL_dout, "grad of the feature map", dev)
+            _lib.call(
+                "gsr_features_backward", _lib.stream(dev), P, Cn, W, H, int(num_rendered), ptr(means3D), ptr(radii), ptr(scales),
+                float(rs.scale_modifier), ptr(rotations), ptr(cov3D_precomp), ptr(vm), ptr(pm), ptr(cp), float(rs.tanfovx), float(rs.tanfovy),
+                ptr(features), ptr(gF), ptr(geom), geom.numel(), ptr(binning), binning.numel(), ptr(img), img.numel(),
+                ptr(ws), ws.numel(), 0 if into is None else 1,
+                ptr(g_means2D), ptr(g_opacity), ptr(g_means3D), ptr(g_cov3D), ptr(g_scales), ptr(g_rots), ptr(g_feat))
+        return g_means3D, g_means2D, g_opacity, g_scales, g_rots, g_cov3D, g_feat
+
     def depth_backward(self, rs, num_rendered, mode, dL_ddepth, dL_dalpha, means3D, radii, scales, rotations, cov3D_precomp,
                        geom, binning, img, into=None, sh_floats=0, return_ws=False):
         """Gradients of the depth and alpha maps (include/gsr_depth.h).  into = None: new tensors (slices of the gradient arena when one
@@ -296,16 +343,7 @@ class HipBackend:
         P, H, W = int(means3D.shape[0]), int(rs.image_height), int(rs.image_width)
         has_sr, has_cov = scales.numel() > 0, cov3D_precomp.numel() > 0
         with torch.cuda.device(dev):
-            if into is None:
-                M = sh_floats // 3
-                arena = _usable_arena(dev, P, M, has_sr)
-                self._release_arena(geom)
-                g_means3D, g_means2D, g_sh, _c, g_opacity, g_scales, g_rots, g_cov3D, _r = self._gradient_outputs(
-                    dev, P, M if arena is not None else 0, 0, has_sr, False, has_cov, arena)
-                if arena is not None and g_sh.numel():
-                    g_sh.zero_()
-            else:
-                g_means3D, g_means2D, g_opacity, g_scales, g_rots, g_cov3D = into
+            g_means3D, g_means2D, g_opacity, g_scales, g_rots, g_cov3D = self._map_outputs(dev, P, has_sr, has_cov, geom, into, sh_floats)
             ws = _lib.workspace("gsr_depth_workspace_bytes", dev, P)
             vm, pm, cp = _camera(rs, dev)
             gD = None if dL_ddepth is None else _f32c(dL_ddepth, "grad of the depth map", dev)
@@ -543,7 +581,7 @@ def _reverse_passes(ctx, be, grad_color, grad_depth, grad_alpha, camera_pass=Non
     of the eight Gaussian inputs.  camera_pass: called as camera_pass(pose kind, workspace) right after each pass whose loss the
     caller differentiates, while that pass is the last one on the stream; the workspaces are asked for (return_ws) only then."""
     rs = ctx.raster_settings
-    colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img = ctx.saved_tensors
+    colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img = ctx.saved_tensors[:10]      # (a feature render keeps an eleventh)
     maps = grad_depth is not None or grad_alpha is not None
     keep_ws = {} if camera_pass is None else {"return_ws": True}
     g_sh = g_colors = None
@@ -596,6 +634,58 @@ class _RasterizeGaussiansDepth(torch.autograd.Function):
         if grad_color is None and grad_depth is None and grad_alpha is None:
             return (None,) * 10
         return _reverse_passes(ctx, get_backend(), grad_color, grad_depth, grad_alpha) + (None, None)
+
+
+class _RasterizeGaussiansFeatures(torch.autograd.Function):
+    """(color, radii, feature_map) for mode None, (color, radii, depth, alpha, feature_map) for a depth mode: _RasterizeGaussians' or
+    _RasterizeGaussiansDepth's render followed by the [C,H,W] map of `features` [P,C] over the same lists (include/gsr_features.h).
+    Backward runs what the losses used: the passes of _reverse_passes for colour, depth and alpha, then the feature pass adding into
+    their tensors -- or the feature pass alone; a map whose gradient is None costs no reverse pass."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, features, raster_settings, mode):
+        be = get_backend()
+        if not hasattr(be, "features_forward") or (mode is not None and not hasattr(be, "depth_forward")):
+            raise _lib.GsrError(f"the {getattr(be, 'name', type(be).__name__)} backend renders no feature map")
+        args = _gaussian_inputs(means3D, (sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp), _INPUT_NAMES)
+        means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c = args
+        feat_c = _f32c(features, "features", means3D.device)
+        P = int(means3D_c.shape[0])
+        num_rendered, color, radii, geom, binning, img = be.forward(
+            raster_settings, means3D_c, sh_c, colors_c, opac_c, scales_c, rots_c, cov_c, **_announce(ctx, be))
+        fmap = be.features_forward(raster_settings, P, num_rendered, feat_c, geom, binning, img)
+        ctx.raster_settings, ctx.num_rendered, ctx.depth_mode = raster_settings, num_rendered, mode
+        _keep(ctx, (colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img, feat_c), 7, 1, radii)
+        if mode is None:
+            return color, radii, fmap
+        depth, alpha = be.depth_forward(raster_settings, P, num_rendered, mode, geom, binning, img)
+        return color, radii, depth.unsqueeze(0), alpha.unsqueeze(0), fmap
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii, *grad_maps):
+        grad_depth, grad_alpha = (None, None) if ctx.depth_mode is None else grad_maps[:2]
+        grad_feat = grad_maps[-1]
+        others = grad_color is not None or grad_depth is not None or grad_alpha is not None
+        if not others and grad_feat is None:
+            return (None,) * 11
+        be = get_backend()
+        _colors_c, means3D_c, scales_c, rots_c, cov_c, radii, sh_c, geom, binning, img, feat_c = ctx.saved_tensors
+        g = None
+        # the feature pass alone must not write into an arena the library may still be zero-filling: the colour pass joins that fill
+        # and runs first, on a zero gradient (_reverse_passes does that when it is given nothing)
+        if others or (hasattr(be, "arena_fill_in_flight") and be.arena_fill_in_flight(geom)):
+            g = _reverse_passes(ctx, be, grad_color, grad_depth, grad_alpha)
+        g_feat = None
+        if grad_feat is not None:
+            into = None if g is None else (g[0], g[1], g[4], g[5], g[6], g[7])
+            g_means3D, g_means2D, g_opac, g_scales, g_rots, g_cov, g_feat = be.features_backward(
+                ctx.raster_settings, ctx.num_rendered, feat_c, grad_feat, means3D_c, radii, scales_c, rots_c, cov_c, geom, binning, img,
+                into=into, sh_floats=3 * int(sh_c.shape[1]) if sh_c.numel() else 0, want_features_grad=ctx.needs_input_grad[8])
+            if g is None:
+                none_if_empty = lambda t, src: t if (t is not None and src.numel() > 0) else None
+                g = (g_means3D, g_means2D, None, None, g_opac, none_if_empty(g_scales, scales_c), none_if_empty(g_rots, rots_c),
+                     none_if_empty(g_cov, cov_c))
+        return g + (g_feat, None, None)
 
 
 class _RasterizeGaussiansPose(torch.autograd.Function):
@@ -706,15 +796,25 @@ class GaussianRasterizer(nn.Module):
             return get_backend().mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, depth=None):
+                cov3D_precomp=None, depth=None, features=None):
         """depth = None: (color, radii), the reference's call.  depth = "expected" or "inverse": (color, radii, depth, alpha) with
         depth [1,H,W] = sum z alpha T (or sum (1/z) alpha T), not normalised, no background term, and alpha [1,H,W] = 1 - T_final;
         gradients flow from all three images.  When grad mode is on and viewmatrix, projmatrix or campos of the settings requires
         grad, the camera receives gradients as well (_RasterizeGaussiansPose, include/gsr_pose.h); every other call goes where it
-        went before."""
+        went before.
+        features = [P,C] float32 on the device, 1 <= C <= 64 (any strides, leaf or not): feature_map [C,H,W] = sum F[g, c] alpha T over
+        the entries the colour pass blended, not normalised, no background term (include/gsr_features.h), is appended to what the
+        call returns otherwise -- (color, radii, feature_map) or (color, radii, depth, alpha, feature_map) -- and gradients flow from
+        every image to the Gaussians and from the map to `features`.  No camera gradient of the map is formed: camera tensors that
+        require grad are refused together with `features`."""
         rs = self.raster_settings
         if depth is not None and depth not in DEPTH_MODES:
             raise _lib.GsrError(f"depth must be None, 'expected' or 'inverse', got {depth!r}")
+        if features is not None:
+            _lib.require_tensor("GaussianRasterizer", "features", features)
+            if features.dim() != 2 or features.shape[0] != means3D.shape[0] or not 1 <= features.shape[1] <= _lib.FEATURES_MAX_C:
+                raise _lib.GsrError(f"features must have dimensions (num_points, C) with 1 <= C <= {_lib.FEATURES_MAX_C}, "
+                                    f"got {tuple(features.shape)} for {int(means3D.shape[0])} points")
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -727,6 +827,13 @@ class GaussianRasterizer(nn.Module):
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
         cam = (rs.viewmatrix, rs.projmatrix, rs.campos)
+        if features is not None:
+            if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in cam):
+                raise _lib.GsrError("features together with camera tensors that require grad: no camera gradient of the feature map "
+                                    "is formed (include/gsr_pose.h) -- detach viewmatrix, projmatrix and campos, or render the features "
+                                    "in a call of their own")
+            return _RasterizeGaussiansFeatures.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                                     features, rs, None if depth is None else DEPTH_MODES[depth])
         if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in cam):
             return _RasterizeGaussiansPose.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                                  *cam, rs, None if depth is None else DEPTH_MODES[depth])

@@ -12,6 +12,7 @@ from dataclasses import dataclass
 
 import torch
 
+from ._lib import GsrError
 from .rasterizer import GaussianRasterizer, camera_settings, rasterize_gaussians_fused
 
 
@@ -44,11 +45,12 @@ def eval_sh_torch(deg: int, sh: torch.Tensor, dirs: torch.Tensor) -> torch.Tenso
     return result
 
 
-def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0, override_color=None, depth=None):
+def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0, override_color=None, depth=None,
+           features=None):
     """viewpoint_camera: anything with image_height/width, FoVx/FoVy, world_view_transform,
     full_proj_transform, camera_center (torch tensors on the device).  pc: GaussianParams-like.
     depth: None (the reference's dict), or "expected" / "inverse": the dict also holds "depth" and "alpha", [1,H,W] each
-    (GaussianRasterizer.forward)."""
+    (GaussianRasterizer.forward).  features: None, or [P,C] float32: the dict also holds "features", the [C,H,W] map of them."""
     xyz = pc.get_xyz
     screenspace_points = torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True, device=xyz.device) + 0
     try:
@@ -74,6 +76,16 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
             shs = pc.get_features
     else:
         colors_precomp = override_color
+    if features is not None:
+        extra = {} if depth is None else {"depth": depth}
+        rendered_image, radii, *maps = rasterizer(
+            means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity, scales=scales,
+            rotations=rotations, cov3D_precomp=cov3D_precomp, features=features, **extra)
+        out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
+               "features": maps[-1]}
+        if depth is not None:
+            out["depth"], out["alpha"] = maps[0], maps[1]
+        return out
     if depth is not None:
         rendered_image, radii, depth_map, alpha_map = rasterizer(
             means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity, scales=scales,
@@ -85,11 +97,15 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
     return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
 
 
-def render_fused(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0):
+def render_fused(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0, features=None):
     """Same result dict as render(), through the fused-step entry point: the raw parameters
     of the model go straight to the kernels -- no exp / sigmoid / normalize / cat tensors, no autograd nodes
     for them.  Only the default configuration of render() (SH colours, scale/rotation covariance) is
-    covered; use render() for override_color / convert_SHs_python / compute_cov3D_python."""
+    covered; use render() for override_color / convert_SHs_python / compute_cov3D_python, and for feature maps:
+    `features` is refused here (include/gsr_features.h has no raw_params form)."""
+    if features is not None:
+        raise GsrError("render_fused: no feature maps on the raw-parameter path (include/gsr_features.h has no raw_params form): "
+                       "use render(features=...)")
     xyz = pc._xyz
     screenspace_points = torch.zeros_like(xyz, requires_grad=True) + 0
     try:

@@ -142,7 +142,7 @@ class _RenderRows(torch.autograd.Function):
             return _pack(arenas, P, D, dev), None, None
 
 
-def render_rows(cameras, rows: torch.Tensor, pipe, bg: torch.Tensor, scaling_modifier: float = 1.0, sh_degree=None) -> dict:
+def render_rows(cameras, rows: torch.Tensor, pipe, bg: torch.Tensor, scaling_modifier: float = 1.0, sh_degree=None, features=None) -> dict:
     """Renders float32 rows [P, 3 K + 14] (K in 1, 4, 9, 16) on a HIP device under every camera of `cameras` (the objects render()
     takes; they may differ in size).  Returns {"renders": list of B images [3, H_b, W_b], "radii": [B, P] int32,
     "visibility_filter": [P] bool, the OR over the cameras of radii > 0}.
@@ -157,8 +157,11 @@ def render_rows(cameras, rows: torch.Tensor, pipe, bg: torch.Tensor, scaling_mod
     No camera gradient: the cameras' tensors are constants here even when they require grad (the raw-parameter path has none,
     include/gsr_pose.h).
     `rasterizer.composited_mask()` without an argument refers to the LAST camera's render afterwards (while the images' graph is
-    alive: a no_grad call keeps no workspace); composited_mask(image) does not know the images of this function and returns None."""
+    alive: a no_grad call keeps no workspace); composited_mask(image) does not know the images of this function and returns None.
+    `features`: refused -- the raw-parameter path has no feature maps (include/gsr_features.h); render() takes the keyword."""
     who = "render_rows"
+    if features is not None:
+        raise _lib.GsrError(f"{who}: no feature maps on the raw-parameter path (include/gsr_features.h has no raw_params form): use render(features=...)")
     K = _check_rows(who, rows)
     cameras = list(cameras)
     if len(cameras) < 1:
