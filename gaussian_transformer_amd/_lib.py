@@ -126,6 +126,29 @@ DENSITY_SIGNATURES = {
                                  _p, _p, _p, _p, _sz]),                                  # scaling rotation noise ws ws_bytes
 }
 
+# include/gsr_mcmc.h (likewise a table of its own)
+MCMC_MAX_GROUPS, MCMC_N_MAX = 16, 51
+MCMC_RELOCATE, MCMC_GROW = 0, 1
+MCMC_COPY, MCMC_OPACITY, MCMC_SCALING = 0, 1, 2
+
+
+class McmcGroup(C.Structure):          # gsr_mcmc_group_t of include/gsr_mcmc.h
+    _fields_ = [("src", C.c_void_p), ("src_exp_avg", C.c_void_p), ("src_exp_avg_sq", C.c_void_p),
+                ("dst", C.c_void_p), ("dst_exp_avg", C.c_void_p), ("dst_exp_avg_sq", C.c_void_p),
+                ("width_floats", C.c_int32), ("role", C.c_int32)]
+
+
+MCMC_SIGNATURES = {
+    "gsr_mcmc_plan_workspace": (_i32, [_i32, _i32, C.POINTER(_sz)]),                     # P n_draws bytes
+    "gsr_mcmc_plan": (_i32, [_p, _i32, _i32, _p, _p, _f, C.c_double, _i32, _i32,         # stream mode P opacity scaling L min_opacity n_max n_draws
+                             _p, _p, _p, _sz]),                                          # u counts_host ws ws_bytes
+    "gsr_mcmc_apply": (_i32, [_p, _i32, _i32, _i32, _i32, C.POINTER(McmcGroup), _p, _sz]),   # stream mode P n_draws n_groups groups ws ws_bytes
+    "gsr_mcmc_noise": (_i32, [_p, _i32, _p, _p, _p, _p, _p, _f, _f, _f]),                # stream P opacity scaling rotation noise xyz gate_k gate_t scale
+    "gsr_mcmc_regularize_workspace": (_i32, [_i32, C.POINTER(_sz)]),                     # P bytes
+    "gsr_mcmc_regularize": (_i32, [_p, _i32, _p, _p, _p, _i32, _p, _i32,                 # stream P opacity scaling grad_opacity stride_o grad_scaling stride_s
+                                   C.c_double, C.c_double, _p, _p, _sz]),                # lambda_o lambda_s means_out ws ws_bytes
+}
+
 # include/gsr_depth.h (likewise a table of its own)
 DEPTH_EXPECTED, DEPTH_INVERSE = 0, 1
 DEPTH_SIGNATURES = {
@@ -197,7 +220,7 @@ def load() -> C.CDLL:
         except OSError as e:
             raise GsrError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES, **SEQUENCE_SIGNATURES, **ROWS_SIGNATURES, **DENSITY_SIGNATURES,
-                                   **DEPTH_SIGNATURES, **FEATURES_SIGNATURES, **POSE_SIGNATURES}.items():
+                                   **MCMC_SIGNATURES, **DEPTH_SIGNATURES, **FEATURES_SIGNATURES, **POSE_SIGNATURES}.items():
             fn = getattr(lib, name)       # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

@@ -45,7 +45,9 @@ SOURCES = {
     "chamfer.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],
     "sequence.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],   # as preprocess.hip: gsr_visible_union's radii must round as gsr_forward's
     "density.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],    # record's norm and the split children round as written (include/gsr_density.h)
-    "rows.hip": [],                # copies and float adds only (include/gsr_rows.h): nothing to contract
+    # as density.hip: a draw's t_j is one IEEE double multiply and the regularisers' gradients round as written (include/gsr_mcmc.h)
+    "mcmc.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    "rows.hip": [],               # copies and float adds only (include/gsr_rows.h): nothing to contract
     # as composite_bwd.hip, whose staging, replica rows and LDS reduction it shares (csrc/composite_common.h) under recurrences of its own
     # for the depth and alpha maps (include/gsr_depth.h): native float atomic add, no packed f32 pairs
     "depth_maps.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],

@@ -10,6 +10,10 @@ DensityController, which stays the oracle.
 
 One deliberate extension: `densify_and_split` draws its samples from a caller-supplied torch.Generator, so
 data-parallel ranks that seed it identically split identically (the reference uses the global RNG).
+
+MCMCController / FusedMCMCController, after them, are a second strategy that is not in the reference (Kheradmand et al. 2024,
+include/gsr_mcmc.h): a fixed budget, relocation of dead Gaussians, growth to a count the host knows in advance, position noise
+and two regularisers -- in torch index arithmetic (the oracle) and on the HIP path.  Opt-in as well.
 """
 from __future__ import annotations
 
@@ -365,3 +369,378 @@ class FusedDensityController(DensityController):
         # 7. statistics of the new set
         self._reset_statistics(P_new, dev)
         return {"cloned": n_clone, "split": n_split, "pruned": n_pruned}
+
+
+# ---- MCMC density control (include/gsr_mcmc.h): a fixed budget, relocation, growth, noise, two regularisers ----
+
+@dataclass
+class MCMCParams:
+    """Kheradmand et al. 2024, "3D Gaussian Splatting as Markov Chain Monte Carlo"; cap_max is the budget of Gaussians."""
+    cap_max: int
+    min_opacity: float = 0.005
+    noise_lr: float = 5e5
+    refine_start: int = 500
+    refine_stop: int = 25_000
+    refine_every: int = 100
+    grow_factor_percent: int = 105
+    opacity_reg: float = 0.01
+    scale_reg: float = 0.01
+    n_max: int = 51
+    gate_k: float = 100.0
+    gate_t: float = 0.005
+
+
+def _binomial_table(n_max: int) -> torch.Tensor:
+    """[n_max + 1, n_max] float64: row N, column k holds C(N, k + 1) (0 beyond N); exact in double up to C(51, .)."""
+    return torch.tensor([[float(math.comb(N, k + 1)) for k in range(n_max)] for N in range(n_max + 1)], dtype=torch.float64)
+
+
+class MCMCController(DensityController):
+    """The rule of include/gsr_mcmc.h in torch index arithmetic, on the CPU or the device that holds the Gaussians: int64 cumsum,
+    searchsorted, bincount, the correction in float64.  The oracle of FusedMCMCController.  It keeps none of the gradient
+    statistics: P changes only in grow(), to a number the host computes from P alone.
+
+    Deviation from the published code, on purpose: every row whose parameters were replaced -- sources, relocated rows, appended
+    rows -- starts with zero Adam moments (the published code leaves a relocated row the dead Gaussian's moments)."""
+
+    def __init__(self, model: GaussianParams, mcmc: MCMCParams, opt: Optional[OptimizationParams] = None, spatial_lr_scale: float = 1.0,
+                 fused_adam: bool = False, adam: str = "torch"):
+        super().__init__(model, opt, spatial_lr_scale=spatial_lr_scale, fused_adam=fused_adam, adam=adam)
+        if not 1 <= mcmc.n_max <= _lib.MCMC_N_MAX:
+            raise ValueError(f"n_max must lie in 1..{_lib.MCMC_N_MAX}, got {mcmc.n_max}")
+        if not 0.0 < mcmc.min_opacity < 1.0:
+            raise ValueError(f"min_opacity must lie in (0, 1), got {mcmc.min_opacity}")
+        self.mcmc = mcmc
+        m = mcmc.min_opacity
+        self.dead_logit = float(np.float32(math.log(m / (1.0 - m))))      # L: the comparison is on the logit
+        self._last = {}                                                    # counts of the last relocate / grow
+
+    # ---- helpers ----
+    def _param(self, name: str) -> torch.Tensor:
+        return next(g["params"][0] for g in self.optimizer.param_groups if g["name"] == name)
+
+    def _xyz_lr_now(self) -> float:
+        return float(next(g["lr"] for g in self.optimizer.param_groups if g["name"] == "xyz"))
+
+    def grown_size(self, P: int) -> int:
+        """P after a growth step: min(cap_max, floor(1.05 P)) in integer arithmetic, never below P."""
+        return max(P, min(int(self.mcmc.cap_max), (P * int(self.mcmc.grow_factor_percent)) // 100))
+
+    def record(self, *args, **kwargs) -> None:
+        """The rule reads only parameters: no statistics."""
+
+    def counts(self, which: str = "relocate") -> Dict[str, int]:
+        """{"n_dead", "n_draws", "n_sources", "P_new"} of the last relocate() or grow()."""
+        return dict(self._last[which])
+
+    def _uniforms(self, n: int, generator, u, dev) -> torch.Tensor:
+        if u is None:
+            u = torch.rand(n, generator=generator, device=dev, dtype=torch.float32)
+        if u.dtype != torch.float32 or u.dim() != 1 or u.shape[0] < n:
+            raise ValueError(f"u must be float32 [>= {n}], got {u.dtype} {tuple(u.shape)}")
+        return u.to(dev).contiguous()
+
+    def _draws(self, u: torch.Tensor, n_grow: Optional[int]):
+        """(dead [P] bool, src [n] int64, c [P] int64, total) -- n = n_dead for relocation (n_grow None), n_grow for growth."""
+        op = self._param("opacity").detach().reshape(-1)
+        P = op.shape[0]
+        dead = op <= self.dead_logit
+        w = torch.floor(torch.sigmoid(op.double()) * float(1 << 20) + 0.5).to(torch.int64)
+        w[dead] = 0
+        cdf = torch.cumsum(w, dim=0)
+        total = int(cdf[-1]) if P else 0
+        n = int(dead.sum()) if n_grow is None else n_grow
+        if total == 0:
+            return dead, None, torch.zeros(P, dtype=torch.int64, device=op.device), 0
+        t = torch.floor(u[:n].double() * float(total)).to(torch.int64).clamp_(max=total - 1)
+        src = torch.searchsorted(cdf, t, right=True)               # the smallest i with C_i > t
+        return dead, src, torch.bincount(src, minlength=P), total
+
+    def _correction(self, rows: torch.Tensor, c: torch.Tensor):
+        """New opacity logits [S, 1] and log scales [S, 3] of the sources `rows` drawn c times, float64 rounded once."""
+        mc = self.mcmc
+        lg = self._param("opacity").detach().reshape(-1)[rows].double()
+        N = torch.clamp(c + 1, max=mc.n_max)
+        o, q = torch.sigmoid(lg), torch.sigmoid(-lg)                # q = 1 - o without the cancellation
+        lq = torch.log(q) / N
+        x = -torch.expm1(lq)
+        k = torch.arange(mc.n_max, device=lg.device, dtype=torch.float64)
+        sign = 1.0 - 2.0 * (k % 2)
+        terms = _binomial_table(mc.n_max).to(lg.device)[N] * sign * torch.pow(x[:, None], k + 1.0) / torch.sqrt(k + 1.0)
+        D = terms.sum(dim=1)
+        new_sc = (self._param("scaling").detach()[rows].double() + torch.log(o / D)[:, None]).float()
+        oc = x.clamp(min=mc.min_opacity, max=1.0 - 2.0 ** -23)
+        rest = torch.where(oc == x, torch.exp(lq), 1.0 - oc)
+        return torch.log(oc / rest).float()[:, None], new_sc
+
+    # ---- the two changes of the set ----
+    def relocate(self, generator: Optional[torch.Generator] = None, u: Optional[torch.Tensor] = None) -> None:
+        """Every dead Gaussian becomes a copy of a live one drawn by opacity; the sources are corrected.  P is unchanged.
+        Always consumes P uniforms of `generator`, whatever the number of dead rows."""
+        P, dev = self._param("xyz").shape[0], self._param("xyz").device
+        u = self._uniforms(P, generator, u, dev)
+        dead, src, c, total = self._draws(u, None)
+        n_dead = int(dead.sum()) if P else 0
+        if total == 0 or n_dead == 0:
+            self._last["relocate"] = {"n_dead": n_dead, "n_draws": n_dead if total else 0, "n_sources": 0, "P_new": P}
+            return
+        srcs = (c > 0).nonzero().reshape(-1)
+        dest = dead.nonzero().reshape(-1)
+        new = dict(zip(("opacity", "scaling"), self._correction(srcs, c[srcs])))
+
+        def param_fn(n, p):
+            p = p.clone()
+            if n in new:
+                p[srcs] = new[n]
+            p[dest] = p[src]
+            return p
+
+        def moment_fn(n, m):
+            m = m.clone()
+            m[srcs] = 0
+            m[dest] = 0
+            return m
+        self._remap(param_fn, moment_fn)
+        self._last["relocate"] = {"n_dead": n_dead, "n_draws": n_dead, "n_sources": int(srcs.shape[0]), "P_new": P}
+
+    def grow(self, generator: Optional[torch.Generator] = None, u: Optional[torch.Tensor] = None) -> int:
+        """Appends min(cap_max, floor(1.05 P)) - P copies of live Gaussians drawn by opacity; returns the new P."""
+        P, dev = self._param("xyz").shape[0], self._param("xyz").device
+        P_new = self.grown_size(P)
+        n = P_new - P
+        if n == 0:
+            self._last["grow"] = {"n_dead": 0, "n_draws": 0, "n_sources": 0, "P_new": P}
+            return P
+        u = self._uniforms(n, generator, u, dev)
+        dead, src, c, total = self._draws(u, n)
+        if total == 0:                                              # nothing to draw from: plain copies (include/gsr_mcmc.h)
+            src, srcs, new = torch.arange(n, device=dev) % P, torch.zeros(0, dtype=torch.int64, device=dev), {}
+        else:
+            srcs = (c > 0).nonzero().reshape(-1)
+            new = dict(zip(("opacity", "scaling"), self._correction(srcs, c[srcs])))
+
+        def param_fn(name, p):
+            p = p.clone()
+            if name in new:
+                p[srcs] = new[name]
+            return torch.cat((p, p[src]), dim=0)
+
+        def moment_fn(name, m):
+            m = m.clone()
+            m[srcs] = 0
+            return torch.cat((m, torch.zeros((n,) + tuple(m.shape[1:]), dtype=m.dtype, device=m.device)), dim=0)
+        self._remap(param_fn, moment_fn)
+        self._resize_statistics(P_new, dev)
+        self._last["grow"] = {"n_dead": int(dead.sum()), "n_draws": n if total else 0, "n_sources": int(srcs.shape[0]), "P_new": P_new}
+        return P_new
+
+    def _resize_statistics(self, P: int, dev) -> None:
+        m = self.model
+        m.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
+        m.denom = torch.zeros((P, 1), device=dev)
+        m.max_radii2D = torch.zeros((P,), device=dev)
+
+    # ---- every iteration ----
+    def add_noise(self, generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None) -> None:
+        """xyz += (R S S R^T noise) * gate(opacity) * noise_lr * (current xyz learning rate), in place."""
+        mc = self.mcmc
+        xyz = self._param("xyz")
+        P, dev = xyz.shape[0], xyz.device
+        if noise is None:
+            noise = torch.randn((P, 3), generator=generator, device=dev, dtype=torch.float32)
+        if P == 0:
+            return
+        with torch.no_grad():
+            o = torch.sigmoid(self._param("opacity").detach())
+            f = 1.0 / (1.0 + torch.exp(mc.gate_k * (o - mc.gate_t)))
+            RS = quaternion_to_rotation(self._param("rotation").detach()) * torch.exp(self._param("scaling").detach())[:, None, :]
+            cov = torch.bmm(RS, RS.transpose(1, 2))
+            xyz.add_(torch.bmm(cov, noise.to(dev)[:, :, None]).squeeze(-1) * f * float(np.float32(mc.noise_lr * self._xyz_lr_now())))
+
+    def regularize(self):
+        """Adds the gradients of opacity_reg * mean sigmoid(opacity) + scale_reg * mean exp(scaling) into the parameters' .grad;
+        returns the two terms (0-d tensors on the parameters' device)."""
+        mc = self.mcmc
+        op, sc = self._param("opacity"), self._param("scaling")
+        P = op.shape[0]
+        with torch.no_grad():
+            for p in (op, sc):
+                if p.grad is None:
+                    p.grad = torch.zeros_like(p)
+            if P == 0:
+                z = torch.zeros((), dtype=torch.float64, device=op.device)
+                return z, z.clone()
+            s, e = torch.sigmoid(op.detach()), torch.exp(sc.detach())
+            op.grad.add_(float(np.float32(mc.opacity_reg / P)) * (s * (1.0 - s)))
+            sc.grad.add_(float(np.float32(mc.scale_reg / (3.0 * P))) * e)
+            return mc.opacity_reg * s.double().mean(), mc.scale_reg * e.double().mean()
+
+    # ---- the schedule ----
+    def after_backward(self, iteration: int, *args, **kwargs):
+        """Call after loss.backward() and before optimizer.step(): the regularisers' gradients.  Returns the two terms."""
+        return self.regularize()
+
+    def after_step(self, iteration: int, generator: Optional[torch.Generator] = None) -> None:
+        """Call after optimizer.step(): noise every iteration; relocation then growth every refine_every iterations inside
+        [refine_start, refine_stop)."""
+        mc = self.mcmc
+        self.add_noise(generator=generator)
+        if mc.refine_start <= iteration < mc.refine_stop and iteration % mc.refine_every == 0:
+            self.relocate(generator=generator)
+            self.grow(generator=generator)
+
+
+_MCMC_ROLE = {"opacity": _lib.MCMC_OPACITY, "scaling": _lib.MCMC_SCALING}     # every other group is a plain copy
+
+
+class FusedMCMCController(MCMCController):
+    """MCMCController on the HIP path (include/gsr_mcmc.h, csrc/mcmc.hip).  relocate, add_noise and regularize enqueue their kernels
+    and return: no host wait.  grow allocates the new rows -- their number is known on the host -- and installs them as _remap
+    does, also without a wait.  counts() is the one method that synchronises.  Same results as MCMCController: indices, counts
+    and copied rows bit for bit, the corrected opacity and scaling to one float32 ulp.  No CPU fallback."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._ws = None
+        self._reg_ws = None
+        self._pinned = {}              # which -> pinned host words {n_dead, n_draws, n_sources, P_new}
+        self._issued = {}              # which -> device the last plan ran on
+
+    @staticmethod
+    def _device_f32(name: str, t) -> torch.Tensor:
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise _lib.GsrError(f"FusedMCMCController: {name} must be on a HIP device (no CPU fallback)")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.GsrError(f"FusedMCMCController: {name} must be contiguous float32, got {t.dtype}")
+        return t
+
+    def counts(self, which: str = "relocate") -> Dict[str, int]:
+        """Waits for the device, then {"n_dead", "n_draws", "n_sources", "P_new"} of the last relocate() or grow()."""
+        if which in self._last:        # decided on the host (nothing to do): no plan ran
+            return dict(self._last[which])
+        torch.cuda.current_stream(self._issued[which]).synchronize()
+        return dict(zip(("n_dead", "n_draws", "n_sources", "P_new"), (int(v) for v in self._pinned[which].tolist())))
+
+    def _groups(self, olds, news=None, new_states=None):
+        """The group table of gsr_mcmc_apply: in place (news None) or into the tensors of news / new_states."""
+        ptr, descs = _lib.ptr, []
+        for g in self.optimizer.param_groups:
+            n, old = g["name"], olds[g["name"]]
+            state = self.optimizer.state.get(g["params"][0], None)
+            has = state is not None and "exp_avg" in state
+            width = old[0].numel() if old.shape[0] else 0
+            if not width:
+                continue
+            sm = (self._device_f32(n + " exp_avg", state["exp_avg"]), self._device_f32(n + " exp_avg_sq", state["exp_avg_sq"])) if has else (None, None)
+            dst, dm = (old, sm) if news is None else (news[n], new_states[n] if has else (None, None))
+            descs.append(_lib.McmcGroup(ptr(old), ptr(sm[0]), ptr(sm[1]), ptr(dst), ptr(dm[0]), ptr(dm[1]), width, _MCMC_ROLE.get(n, _lib.MCMC_COPY)))
+        return (_lib.McmcGroup * len(descs))(*descs), len(descs)
+
+    def _plan(self, which: str, mode: int, olds, P: int, n: int, u: torch.Tensor, dev):
+        need = _lib.workspace_bytes("gsr_mcmc_plan_workspace", P, n)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)            # kept across calls: not _lib.workspace()
+        if which not in self._pinned:
+            self._pinned[which] = torch.zeros(4, dtype=torch.int32).pin_memory()
+        ptr = _lib.ptr
+        _lib.call("gsr_mcmc_plan", _lib.stream(dev), mode, P, ptr(olds["opacity"]), ptr(olds["scaling"]), self.dead_logit, float(self.mcmc.min_opacity),
+                  int(self.mcmc.n_max), n, ptr(u), ptr(self._pinned[which]), ptr(self._ws), self._ws.numel())
+        self._last.pop(which, None)
+        self._issued[which] = dev
+
+    def _olds(self):
+        olds = {g["name"]: g["params"][0].detach() for g in self.optimizer.param_groups}
+        for n in GROUPS:
+            self._device_f32(n, olds[n])
+        return olds
+
+    def relocate(self, generator: Optional[torch.Generator] = None, u: Optional[torch.Tensor] = None) -> None:
+        olds = self._olds()
+        P, dev = olds["xyz"].shape[0], olds["xyz"].device
+        u = self._device_f32("u", self._uniforms(P, generator, u, dev))
+        if P == 0:
+            self._last["relocate"] = {"n_dead": 0, "n_draws": 0, "n_sources": 0, "P_new": 0}
+            return
+        with torch.cuda.device(dev):
+            self._plan("relocate", _lib.MCMC_RELOCATE, olds, P, 0, u, dev)
+            arr, k = self._groups(olds)
+            _lib.call("gsr_mcmc_apply", _lib.stream(dev), _lib.MCMC_RELOCATE, P, 0, k, arr, _lib.ptr(self._ws), self._ws.numel())
+
+    def grow(self, generator: Optional[torch.Generator] = None, u: Optional[torch.Tensor] = None) -> int:
+        olds = self._olds()
+        P, dev = olds["xyz"].shape[0], olds["xyz"].device
+        P_new = self.grown_size(P)
+        n = P_new - P
+        if n == 0:
+            self._last["grow"] = {"n_dead": 0, "n_draws": 0, "n_sources": 0, "P_new": P}
+            return P
+        u = self._device_f32("u", self._uniforms(n, generator, u, dev))
+        new, states = {}, {}
+        for g in self.optimizer.param_groups:
+            name, old = g["name"], g["params"][0]
+            state = self.optimizer.state.get(old, None)
+            shape = (P_new,) + tuple(old.shape[1:])
+            new[name] = torch.empty(shape, device=dev)
+            states[name] = (torch.empty(shape, device=dev), torch.empty(shape, device=dev)) if state is not None and "exp_avg" in state else None
+        with torch.cuda.device(dev):
+            self._plan("grow", _lib.MCMC_GROW, olds, P, n, u, dev)
+            arr, k = self._groups(olds, new, states)
+            _lib.call("gsr_mcmc_apply", _lib.stream(dev), _lib.MCMC_GROW, P, n, k, arr, _lib.ptr(self._ws), self._ws.numel())
+        for g in self.optimizer.param_groups:                       # install, as _remap does
+            name, old = g["name"], g["params"][0]
+            state = self.optimizer.state.pop(old, None)
+            p = torch.nn.Parameter(new[name].requires_grad_(True))
+            if state is not None:
+                if states[name] is not None:
+                    state["exp_avg"], state["exp_avg_sq"] = states[name]
+                self.optimizer.state[p] = state
+            g["params"][0] = p
+            setattr(self.model, _ATTR[name], p)
+        self._resize_statistics(P_new, dev)
+        return P_new
+
+    def add_noise(self, generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None) -> None:
+        olds = self._olds()
+        P, dev = olds["xyz"].shape[0], olds["xyz"].device
+        if noise is None:
+            noise = torch.randn((P, 3), generator=generator, device=dev, dtype=torch.float32)
+        noise = self._device_f32("noise", noise)
+        if tuple(noise.shape) != (P, 3):
+            raise _lib.GsrError(f"FusedMCMCController.add_noise: noise must be [{P}, 3], got {tuple(noise.shape)}")
+        if P == 0:
+            return
+        ptr, mc = _lib.ptr, self.mcmc
+        with torch.cuda.device(dev):
+            _lib.call("gsr_mcmc_noise", _lib.stream(dev), P, ptr(olds["opacity"]), ptr(olds["scaling"]), ptr(olds["rotation"]), ptr(noise),
+                      ptr(olds["xyz"]), float(mc.gate_k), float(mc.gate_t), float(np.float32(mc.noise_lr * self._xyz_lr_now())))
+
+    def regularize(self):
+        """As MCMCController.regularize, one entry point.  The .grad tensors are taken as they come: float32, unit column stride,
+        any row stride (views into a gradient arena)."""
+        mc = self.mcmc
+        op, sc = self._param("opacity"), self._param("scaling")
+        self._device_f32("opacity", op.detach()); self._device_f32("scaling", sc.detach())
+        P, dev = op.shape[0], op.device
+        for p in (op, sc):
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        means = torch.zeros(2, dtype=torch.float64, device=dev)
+        if P == 0:
+            return means[0], means[1]
+        strides = []
+        for name, p, width in (("opacity", op, 1), ("scaling", sc, 3)):
+            g = p.grad
+            if g.device != dev or g.dtype != torch.float32 or tuple(g.shape) != tuple(p.shape) or (width > 1 and g.stride(1) != 1) or \
+                    (P > 1 and g.stride(0) < width):
+                raise _lib.GsrError(f"FusedMCMCController.regularize: {name}.grad must be float32 [{P}, {width}] on the parameters' device with "
+                                    f"unit column stride, got {g.dtype} {tuple(g.shape)} strides {g.stride()}")
+            strides.append(max(int(g.stride(0)), width))
+        with torch.cuda.device(dev):
+            need = _lib.workspace_bytes("gsr_mcmc_regularize_workspace", P)
+            if self._reg_ws is None or self._reg_ws.numel() < need or self._reg_ws.device != dev:
+                self._reg_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            # .data_ptr(), not ptr(): the strided tensors that cross the boundary, handed over with their row strides
+            _lib.call("gsr_mcmc_regularize", _lib.stream(dev), P, _lib.ptr(op.detach()), _lib.ptr(sc.detach()), op.grad.data_ptr(), strides[0],
+                      sc.grad.data_ptr(), strides[1], float(mc.opacity_reg), float(mc.scale_reg), _lib.ptr(means), _lib.ptr(self._reg_ws),
+                      self._reg_ws.numel())
+        return mc.opacity_reg * means[0], mc.scale_reg * means[1]

@@ -4,7 +4,10 @@
 -> Adam step.  Target images come from a hidden "ground truth" set of Gaussians seen from a ring of cameras; the trained
 set starts from a perturbed, thinned copy.  Informational (bench.py is the headline metric).
 
-    python scripts/train_synthetic.py [--iters 600] [--P 20000] [--size 256] [--density torch|hip] [--adam hip|hip_sparse]
+    python scripts/train_synthetic.py [--iters 600] [--P 20000] [--size 256] [--density torch|hip|mcmc|mcmc_hip] [--cap N] [--adam hip|hip_sparse]
+
+--density mcmc / mcmc_hip: MCMC density control (densify.MCMCController / FusedMCMCController, include/gsr_mcmc.h) with a budget of
+--cap Gaussians: regularisers before the step, position noise after it, relocation and growth every `densify_every` iterations.
 """
 import argparse, json, math, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,13 +16,17 @@ import numpy as np
 import torch
 from gaussian_transformer_amd import synth
 from gaussian_transformer_amd.camera import look_at_camera
-from gaussian_transformer_amd.densify import DensityController, FusedDensityController, OptimizationParams
+from gaussian_transformer_amd.densify import (DensityController, FusedDensityController, FusedMCMCController, MCMCController, MCMCParams,
+                                              OptimizationParams)
 from gaussian_transformer_amd.loss import fused_l1_ssim_loss, psnr
 from gaussian_transformer_amd.model import GaussianParams
 from gaussian_transformer_amd.render import PipelineParams, TorchCamera, render_fused
 
 
-def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_every=100, log=None, density="torch", adam="hip"):
+DEFAULT_CAP = 26619      # the count a --density hip run at the defaults ends at (profiles/density/bench.json): the same final set size
+
+
+def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_every=100, log=None, density="torch", adam="hip", cap=None):
     dev = torch.device("cuda", 0)
     sc = synth.make_scene(P=P, width=size, height=size, sh_degree=1, s0=0.03, seed=seed, zmin=3.0, zmax=6.0)
     truth = GaussianParams.from_synthetic(sc, dev, requires_grad=False)
@@ -41,7 +48,12 @@ def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_
     model = GaussianParams.from_synthetic(sc0, dev)
     opt = OptimizationParams(densify_from_iter=densify_from, densification_interval=densify_every, opacity_reset_interval=10 ** 9,
                              densify_until_iter=iters)
-    ctl = (FusedDensityController if density == "hip" else DensityController)(model, opt, spatial_lr_scale=1.0, adam=adam)
+    mcmc = density in ("mcmc", "mcmc_hip")
+    if mcmc:
+        params = MCMCParams(cap_max=cap if cap is not None else DEFAULT_CAP, refine_start=densify_from, refine_every=densify_every, refine_stop=iters)
+        ctl = (FusedMCMCController if density == "mcmc_hip" else MCMCController)(model, params, opt, spatial_lr_scale=1.0, adam=adam)
+    else:
+        ctl = (FusedDensityController if density == "hip" else DensityController)(model, opt, spatial_lr_scale=1.0, adam=adam)
     gen = torch.Generator(device=dev).manual_seed(seed)
 
     def evaluate():
@@ -60,11 +72,16 @@ def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_
         loss.backward()
         with torch.no_grad():
             ev = ctl.after_backward(it, pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"], extent=3.0, generator=gen)
+            if mcmc:
+                ev = None                  # the two regularisation terms (device tensors): not an event, and reading them would wait
             if adam == "hip_sparse":       # rows of Gaussians outside this view stand still (include/gsr_optim.h); a no-op right after a densification
                 ctl.optimizer.step(visibility=pkg["radii"])
             else:
                 ctl.optimizer.step()
             ctl.optimizer.zero_grad(set_to_none=True)
+            if mcmc:
+                ctl.after_step(it, generator=gen)
+                ev = {"P": int(model._xyz.shape[0])} if densify_from <= it < iters and it % densify_every == 0 else None      # relocated and grown
         if it % 50 == 0 or ev:
             rec = {"it": it, "loss": round(float(loss.detach()), 5), "P": int(model._xyz.shape[0]), "event": ev}
             hist.append(rec)
@@ -83,11 +100,13 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=600)
     ap.add_argument("--P", type=int, default=20000)
     ap.add_argument("--size", type=int, default=256)
-    ap.add_argument("--density", choices=("torch", "hip"), default="torch",
-                    help="density control: torch index arithmetic (DensityController) or the HIP path (FusedDensityController)")
+    ap.add_argument("--density", choices=("torch", "hip", "mcmc", "mcmc_hip"), default="torch",
+                    help="density control: torch index arithmetic (DensityController), the HIP path (FusedDensityController), or MCMC "
+                         "density control in torch (MCMCController) / on the HIP path (FusedMCMCController)")
+    ap.add_argument("--cap", type=int, default=None, help="mcmc / mcmc_hip: the budget of Gaussians (default: what --density hip ends at)")
     ap.add_argument("--adam", choices=("hip", "hip_sparse"), default="hip",
                     help="hip = HipAdam over all rows; hip_sparse = HipSparseAdam with the view's radii as visibility")
     a = ap.parse_args()
-    out = run(a.iters, a.P, a.size, density=a.density, adam=a.adam, log=lambda r: print(json.dumps(r), flush=True))
+    out = run(a.iters, a.P, a.size, density=a.density, adam=a.adam, cap=a.cap, log=lambda r: print(json.dumps(r), flush=True))
     out.pop("history")
     print(json.dumps(out))
