@@ -23,17 +23,18 @@
 // its launcher already takes), and depth_finish_kernel adds the dL/dv term to dL/dmeans3D -- and, with accumulate, the whole result
 // to the caller's buffers.
 // Shared with the colour passes, one copy each in composite_common.h: the staged conic pair, the replica-row rule and the LDS + DPP
-// reduction (here with 7 sums, there with 9); the signed wave-wide max is gsr_device.h's.  Kept here: the half tile's geometry (its y is
-// formed once for both blocks) and the record gather behind the range check on the id -- through the shared helpers these two kernels
-// come out with another instruction order (scripts/isa_diff.py).  The recurrences differ from bwd_unit's on purpose, see above.
+// reduction (here with 7 sums, there with 9); the signed wave-wide max is gsr_device.h's.  Not its geometry and gather helpers: through
+// them these two kernels come out with another instruction order (scripts/isa_diff.py).  The recurrences differ from bwd_unit's on
+// purpose, see above.
+// Shared with feature_maps.hip, one copy each in map_walk.h: the leading argument fields, the half tile's geometry, the record gather
+// behind the range check on the id, the add of the staged result, and on the host the views, the sizes refusal, the workspace carve and
+// the reverse call's common refusals, R == 0 clearing and per-Gaussian launch.  The walk loops are this file's own (map_walk.h says why).
 // Zeroing: only the rows that can be added into (marked Gaussians + replica rows) are cleared, by composite_bwd.hip's
 // launch_zero_marked_rows: 64 B per marked row and a byte read per Gaussian instead of a 66 P byte memset.
 #include <string.h>
 
 #include "../../include/gsr_depth.h"
-#include "composite_common.h"
-#include "gsr_host.h"
-#include "gsr_internal.h"
+#include "map_walk.h"
 #include "pergauss_chain.h"
 
 namespace gsr {
@@ -42,78 +43,21 @@ namespace {
 #define DEPTH_NSUM 7                                    // s dx, s dy, s dx dx, s dx dy, s dy dy, s, dL/dv -> row slots 3..9
 #define DEPTH_BWD_LDS_F4 (64 * 2 + (DEPTH_NSUM * RED_STRIDE + 3) / 4)
 
-struct DepthArgs {
-    int W, H, gridx, gridy, P, mode;
-    size_t list_len;             // R: entries of point_list, stride of contrib
-    size_t acc_rows;             // rows of acc (reverse pass)
-    const uint8_t *contrib;      // [4][list_len]
-    const uint2 *ranges;
-    const uint32_t *point_list;
-    const float *rec;
-    const float *final_T;
-    const uint32_t *n_contrib;
+struct DepthArgs : WalkArgs {                        // mode: GSR_DEPTH_*
     float *out_depth, *out_alpha;           // forward (either may be NULL)
     const float *gD, *gA;                   // reverse (either may be NULL)
     float *acc;
 };
 
-// what a wave knows of its half tile before it walks: pixel coordinates, each pixel's last contributor (0 outside the image), the
-// largest one per block and overall (clamped to the list: a garbage n_contrib cannot send the walk past the tile's range)
-struct HalfTile {
-    float fx[2], fy;
-    bool inside[2];
-    size_t pix[2];
-    int last[2], blk_last[2], hi;
-    uint2 range;
-};
-__device__ __forceinline__ HalfTile half_tile(const DepthArgs &a, const int tile, const int sub, const int lane) {
-    HalfTile h;
-    const int tx = tile % a.gridx, ty = tile / a.gridx;
-    h.range = a.ranges[tile];
-    const int y = ty * GSR_TILE + sub * 8 + (lane >> 3);
-    h.fy = (float)y;
-    int hi = 0;
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        const int x = tx * GSR_TILE + q * 8 + (lane & 7);
-        h.inside[q] = x < a.W && y < a.H;
-        h.pix[q] = (size_t)(h.inside[q] ? y : 0) * a.W + (h.inside[q] ? x : 0);
-        h.fx[q] = (float)x;
-        h.last[q] = h.inside[q] ? (int)a.n_contrib[h.pix[q]] : 0;
-        int m = h.last[q];
-        GSR_WAVE_MAX_I32(m);
-        h.blk_last[q] = __builtin_amdgcn_readfirstlane(m);
-        hi = max(hi, h.blk_last[q]);
-    }
-    const long long n = (long long)h.range.y - (long long)h.range.x;
-    h.hi = (int)min((long long)hi, max(n, 0ll));
-    return h;
-}
-
 // stages entry base + lane of the tile's list: (px, py, a, b) (c, opacity, v, bits | row << 4); returns whether the entry reaches a block
 __device__ __forceinline__ bool stage_entry(const DepthArgs &a, const HalfTile &h, float4 *my, const int tile, const int sub, const int base,
                                             const int cnt, const int lane, const bool want_row) {
-    if (lane >= cnt) return false;
-    const size_t at = (size_t)h.range.x + base + lane;
-    if (at >= a.list_len) return false;
-    const uint32_t g = a.point_list[at];
-    if (g >= (uint32_t)a.P) return false;
-    const float4 *rec4 = reinterpret_cast<const float4 *>(a.rec) + 3 * (size_t)g;
-    const float4 r0 = rec4[0], r1 = rec4[1], r2 = rec4[2];
-    uint32_t bits = 0u;
-#pragma unroll
-    for (int q = 0; q < 2; q++) bits |= a.contrib[(size_t)(sub * 2 + q) * a.list_len + at] ? (1u << q) : 0u;
-    uint32_t row = g;
-    if (want_row) {
-        row = replica_row(__float_as_uint(r2.w), g, a.P, tile);
-        if ((size_t)row >= a.acc_rows) return false;
-    }
-    float4 s0, s1;
-    stage_record(r0, r1, s0, s1);                                // as the colour pass stages it
-    const float v = a.mode == GSR_DEPTH_INVERSE ? 1.0f / r2.y : r2.y;
-    my[lane] = s0;
-    my[64 + lane] = make_float4(s1.x, s1.y, v, __uint_as_float(bits | (row << 4)));      // row < 2^28 (checked by the entry point)
-    return bits != 0u;
+    Entry e;
+    if (!gather_entry(a, h, tile, sub, base, cnt, lane, want_row, e)) return false;
+    const float v = a.mode == GSR_DEPTH_INVERSE ? 1.0f / e.r2.y : e.r2.y;
+    my[lane] = e.s0;
+    my[64 + lane] = make_float4(e.s1.x, e.s1.y, v, entry_code(e));
+    return e.bits != 0u;
 }
 
 __global__ __launch_bounds__(256) void depth_fwd_kernel(DepthArgs a) {
@@ -245,9 +189,7 @@ struct FinishArgs {
     const uint8_t *touched, *clamped;
     const uint32_t *touch_mark, *hot;
     const float *acc;
-    // accumulate: the per-Gaussian chain's result (staged in the workspace) is added to the caller's buffers
-    const float *t_means2D, *t_opacity, *t_means3D, *t_cov3D, *t_scales, *t_rots;
-    float *dL_dmeans2D, *dL_dopacity, *dL_dmeans3D, *dL_dcov3D, *dL_dscales, *dL_drots;
+    StagedAdd add;               // out: the caller's buffers; accumulate: the per-Gaussian chain's result (t, staged in the workspace) is added to them
 };
 
 // One lane per Gaussian: dL/dmeans3D += dL/dv dv/dz (m[2], m[6], m[10]); with accumulate, out += staged result.  A Gaussian whose mark
@@ -265,56 +207,21 @@ __global__ __launch_bounds__(256) void depth_finish_kernel(FinishArgs f) {
     const float g = f.mode == GSR_DEPTH_INVERSE ? -dv / (zv * zv) : dv;
     const float e0 = g * m[2], e1 = g * m[6], e2 = g * m[10];
     if (!f.accumulate) {
-        f.dL_dmeans3D[3 * si] += e0; f.dL_dmeans3D[3 * si + 1] += e1; f.dL_dmeans3D[3 * si + 2] += e2;
+        float *const o = f.add.out.means3D;
+        o[3 * si] += e0; o[3 * si + 1] += e1; o[3 * si + 2] += e2;
         return;
     }
-    f.dL_dmeans3D[3 * si] += f.t_means3D[3 * si] + e0; f.dL_dmeans3D[3 * si + 1] += f.t_means3D[3 * si + 1] + e1;
-    f.dL_dmeans3D[3 * si + 2] += f.t_means3D[3 * si + 2] + e2;
-    f.dL_dmeans2D[3 * si] += f.t_means2D[3 * si]; f.dL_dmeans2D[3 * si + 1] += f.t_means2D[3 * si + 1];
-    f.dL_dopacity[si] += f.t_opacity[si];
-    if (f.dL_dcov3D) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) f.dL_dcov3D[6 * si + k] += f.t_cov3D[6 * si + k];
-    }
-    if (f.dL_dscales) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) f.dL_dscales[3 * si + k] += f.t_scales[3 * si + k];
-#pragma unroll
-        for (int k = 0; k < 4; k++) f.dL_drots[4 * si + k] += f.t_rots[4 * si + k];
-    }
+    const float e[3] = {e0, e1, e2};
+    add_staged(f.add, si, e);
 }
 
 // ---- host side ----
-// gsr_depth_backward's workspace: the accumulator rows where gsr_backward's has them, then the staging area `accumulate` sends the
-// per-Gaussian stage's results through, one piece of 20 floats per Gaussian: rots 4 | means2D 3 | means3D 3 | opacity 1 | scales 3 | cov3D 6
-struct DepthWs { float *acc, *t_rots, *t_m2, *t_m3, *t_op, *t_sc, *t_cov; size_t total_bytes; };
-DepthWs carve_depth_ws(void *ws, int P) {
-    const BackwardView rows = carve_backward(ws, P, 0);
-    const size_t n = (size_t)(P > 0 ? P : 0);
-    Bump w = {(char *)ws, rows.vis_off};
-    float *const st = w.take<float>(20 * n);
-    return {rows.acc, st, st + 4 * n, st + 7 * n, st + 10 * n, st + 11 * n, st + 14 * n, w.off};
-}
-
 int32_t sizes_and_mode(const char *who, int P, int W, int H, long long R, int mode) {
-    if (P < 0 || W <= 0 || H <= 0 || R < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
-    if (W > 65535 * GSR_TILE_HOST || H > 65535 * GSR_TILE_HOST || (long long)grid_dim(W) * grid_dim(H) > (1ll << 28)) return fail(GSR_ERR_INVALID_ARGUMENT, "image too large");
+    GSR_TRY(map_sizes(who, P, W, H, R));
     if (mode != GSR_DEPTH_EXPECTED && mode != GSR_DEPTH_INVERSE)
         return fail(GSR_ERR_INVALID_ARGUMENT, "%s: mode %d is neither 0 (expected depth) nor 1 (inverse depth)", who, mode);
     return GSR_OK;
 }
-
-// the three workspaces of the gsr_forward before this call (gsr_internal.h: view_geom, view_image, view_lists, refused in this order)
-struct Views { GeomView g; ImageView im; BinningView b; };
-DepthArgs walk_args(const Views &v, int P, int W, int H, long long R, int mode) {
-    DepthArgs a;
-    memset(&a, 0, sizeof a);
-    a.W = W; a.H = H; a.gridx = grid_dim(W); a.gridy = grid_dim(H); a.P = P; a.mode = mode; a.list_len = (size_t)R;
-    a.contrib = v.b.contrib; a.ranges = v.im.ranges; a.point_list = v.b.point_list; a.rec = v.g.rec;
-    a.final_T = v.im.final_T; a.n_contrib = v.im.n_contrib;
-    return a;
-}
-inline unsigned walk_blocks(const DepthArgs &a) { return (unsigned)((2ll * a.gridx * a.gridy + 3) / 4); }
 
 }  // namespace
 }  // namespace gsr
@@ -325,7 +232,7 @@ extern "C" {
 
 int32_t gsr_depth_workspace_bytes(int32_t P, size_t *bytes) {
     if (P < 0 || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_depth_workspace_bytes: bad argument");
-    *bytes = carve_depth_ws(nullptr, P).total_bytes;
+    *bytes = carve_map_ws(nullptr, P, 0).total_bytes;
     return GSR_OK;
 }
 
@@ -343,11 +250,9 @@ int32_t gsr_depth_forward(gsr_stream_t stream, int32_t P, int32_t W, int32_t H, 
     }
     if (!geom_ws || !binning_ws || !img_ws) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_depth_forward: missing workspace");
     Views v;
-    GSR_TRY(view_geom(geom_ws, geom_bytes, P, &v.g));
-    GSR_TRY(view_image(img_ws, img_bytes, W, H, &v.im));
-    GSR_TRY(view_lists(binning_ws, binning_bytes, R, &v.b));
-    DepthArgs a = walk_args(v, P, W, H, (long long)R, mode);
-    a.out_depth = out_depth; a.out_alpha = out_alpha;
+    GSR_TRY(view_all(v, P, W, H, (long long)R, {geom_ws, geom_bytes, binning_ws, binning_bytes, img_ws, img_bytes}));
+    DepthArgs a = walk_args<DepthArgs>(v, P, W, H, (long long)R);
+    a.mode = mode; a.out_depth = out_depth; a.out_alpha = out_alpha;
     hipLaunchKernelGGL(depth_fwd_kernel, dim3(walk_blocks(a)), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError(), "depth forward launch");
     return GSR_OK;
@@ -365,62 +270,31 @@ int32_t gsr_depth_backward(gsr_stream_t stream, int32_t P, int32_t W, int32_t H,
     GSR_TRY(sizes_and_mode(who, P, W, H, (long long)R, mode));
     if (!dL_ddepth && !dL_dalpha) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_ddepth and dL_dalpha are both NULL", who);
     if (P == 0) return GSR_OK;
-    if (!means3D || !radii || !viewmatrix || !projmatrix || !geom_ws || !img_ws || !ws || !dL_dmeans2D || !dL_dopacity || !dL_dmeans3D)
-        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: missing input, workspace or gradient buffer", who);
-    if (((scales != nullptr) && (rotations != nullptr)) == (cov3D_precomp != nullptr) || ((scales != nullptr) != (rotations != nullptr)))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: exactly one of (scales, rotations) / cov3D_precomp must be given", who);
-    if ((cov3D_precomp && !dL_dcov3D) || (scales && (!dL_dscales || !dL_drots)))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_dcov3D required with cov3D_precomp, dL_dscales and dL_drots with scales and rotations", who);
-    if (R > 0 && !binning_ws) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: binning workspace missing", who);
-    int32_t det = 0;
-    GSR_TRY(gsr_get_option("deterministic_bwd", &det));
-    if (det) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: not available while the option deterministic_bwd is on (this pass sums with float atomics and has no slot form)", who);
-    const DepthWs dw = carve_depth_ws(ws, P);
-    if (ws_bytes < dw.total_bytes) return fail(GSR_ERR_WORKSPACE, "depth workspace %zu < %zu", ws_bytes, dw.total_bytes);
-    if (acc_rows(P) >= (1u << 28)) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: P too large for the 28-bit accumulator row index", who);
-    float *const d_scales = scales ? dL_dscales : nullptr, *const d_rots = scales ? dL_drots : nullptr;      // the form that was not given is not written
-    if (R == 0) {                                       // nothing was composited: every gradient is zero
-        if (accumulate) return GSR_OK;
-        const size_t n = (size_t)P * sizeof(float);
-        HIP_TRY(hipMemsetAsync(dL_dmeans2D, 0, 3 * n, s), "clear gradients");
-        HIP_TRY(hipMemsetAsync(dL_dopacity, 0, n, s), "clear gradients");
-        HIP_TRY(hipMemsetAsync(dL_dmeans3D, 0, 3 * n, s), "clear gradients");
-        if (dL_dcov3D) HIP_TRY(hipMemsetAsync(dL_dcov3D, 0, 6 * n, s), "clear gradients");
-        if (d_scales) { HIP_TRY(hipMemsetAsync(d_scales, 0, 3 * n, s), "clear gradients"); HIP_TRY(hipMemsetAsync(d_rots, 0, 4 * n, s), "clear gradients"); }
-        return GSR_OK;
-    }
+    ReverseCall c = {who, P, W, H, (long long)R, means3D, radii, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                     tanfovx, tanfovy, {geom_ws, geom_bytes, binning_ws, binning_bytes, img_ws, img_bytes}, ws, ws_bytes, accumulate,
+                     {dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dscales, dL_drots}};
+    MapWs dw;
+    GSR_TRY(reverse_prologue(c, true, "depth", 0, &dw));
+    if (R == 0) return clear_gradients(c, nullptr, 0, s);
     Views v;
-    GSR_TRY(view_geom(geom_ws, geom_bytes, P, &v.g));
-    GSR_TRY(view_image(img_ws, img_bytes, W, H, &v.im));
-    GSR_TRY(view_lists(binning_ws, binning_bytes, R, &v.b));
+    GSR_TRY(view_all(v, P, W, H, c.R, c.fws));
 
     // 1. clear the rows that can be added into; 2. the reverse walk
     HIP_TRY(launch_zero_marked_rows(P, v.g.touched, v.g.touch_mark, dw.acc, acc_rows(P), v.im.seg, 0, 0, s), "zero depth accumulators");
-    DepthArgs a = walk_args(v, P, W, H, (long long)R, mode);
-    a.gD = dL_ddepth; a.gA = dL_dalpha; a.acc = dw.acc; a.acc_rows = acc_rows(P);
+    DepthArgs a = walk_args<DepthArgs>(v, P, W, H, c.R);
+    a.mode = mode; a.gD = dL_ddepth; a.gA = dL_dalpha; a.acc = dw.acc; a.acc_rows = acc_rows(P);
     hipLaunchKernelGGL(depth_bwd_kernel, dim3(walk_blocks(a)), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError(), "depth backward launch");
 
-    // 3. the per-Gaussian chain S11-S13 on these rows: pergauss_bwd.hip's streaming kernel, no colour input, into the caller's buffers or
-    //    -- with accumulate -- into the staging area behind the rows
-    PergaussBwdArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.P = P; pa.W = W; pa.H = H; pa.rec = v.g.rec; pa.means3D = means3D; pa.scales = scales; pa.rotations = rotations; pa.cov3D_precomp = cov3D_precomp;
-    pa.opac = v.g.opac; pa.viewmatrix = viewmatrix; pa.projmatrix = projmatrix; pa.campos = campos;
-    pa.scale_modifier = scale_modifier; pa.tanfovx = tanfovx; pa.tanfovy = tanfovy; pa.radii = radii; pa.clamped = v.g.clamped;
-    pa.acc = dw.acc; pa.hot = v.g.hot; pa.touched = v.g.touched; pa.touch_mark = v.g.touch_mark;
-    pa.dL_dmeans2D = accumulate ? dw.t_m2 : dL_dmeans2D; pa.dL_dopacity = accumulate ? dw.t_op : dL_dopacity; pa.dL_dmeans3D = accumulate ? dw.t_m3 : dL_dmeans3D;
-    pa.dL_dcov3D = dL_dcov3D ? (accumulate ? dw.t_cov : dL_dcov3D) : nullptr;
-    pa.dL_dscales = d_scales ? (accumulate ? dw.t_sc : d_scales) : nullptr; pa.dL_drots = d_rots ? (accumulate ? dw.t_rots : d_rots) : nullptr;
-    HIP_TRY(launch_pergauss_bwd(pa, s), "per-Gaussian backward launch");
+    // 3. the per-Gaussian chain on these rows
+    GSR_TRY(launch_chain(c, v, dw, s));
 
     // 4. dL/dv -> dL/dmeans3D, and the accumulation
     FinishArgs f;
     memset(&f, 0, sizeof f);
     f.P = P; f.mode = mode; f.accumulate = accumulate ? 1 : 0; f.means3D = means3D; f.viewmatrix = viewmatrix; f.radii = radii;
     f.touched = v.g.touched; f.clamped = v.g.clamped; f.touch_mark = v.g.touch_mark; f.hot = v.g.hot; f.acc = dw.acc;
-    f.t_means2D = dw.t_m2; f.t_opacity = dw.t_op; f.t_means3D = dw.t_m3; f.t_cov3D = dw.t_cov; f.t_scales = dw.t_sc; f.t_rots = dw.t_rots;
-    f.dL_dmeans2D = dL_dmeans2D; f.dL_dopacity = dL_dopacity; f.dL_dmeans3D = dL_dmeans3D; f.dL_dcov3D = dL_dcov3D; f.dL_dscales = d_scales; f.dL_drots = d_rots;
+    f.add = {dw.staged, c.out};
     hipLaunchKernelGGL(depth_finish_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, f);
     HIP_TRY(hipGetLastError(), "depth finish launch");
     return GSR_OK;

@@ -21,14 +21,14 @@
 //              contiguous floats of the entry's row in a [rows][C] buffer of the workspace, replica rows included).
 // pergauss_bwd.hip's streaming kernel then runs unchanged on the accumulator rows; features_df_kernel folds the replica rows and
 // writes dL/dF [P,C] in full, features_add_kernel adds the staged per-Gaussian result with accumulate.
-// Kept here as copies of depth_maps.hip's lines and not shared with it: the half tile's geometry and the record gather -- that file's
-// two kernels come out in another instruction order through shared helpers (its header; scripts/isa_diff.py), and they stay as they are.
+// Shared with depth_maps.hip, one copy each in map_walk.h: the leading argument fields, the half tile's geometry, the record gather
+// behind the range check on the id, the add of the staged result, and on the host the views, the sizes refusal, the workspace carve and
+// the reverse call's common refusals, R == 0 clearing and per-Gaussian launch.  The walk loops are this file's own (map_walk.h says
+// why).  With the colour passes it shares what depth_maps.hip shares with them (composite_common.h), and no more.
 #include <string.h>
 
 #include "../../include/gsr_features.h"
-#include "composite_common.h"
-#include "gsr_host.h"
-#include "gsr_internal.h"
+#include "map_walk.h"
 #include "pergauss_chain.h"
 
 namespace gsr {
@@ -36,16 +36,7 @@ namespace {
 
 #define FEAT_NMOM 6                                     // s dx, s dy, s dx dx, s dx dy, s dy dy, s -> row slots 3..8
 
-struct FeatArgs {
-    int W, H, gridx, gridy, P, C;
-    size_t list_len;             // R: entries of point_list, stride of contrib
-    size_t acc_rows;             // rows of acc and of dfacc (reverse pass)
-    const uint8_t *contrib;      // [4][list_len]
-    const uint2 *ranges;
-    const uint32_t *point_list;
-    const float *rec;
-    const float *final_T;
-    const uint32_t *n_contrib;
+struct FeatArgs : WalkArgs {     // C: channels; acc_rows: rows of acc and of dfacc
     const float *features;       // [P][C]
     float *out;                  // forward: [C][H][W]
     const float *G;              // reverse: dL_dout [C][H][W]
@@ -53,70 +44,23 @@ struct FeatArgs {
     float *dfacc;                // [acc_rows][C]
 };
 
-// what a wave knows of its half tile before it walks (depth_maps.hip's HalfTile)
-struct HalfTile {
-    float fx[2], fy;
-    bool inside[2];
-    size_t pix[2];
-    int last[2], blk_last[2], hi;
-    uint2 range;
-};
-__device__ __forceinline__ HalfTile half_tile(const FeatArgs &a, const int tile, const int sub, const int lane) {
-    HalfTile h;
-    const int tx = tile % a.gridx, ty = tile / a.gridx;
-    h.range = a.ranges[tile];
-    const int y = ty * GSR_TILE + sub * 8 + (lane >> 3);
-    h.fy = (float)y;
-    int hi = 0;
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        const int x = tx * GSR_TILE + q * 8 + (lane & 7);
-        h.inside[q] = x < a.W && y < a.H;
-        h.pix[q] = (size_t)(h.inside[q] ? y : 0) * a.W + (h.inside[q] ? x : 0);
-        h.fx[q] = (float)x;
-        h.last[q] = h.inside[q] ? (int)a.n_contrib[h.pix[q]] : 0;
-        int m = h.last[q];
-        GSR_WAVE_MAX_I32(m);
-        h.blk_last[q] = __builtin_amdgcn_readfirstlane(m);
-        hi = max(hi, h.blk_last[q]);
-    }
-    const long long n = (long long)h.range.y - (long long)h.range.x;
-    h.hi = (int)min((long long)hi, max(n, 0ll));      // a garbage n_contrib cannot send the walk past the tile's range
-    return h;
-}
-
 // stages entry base + lane of the tile's list: (px, py, a, b) (c, opacity, -, bits | row << 4) and its CH features from channel c0 on
 // (zeros from channel C on); returns whether the entry reaches a block
 template <int CH>
 __device__ __forceinline__ bool stage_entry(const FeatArgs &a, const HalfTile &h, float4 *my, float4 *ft, const int tile, const int sub,
                                             const int base, const int cnt, const int lane, const int c0, const bool want_row) {
-    if (lane >= cnt) return false;
-    const size_t at = (size_t)h.range.x + base + lane;
-    if (at >= a.list_len) return false;
-    const uint32_t g = a.point_list[at];
-    if (g >= (uint32_t)a.P) return false;
-    const float4 *rec4 = reinterpret_cast<const float4 *>(a.rec) + 3 * (size_t)g;
-    const float4 r0 = rec4[0], r1 = rec4[1], r2 = rec4[2];
-    uint32_t bits = 0u;
-#pragma unroll
-    for (int q = 0; q < 2; q++) bits |= a.contrib[(size_t)(sub * 2 + q) * a.list_len + at] ? (1u << q) : 0u;
-    uint32_t row = g;
-    if (want_row) {
-        row = replica_row(__float_as_uint(r2.w), g, a.P, tile);
-        if ((size_t)row >= a.acc_rows) return false;
-    }
-    float4 s0, s1;
-    stage_record(r0, r1, s0, s1);                                // as the colour pass stages it
-    my[lane] = s0;
-    my[64 + lane] = make_float4(s1.x, s1.y, 0.f, __uint_as_float(bits | (row << 4)));      // row < 2^28 (checked by the entry point)
-    const float *fr = a.features + (size_t)g * a.C;
+    Entry e;
+    if (!gather_entry(a, h, tile, sub, base, cnt, lane, want_row, e)) return false;
+    my[lane] = e.s0;
+    my[64 + lane] = make_float4(e.s1.x, e.s1.y, 0.f, entry_code(e));
+    const float *fr = a.features + (size_t)e.g * a.C;
 #pragma unroll
     for (int k = 0; k < CH / 4; k++) {
         const int c = c0 + 4 * k;
         ft[64 * k + lane] = make_float4(c < a.C ? fr[c] : 0.f, c + 1 < a.C ? fr[c + 1] : 0.f, c + 2 < a.C ? fr[c + 2] : 0.f,
                                         c + 3 < a.C ? fr[c + 3] : 0.f);
     }
-    return bits != 0u;
+    return e.bits != 0u;
 }
 
 template <int CH>
@@ -317,8 +261,7 @@ struct AddArgs {
     const int *radii;
     const uint8_t *touched;
     const uint32_t *touch_mark;
-    const float *t_means2D, *t_opacity, *t_means3D, *t_cov3D, *t_scales, *t_rots;
-    float *dL_dmeans2D, *dL_dopacity, *dL_dmeans3D, *dL_dcov3D, *dL_dscales, *dL_drots;
+    StagedAdd add;
 };
 
 // accumulate: out += the per-Gaussian chain's result staged in the workspace, one lane per Gaussian.  A Gaussian whose mark differs
@@ -328,65 +271,21 @@ __global__ __launch_bounds__(256) void features_add_kernel(AddArgs f) {
     if (i >= f.P) return;
     const size_t si = (size_t)i;
     if (!(f.radii[si] > 0 && (uint32_t)f.touched[si] == *f.touch_mark)) return;
-#pragma unroll
-    for (int k = 0; k < 3; k++) f.dL_dmeans3D[3 * si + k] += f.t_means3D[3 * si + k];
-    f.dL_dmeans2D[3 * si] += f.t_means2D[3 * si]; f.dL_dmeans2D[3 * si + 1] += f.t_means2D[3 * si + 1];
-    f.dL_dopacity[si] += f.t_opacity[si];
-    if (f.dL_dcov3D) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) f.dL_dcov3D[6 * si + k] += f.t_cov3D[6 * si + k];
-    }
-    if (f.dL_dscales) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) f.dL_dscales[3 * si + k] += f.t_scales[3 * si + k];
-#pragma unroll
-        for (int k = 0; k < 4; k++) f.dL_drots[4 * si + k] += f.t_rots[4 * si + k];
-    }
+    add_staged(f.add, si, nullptr);
 }
 
 // ---- host side ----
-// gsr_features_backward's workspace: gsr_depth_backward's (the accumulator rows where gsr_backward's has them, then the staging area
-// `accumulate` sends the per-Gaussian stage's results through: rots 4 | means2D 3 | means3D 3 | opacity 1 | scales 3 | cov3D 6 floats
-// per Gaussian), then the dL/dF rows: acc_rows(P) x C floats
-struct FeatWs { float *acc, *t_rots, *t_m2, *t_m3, *t_op, *t_sc, *t_cov, *dfacc; size_t total_bytes; };
-FeatWs carve_features_ws(void *ws, int P, int C) {
-    const BackwardView rows = carve_backward(ws, P, 0);
-    const size_t n = (size_t)(P > 0 ? P : 0);
-    Bump w = {(char *)ws, rows.vis_off};
-    float *const st = w.take<float>(20 * n);
-    float *const df = w.take<float>(acc_rows(P) * (size_t)C);
-    return {rows.acc, st, st + 4 * n, st + 7 * n, st + 10 * n, st + 11 * n, st + 14 * n, df, w.off};
-}
-
 int32_t sizes_and_channels(const char *who, int P, int C, int W, int H, long long R) {
-    if (P < 0 || W <= 0 || H <= 0 || R < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
-    if (W > 65535 * GSR_TILE_HOST || H > 65535 * GSR_TILE_HOST || (long long)grid_dim(W) * grid_dim(H) > (1ll << 28)) return fail(GSR_ERR_INVALID_ARGUMENT, "image too large");
+    GSR_TRY(map_sizes(who, P, W, H, R));
     if (C < 1 || C > GSR_FEATURES_MAX_C) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: C = %d channels, must be 1 .. %d", who, C, GSR_FEATURES_MAX_C);
     return GSR_OK;
 }
 
-// the three workspaces of the gsr_forward before this call (gsr_internal.h: view_geom, view_image, view_lists, refused in this order)
-struct Views { GeomView g; ImageView im; BinningView b; };
-int32_t view_all(Views &v, int P, int W, int H, long long R, const void *geom_ws, size_t geom_bytes, const void *binning_ws, size_t binning_bytes,
-                 const void *img_ws, size_t img_bytes) {
-    GSR_TRY(view_geom(geom_ws, geom_bytes, P, &v.g));
-    GSR_TRY(view_image(img_ws, img_bytes, W, H, &v.im));
-    GSR_TRY(view_lists(binning_ws, binning_bytes, R, &v.b));
-    return GSR_OK;
-}
-FeatArgs walk_args(const Views &v, int P, int C, int W, int H, long long R, const float *features) {
-    FeatArgs a;
-    memset(&a, 0, sizeof a);
-    a.W = W; a.H = H; a.gridx = grid_dim(W); a.gridy = grid_dim(H); a.P = P; a.C = C; a.list_len = (size_t)R;
-    a.contrib = v.b.contrib; a.ranges = v.im.ranges; a.point_list = v.b.point_list; a.rec = v.g.rec;
-    a.final_T = v.im.final_T; a.n_contrib = v.im.n_contrib; a.features = features;
-    return a;
-}
 // the chunk a call's C is cut into, and the grid: x = half tiles / 4 (a wave each), y = chunks
 inline int chunk_of(int C) { return C <= 4 ? 4 : (C <= 8 ? 8 : 16); }
 inline dim3 walk_grid(const FeatArgs &a) {
     const int ch = chunk_of(a.C);
-    return dim3((unsigned)((2ll * a.gridx * a.gridy + 3) / 4), (unsigned)((a.C + ch - 1) / ch));
+    return dim3(walk_blocks(a), (unsigned)((a.C + ch - 1) / ch));
 }
 
 }  // namespace
@@ -398,7 +297,7 @@ extern "C" {
 
 int32_t gsr_features_workspace_bytes(int32_t P, int32_t C, size_t *bytes) {
     if (P < 0 || C < 1 || C > GSR_FEATURES_MAX_C || !bytes) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_features_workspace_bytes: bad argument");
-    *bytes = carve_features_ws(nullptr, P, C).total_bytes;
+    *bytes = carve_map_ws(nullptr, P, C).total_bytes;
     return GSR_OK;
 }
 
@@ -415,9 +314,9 @@ int32_t gsr_features_forward(gsr_stream_t stream, int32_t P, int32_t C, int32_t 
     }
     if (!features || !geom_ws || !binning_ws || !img_ws) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: missing features or workspace", who);
     Views v;
-    GSR_TRY(view_all(v, P, W, H, (long long)R, geom_ws, geom_bytes, binning_ws, binning_bytes, img_ws, img_bytes));
-    FeatArgs a = walk_args(v, P, C, W, H, (long long)R, features);
-    a.out = out;
+    GSR_TRY(view_all(v, P, W, H, (long long)R, {geom_ws, geom_bytes, binning_ws, binning_bytes, img_ws, img_bytes}));
+    FeatArgs a = walk_args<FeatArgs>(v, P, W, H, (long long)R);
+    a.C = C; a.features = features; a.out = out;
     switch (chunk_of(C)) {
         case 4: hipLaunchKernelGGL(features_fwd_kernel<4>, walk_grid(a), dim3(256), 0, s, a); break;
         case 8: hipLaunchKernelGGL(features_fwd_kernel<8>, walk_grid(a), dim3(256), 0, s, a); break;
@@ -440,33 +339,14 @@ int32_t gsr_features_backward(gsr_stream_t stream, int32_t P, int32_t C, int32_t
     GSR_TRY(sizes_and_channels(who, P, C, W, H, (long long)R));
     if (!dL_dout) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_dout is NULL", who);
     if (P == 0) return GSR_OK;
-    if (!means3D || !radii || !viewmatrix || !projmatrix || !features || !geom_ws || !img_ws || !ws || !dL_dmeans2D || !dL_dopacity || !dL_dmeans3D)
-        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: missing input, workspace or gradient buffer", who);
-    if (((scales != nullptr) && (rotations != nullptr)) == (cov3D_precomp != nullptr) || ((scales != nullptr) != (rotations != nullptr)))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: exactly one of (scales, rotations) / cov3D_precomp must be given", who);
-    if ((cov3D_precomp && !dL_dcov3D) || (scales && (!dL_dscales || !dL_drots)))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_dcov3D required with cov3D_precomp, dL_dscales and dL_drots with scales and rotations", who);
-    if (R > 0 && !binning_ws) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: binning workspace missing", who);
-    int32_t det = 0;
-    GSR_TRY(gsr_get_option("deterministic_bwd", &det));
-    if (det) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: not available while the option deterministic_bwd is on (this pass sums with float atomics and has no slot form)", who);
-    const FeatWs fw = carve_features_ws(ws, P, C);
-    if (ws_bytes < fw.total_bytes) return fail(GSR_ERR_WORKSPACE, "features workspace %zu < %zu", ws_bytes, fw.total_bytes);
-    if (acc_rows(P) >= (1u << 28)) return fail(GSR_ERR_INVALID_ARGUMENT, "%s: P too large for the 28-bit accumulator row index", who);
-    float *const d_scales = scales ? dL_dscales : nullptr, *const d_rots = scales ? dL_drots : nullptr;      // the form that was not given is not written
-    if (R == 0) {                                       // nothing was composited: every gradient is zero
-        const size_t n = (size_t)P * sizeof(float);
-        if (dL_dfeatures) HIP_TRY(hipMemsetAsync(dL_dfeatures, 0, (size_t)C * n, s), "clear gradients");
-        if (accumulate) return GSR_OK;
-        HIP_TRY(hipMemsetAsync(dL_dmeans2D, 0, 3 * n, s), "clear gradients");
-        HIP_TRY(hipMemsetAsync(dL_dopacity, 0, n, s), "clear gradients");
-        HIP_TRY(hipMemsetAsync(dL_dmeans3D, 0, 3 * n, s), "clear gradients");
-        if (dL_dcov3D) HIP_TRY(hipMemsetAsync(dL_dcov3D, 0, 6 * n, s), "clear gradients");
-        if (d_scales) { HIP_TRY(hipMemsetAsync(d_scales, 0, 3 * n, s), "clear gradients"); HIP_TRY(hipMemsetAsync(d_rots, 0, 4 * n, s), "clear gradients"); }
-        return GSR_OK;
-    }
+    ReverseCall c = {who, P, W, H, (long long)R, means3D, radii, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                     tanfovx, tanfovy, {geom_ws, geom_bytes, binning_ws, binning_bytes, img_ws, img_bytes}, ws, ws_bytes, accumulate,
+                     {dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dscales, dL_drots}};
+    MapWs fw;
+    GSR_TRY(reverse_prologue(c, features != nullptr, "features", C, &fw));
+    if (R == 0) return clear_gradients(c, dL_dfeatures, C, s);
     Views v;
-    GSR_TRY(view_all(v, P, W, H, (long long)R, geom_ws, geom_bytes, binning_ws, binning_bytes, img_ws, img_bytes));
+    GSR_TRY(view_all(v, P, W, H, c.R, c.fws));
 
     // 1. clear the rows that can be added into; 2. the reverse walk, one wave per (half tile, chunk)
     const size_t rows = acc_rows(P), cells = rows * (size_t)C;
@@ -475,8 +355,8 @@ int32_t gsr_features_backward(gsr_stream_t stream, int32_t P, int32_t C, int32_t
         hipLaunchKernelGGL(features_zero_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, P, C, v.g.touched, v.g.touch_mark, fw.dfacc, rows);
         HIP_TRY(hipGetLastError(), "zero dL/dF rows");
     }
-    FeatArgs a = walk_args(v, P, C, W, H, (long long)R, features);
-    a.G = dL_dout; a.acc = fw.acc; a.dfacc = fw.dfacc; a.acc_rows = rows;
+    FeatArgs a = walk_args<FeatArgs>(v, P, W, H, c.R);
+    a.C = C; a.features = features; a.G = dL_dout; a.acc = fw.acc; a.dfacc = fw.dfacc; a.acc_rows = rows;
 #define LAUNCH_BWD(CH) \
     if (dL_dfeatures) hipLaunchKernelGGL((features_bwd_kernel<CH, true>), walk_grid(a), dim3(256), 0, s, a); \
     else hipLaunchKernelGGL((features_bwd_kernel<CH, false>), walk_grid(a), dim3(256), 0, s, a)
@@ -488,18 +368,8 @@ int32_t gsr_features_backward(gsr_stream_t stream, int32_t P, int32_t C, int32_t
 #undef LAUNCH_BWD
     HIP_TRY(hipGetLastError(), "features backward launch");
 
-    // 3. the per-Gaussian chain S11-S13 on these rows: pergauss_bwd.hip's streaming kernel, no colour input, into the caller's buffers or
-    //    -- with accumulate -- into the staging area behind the rows
-    PergaussBwdArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.P = P; pa.W = W; pa.H = H; pa.rec = v.g.rec; pa.means3D = means3D; pa.scales = scales; pa.rotations = rotations; pa.cov3D_precomp = cov3D_precomp;
-    pa.opac = v.g.opac; pa.viewmatrix = viewmatrix; pa.projmatrix = projmatrix; pa.campos = campos;
-    pa.scale_modifier = scale_modifier; pa.tanfovx = tanfovx; pa.tanfovy = tanfovy; pa.radii = radii; pa.clamped = v.g.clamped;
-    pa.acc = fw.acc; pa.hot = v.g.hot; pa.touched = v.g.touched; pa.touch_mark = v.g.touch_mark;
-    pa.dL_dmeans2D = accumulate ? fw.t_m2 : dL_dmeans2D; pa.dL_dopacity = accumulate ? fw.t_op : dL_dopacity; pa.dL_dmeans3D = accumulate ? fw.t_m3 : dL_dmeans3D;
-    pa.dL_dcov3D = dL_dcov3D ? (accumulate ? fw.t_cov : dL_dcov3D) : nullptr;
-    pa.dL_dscales = d_scales ? (accumulate ? fw.t_sc : d_scales) : nullptr; pa.dL_drots = d_rots ? (accumulate ? fw.t_rots : d_rots) : nullptr;
-    HIP_TRY(launch_pergauss_bwd(pa, s), "per-Gaussian backward launch");
+    // 3. the per-Gaussian chain on these rows
+    GSR_TRY(launch_chain(c, v, fw, s));
 
     // 4. dL/dF: replica rows folded, [P,C] written in full; 5. the accumulation
     if (dL_dfeatures) {
@@ -511,9 +381,7 @@ int32_t gsr_features_backward(gsr_stream_t stream, int32_t P, int32_t C, int32_t
     if (accumulate) {
         AddArgs f;
         memset(&f, 0, sizeof f);
-        f.P = P; f.radii = radii; f.touched = v.g.touched; f.touch_mark = v.g.touch_mark;
-        f.t_means2D = fw.t_m2; f.t_opacity = fw.t_op; f.t_means3D = fw.t_m3; f.t_cov3D = fw.t_cov; f.t_scales = fw.t_sc; f.t_rots = fw.t_rots;
-        f.dL_dmeans2D = dL_dmeans2D; f.dL_dopacity = dL_dopacity; f.dL_dmeans3D = dL_dmeans3D; f.dL_dcov3D = dL_dcov3D; f.dL_dscales = d_scales; f.dL_drots = d_rots;
+        f.P = P; f.radii = radii; f.touched = v.g.touched; f.touch_mark = v.g.touch_mark; f.add = {fw.staged, c.out};
         hipLaunchKernelGGL(features_add_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, f);
         HIP_TRY(hipGetLastError(), "features accumulate launch");
     }
