@@ -193,6 +193,22 @@ POSE_SIGNATURES = {
                                  _p, _p, _p]),                                           # dL_d{viewmatrix projmatrix campos}
 }
 
+# include/gsr_contrib.h (likewise a table of its own)
+CONTRIB_ROW_BYTES = 16
+CONTRIB_MAX_PIXELS = 2 ** 32 - 1       # pixels a row's count can hold (the header's capacity)
+
+
+class ContribRow(C.Structure):         # gsr_contrib_row_t of include/gsr_contrib.h
+    _fields_ = [("sum_q32", C.c_uint64), ("max_bits", C.c_uint32), ("count", C.c_uint32)]
+
+
+CONTRIB_SIGNATURES = {
+    "gsr_contrib_accumulate": (_i32, [_p, _i32, _i32, _i32, C.c_int64,                   # stream P W H R
+                                      _p, _sz, _p, _sz, _p, _sz,                         # geom binning img (+bytes)
+                                      _p]),                                              # rows
+    "gsr_contrib_read": (_i32, [_p, _i32, _p, _p, _p, _p]),                              # stream P rows weight_sum weight_max pixel_count
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -220,7 +236,7 @@ def load() -> C.CDLL:
         except OSError as e:
             raise GsrError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES, **SEQUENCE_SIGNATURES, **ROWS_SIGNATURES, **DENSITY_SIGNATURES,
-                                   **MCMC_SIGNATURES, **DEPTH_SIGNATURES, **FEATURES_SIGNATURES, **POSE_SIGNATURES}.items():
+                                   **MCMC_SIGNATURES, **DEPTH_SIGNATURES, **FEATURES_SIGNATURES, **POSE_SIGNATURES, **CONTRIB_SIGNATURES}.items():
             fn = getattr(lib, name)       # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

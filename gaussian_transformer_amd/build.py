@@ -57,6 +57,9 @@ SOURCES = {
     # as pergauss_bwd.hip, whose chain (csrc/pergauss_chain.h) it calls up to the terms the camera gradient shares with dL/dmeans3D
     # (include/gsr_pose.h)
     "pose_grad.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    # as depth_maps.hip, whose forward walk it restates with an integer reduction per entry (include/gsr_contrib.h): FMA contraction as
+    # there, so the weights are depth_fwd_kernel's bits; its atomics are integer ones, so no float-atomic flag
+    "contrib_stats.hip": ["-fno-slp-vectorize"],
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result", "-fno-gpu-rdc"]
 

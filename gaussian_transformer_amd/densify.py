@@ -144,6 +144,40 @@ class DensityController:
         m.denom = m.denom[keep]
         m.max_radii2D = m.max_radii2D[keep]
 
+    # ---- pruning by measured contribution (rasterizer.ContributionStats: blend weights collected over many views) ----
+    def _contribution(self, stats):
+        w_sum, w_max, n_pix = stats.read()
+        P = self.model._xyz.shape[0]
+        if w_sum.shape[0] != P:
+            raise ValueError(f"the contribution statistics hold {w_sum.shape[0]} Gaussians, the model {P}")
+        dev = self.model._xyz.device
+        return w_sum.to(dev), w_max.to(dev), n_pix.to(dev)
+
+    def prune_by_max_weight(self, stats, threshold: float = 0.01) -> int:
+        """Removes the Gaussians whose largest blend weight alpha T over every collected view is below `threshold` (RadSplat's "max
+        ray contribution"), those never blended in any of the views among them.  Returns how many were removed."""
+        _, w_max, n_pix = self._contribution(stats)
+        mask = (w_max < threshold) | (n_pix == 0)
+        self.prune_points(mask)
+        return int(mask.sum())
+
+    def prune_by_weight_sum(self, stats, fraction: float, volume_power: float = 0.0) -> int:
+        """Removes the round(fraction P) Gaussians with the lowest score weight_sum * (product of the activated scales)^volume_power
+        (LightGaussian's global significance; volume_power = 0: the summed blend weight alone).  Equal scores go by index, the
+        lower index first.  Returns how many were removed."""
+        if not 0.0 <= fraction <= 1.0:
+            raise ValueError(f"fraction must lie in [0, 1], got {fraction}")
+        w_sum, _, _ = self._contribution(stats)
+        score = w_sum.to(torch.float64)
+        if volume_power != 0.0:
+            score = score * self.model.get_scaling.detach().to(torch.float64).prod(dim=1).pow(volume_power)
+        P = score.shape[0]
+        k = int(round(fraction * P))
+        mask = torch.zeros((P,), dtype=torch.bool, device=score.device)
+        mask[torch.sort(score, stable=True).indices[:k]] = True
+        self.prune_points(mask)
+        return k
+
     def append_points(self, new: Dict[str, torch.Tensor]) -> None:
         """Appends Gaussians with zero Adam moments and resets the densification statistics (:303-347)."""
         self._remap(lambda n, p: torch.cat((p, new[n]), dim=0), lambda n, m: torch.cat((m, torch.zeros_like(new[n])), dim=0))

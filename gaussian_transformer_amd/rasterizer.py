@@ -224,6 +224,8 @@ class HipBackend:
                 if len(self._bin_hint) > 64:
                     self._bin_hint.pop(next(iter(self._bin_hint)))
             binning = holder[0] if holder else torch.empty((0,), **u8)
+            if _contrib_stats is not None:     # collect_contribution: this view's blend weights, from the workspaces just filled
+                _contrib_stats._add_view(dev, stream, P, W, H, int(n.value), geom, binning, img)
         return int(n.value), color, radii, geom, binning, img
 
     def backward(self, rs, num_rendered, dL_dpix, means3D, radii, shs, colors_precomp, scales, rotations,
@@ -447,6 +449,71 @@ class gradient_arena:
 
 def arena_floats(P: int, M: int, has_scale_rot: bool = True) -> int:
     return P * (3 + 3 * M + 1 + (7 if has_scale_rot else 0))
+
+
+_contrib_stats = None   # the ContributionStats every forward pass adds its view to (collect_contribution), or None
+
+
+class ContributionStats:
+    """Per-Gaussian blend-weight statistics over many renders (include/gsr_contrib.h): for each of P Gaussians the sum of its blend
+    weights alpha T over every pixel it was blended into, the largest of them, and the number of those pixels.  `rows` is the native
+    accumulator, uint8 [P,16] on `device` (sum_q32 uint64 | max_bits uint32 | count uint32), all zero = nothing collected; `views`
+    and `pixels_added` count what was added.  The sums are integers: they do not depend on the order of the views."""
+
+    def __init__(self, P: int, device):
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.P, self.device = int(P), dev
+        self.rows = torch.zeros((self.P, _lib.CONTRIB_ROW_BYTES), dtype=torch.uint8, device=dev)
+        self.views = 0
+        self.pixels_added = 0
+
+    def reset(self) -> None:
+        self.rows.zero_()
+        self.views = 0
+        self.pixels_added = 0
+
+    def _add_view(self, dev, stream, P, W, H, num_rendered, geom, binning, img) -> None:
+        if P != self.P or dev != self.device:
+            raise _lib.GsrError(f"collect_contribution: the collector holds {self.P} Gaussians on {self.device}, "
+                                f"the render has {P} on {dev}")
+        if self.pixels_added + W * H > _lib.CONTRIB_MAX_PIXELS:
+            raise _lib.GsrError(f"collect_contribution: {self.pixels_added} pixels collected, {W * H} more would pass the "
+                                f"{_lib.CONTRIB_MAX_PIXELS} a row's count can hold (include/gsr_contrib.h): read and reset the collector")
+        _lib.call("gsr_contrib_accumulate", stream, P, W, H, num_rendered, ptr(geom), geom.numel(), ptr(binning), binning.numel(),
+                  ptr(img), img.numel(), ptr(self.rows))
+        self.views += 1
+        self.pixels_added += W * H
+
+    def read(self):
+        """(weight_sum float32 [P], weight_max float32 [P], pixel_count int32 [P]) of what has been collected so far."""
+        w_sum = torch.empty((self.P,), dtype=torch.float32, device=self.device)
+        w_max = torch.empty((self.P,), dtype=torch.float32, device=self.device)
+        n_pix = torch.empty((self.P,), dtype=torch.int32, device=self.device)
+        if self.P:
+            with torch.cuda.device(self.device):
+                _lib.call("gsr_contrib_read", _lib.stream(self.device), self.P, ptr(self.rows), ptr(w_sum), ptr(w_max), ptr(n_pix))
+        return w_sum, w_max, n_pix
+
+
+class collect_contribution:
+    """Context manager: while active, every forward pass of the native backend -- render, render_fused, render_rows, with or without an
+    autograd graph -- ends with one gsr_contrib_accumulate of its view into `stats`.  A render of another P or on another device
+    raises GsrError, as does a view that would take `stats.pixels_added` past 2^32 - 1.  Outside it nothing new runs."""
+
+    def __init__(self, stats: ContributionStats):
+        self.stats = stats
+
+    def __enter__(self):
+        global _contrib_stats
+        self.prev, _contrib_stats = _contrib_stats, self.stats
+        return self.stats
+
+    def __exit__(self, *exc):
+        global _contrib_stats
+        _contrib_stats = self.prev
+        return False
 
 
 def get_backend():

@@ -5,9 +5,13 @@
 set starts from a perturbed, thinned copy.  Informational (bench.py is the headline metric).
 
     python scripts/train_synthetic.py [--iters 600] [--P 20000] [--size 256] [--density torch|hip|mcmc|mcmc_hip] [--cap N] [--adam hip|hip_sparse]
+                                      [--prune-contribution ITER:THRESHOLD]
 
 --density mcmc / mcmc_hip: MCMC density control (densify.MCMCController / FusedMCMCController, include/gsr_mcmc.h) with a budget of
 --cap Gaussians: regularisers before the step, position noise after it, relocation and growth every `densify_every` iterations.
+--prune-contribution ITER:THRESHOLD: after iteration ITER the blend weights of every training camera are collected under no_grad
+(rasterizer.collect_contribution, include/gsr_contrib.h) and the Gaussians whose largest weight stays below THRESHOLD are pruned
+(DensityController.prune_by_max_weight); the record holds the Gaussians and the PSNR before and after.
 """
 import argparse, json, math, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,13 +24,15 @@ from gaussian_transformer_amd.densify import (DensityController, FusedDensityCon
                                               OptimizationParams)
 from gaussian_transformer_amd.loss import fused_l1_ssim_loss, psnr
 from gaussian_transformer_amd.model import GaussianParams
+from gaussian_transformer_amd.rasterizer import ContributionStats, collect_contribution
 from gaussian_transformer_amd.render import PipelineParams, TorchCamera, render_fused
 
 
 DEFAULT_CAP = 26619      # the count a --density hip run at the defaults ends at (profiles/density/bench.json): the same final set size
 
 
-def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_every=100, log=None, density="torch", adam="hip", cap=None):
+def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_every=100, log=None, density="torch", adam="hip", cap=None,
+        prune_contribution=None):
     dev = torch.device("cuda", 0)
     sc = synth.make_scene(P=P, width=size, height=size, sh_degree=1, s0=0.03, seed=seed, zmin=3.0, zmax=6.0)
     truth = GaussianParams.from_synthetic(sc, dev, requires_grad=False)
@@ -63,6 +69,7 @@ def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_
                     float(np.mean([float(psnr(i[None], t[None]).mean()) for i, t in zip(imgs, targets)])))
     loss0, psnr0 = evaluate()
     hist = []
+    pruned = None
     t0 = time.perf_counter()
     for it in range(1, iters + 1):
         ctl.update_learning_rate(it)
@@ -82,6 +89,17 @@ def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_
             if mcmc:
                 ctl.after_step(it, generator=gen)
                 ev = {"P": int(model._xyz.shape[0])} if densify_from <= it < iters and it % densify_every == 0 else None      # relocated and grown
+        if prune_contribution is not None and it == prune_contribution[0]:
+            _, psnr_before = evaluate()
+            stats = ContributionStats(int(model._xyz.shape[0]), dev)
+            with torch.no_grad(), collect_contribution(stats):
+                for c in cams:
+                    render_fused(c, model, pipe, bg)
+                n = ctl.prune_by_max_weight(stats, threshold=prune_contribution[1])
+            pruned = {"it": it, "threshold": prune_contribution[1], "views": stats.views, "P_before": stats.P, "P_after": int(model._xyz.shape[0]),
+                      "pruned": n, "psnr_before": round(psnr_before, 2), "psnr_after": round(evaluate()[1], 2)}
+            if log:
+                log(pruned)
         if it % 50 == 0 or ev:
             rec = {"it": it, "loss": round(float(loss.detach()), 5), "P": int(model._xyz.shape[0]), "event": ev}
             hist.append(rec)
@@ -92,7 +110,7 @@ def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_
     loss1, psnr1 = evaluate()
     return {"density": density, "adam": adam, "iters": iters, "seconds": round(dt, 2), "it_per_s": round(iters / dt, 1), "P_start": len(keep), "P_end": int(model._xyz.shape[0]),
             "loss_first": round(loss0, 5), "loss_last": round(loss1, 5), "psnr_first": round(psnr0, 2), "psnr": round(psnr1, 2),
-            "history": hist}
+            "prune_contribution": pruned, "history": hist}
 
 
 if __name__ == "__main__":
@@ -106,7 +124,13 @@ if __name__ == "__main__":
     ap.add_argument("--cap", type=int, default=None, help="mcmc / mcmc_hip: the budget of Gaussians (default: what --density hip ends at)")
     ap.add_argument("--adam", choices=("hip", "hip_sparse"), default="hip",
                     help="hip = HipAdam over all rows; hip_sparse = HipSparseAdam with the view's radii as visibility")
+    ap.add_argument("--prune-contribution", default=None, metavar="ITER:THRESHOLD",
+                    help="after iteration ITER, prune the Gaussians whose largest blend weight over all training cameras is below THRESHOLD")
     a = ap.parse_args()
-    out = run(a.iters, a.P, a.size, density=a.density, adam=a.adam, cap=a.cap, log=lambda r: print(json.dumps(r), flush=True))
+    prune = None
+    if a.prune_contribution:
+        at, thr = a.prune_contribution.split(":")
+        prune = (int(at), float(thr))
+    out = run(a.iters, a.P, a.size, density=a.density, adam=a.adam, cap=a.cap, prune_contribution=prune, log=lambda r: print(json.dumps(r), flush=True))
     out.pop("history")
     print(json.dumps(out))
