@@ -111,10 +111,13 @@ DENSITY_MAX_GROUPS = 16
 DENSITY_COPY, DENSITY_XYZ, DENSITY_SCALING = 0, 1, 2
 
 
+_GROUP_FIELDS = [("src", C.c_void_p), ("src_exp_avg", C.c_void_p), ("src_exp_avg_sq", C.c_void_p),      # one layout, two public types
+                 ("dst", C.c_void_p), ("dst_exp_avg", C.c_void_p), ("dst_exp_avg_sq", C.c_void_p),
+                 ("width_floats", C.c_int32), ("role", C.c_int32)]
+
+
 class DensityGroup(C.Structure):       # gsr_density_group_t of include/gsr_density.h
-    _fields_ = [("src", C.c_void_p), ("src_exp_avg", C.c_void_p), ("src_exp_avg_sq", C.c_void_p),
-                ("dst", C.c_void_p), ("dst_exp_avg", C.c_void_p), ("dst_exp_avg_sq", C.c_void_p),
-                ("width_floats", C.c_int32), ("role", C.c_int32)]
+    _fields_ = _GROUP_FIELDS
 
 
 DENSITY_SIGNATURES = {
@@ -133,9 +136,7 @@ MCMC_COPY, MCMC_OPACITY, MCMC_SCALING = 0, 1, 2
 
 
 class McmcGroup(C.Structure):          # gsr_mcmc_group_t of include/gsr_mcmc.h
-    _fields_ = [("src", C.c_void_p), ("src_exp_avg", C.c_void_p), ("src_exp_avg_sq", C.c_void_p),
-                ("dst", C.c_void_p), ("dst_exp_avg", C.c_void_p), ("dst_exp_avg_sq", C.c_void_p),
-                ("width_floats", C.c_int32), ("role", C.c_int32)]
+    _fields_ = _GROUP_FIELDS
 
 
 MCMC_SIGNATURES = {

@@ -4,6 +4,8 @@
 //            the four ranks (and the clone total) in one value -> map kernel (the source of every row of the new state, the counts).
 //   apply  : ONE launch over (destination row, column) of every group: consecutive lanes write consecutive floats of the new
 //            parameter and both new moments; 16-byte accesses where the width is a multiple of 4 and every pointer is aligned.
+//            The group table, its filler, the quaternion's rotation and the common group refusals are group_table.h's, shared
+//            with mcmc.hip; the kernel, which reads the map and the ranks, is this file's.
 // Compiled with -ffp-contract=off -fno-slp-vectorize like the other per-Gaussian units: the norm of record and the plan's
 // decisions round as written.  No float atomics anywhere: bit-identical from run to run.
 #include <cstring>  // ROCm 7.2 rocprim/texture_cache_iterator.hpp uses memset without including it
@@ -11,8 +13,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/gsr_density.h"
-#include "gsr_host.h"
-#include "gsr_internal.h"
+#include "group_table.h"
 
 namespace gsr {
 
@@ -167,16 +168,8 @@ static hipError_t launch_densify_plan(int P, const float *opacity, const float *
 
 // ---------------------------------------------------------------- apply ----------------------------------------------------------------
 
-struct ApplyGroupDev {
-    const float *src, *sm, *sv;
-    float *dst, *dm, *dv;
-    uint32_t w;
-    int role;
-    unsigned first_block;        // the group's blocks are [first_block, next group's first_block)
-    int vec4;
-};
 struct ApplyArgs {
-    ApplyGroupDev grp[GSR_DENSITY_MAX_GROUPS];
+    GroupDev grp[GSR_DENSITY_MAX_GROUPS];
     int n_groups, P, N;
     uint32_t p_new, n_split;
     double child_div;            // 0.8 * N
@@ -185,33 +178,26 @@ struct ApplyArgs {
     const Rank5 *ranks;
 };
 
-#define APPLY_PER_BLOCK 1024       // floats of one group per block: 4 rounds of 256 lanes, or 256 lanes x 16 bytes
-
 // The values of the split children are evaluated in float64 and rounded once: each is the float32 nearest to the formula's exact
 // value, so no float32 evaluation of the same formula (torch's, on either device) lies nearer to it.  Three values per child, beside
 // 3 x 59 floats copied per row: the double-rate arithmetic does not show in the kernel's time.
 // coordinate c of the child of Gaussian i drawn with noise row n: R(q / |q|) . (noise * exp(scaling)) + xyz
 __device__ __forceinline__ float child_xyz(const ApplyArgs &a, const float *__restrict__ xyz, uint32_t i, uint32_t n, uint32_t c) {
-    const double qr = a.rotation[4 * (size_t)i], qx = a.rotation[4 * (size_t)i + 1], qy = a.rotation[4 * (size_t)i + 2], qz = a.rotation[4 * (size_t)i + 3];
-    const double norm = sqrt(qr * qr + qx * qx + qy * qy + qz * qz);
-    const double r = qr / norm, x = qx / norm, y = qy / norm, z = qz / norm;
+    const Quat64 q = unit_quat64(a.rotation[4 * (size_t)i], a.rotation[4 * (size_t)i + 1], a.rotation[4 * (size_t)i + 2], a.rotation[4 * (size_t)i + 3]);
     const double s0 = (double)a.noise[3 * (size_t)n] * exp((double)a.scaling[3 * (size_t)i]),
                  s1 = (double)a.noise[3 * (size_t)n + 1] * exp((double)a.scaling[3 * (size_t)i + 1]),
                  s2 = (double)a.noise[3 * (size_t)n + 2] * exp((double)a.scaling[3 * (size_t)i + 2]);
-    double m0, m1, m2;
-    if (c == 0) { m0 = 1.0 - 2.0 * (y * y + z * z); m1 = 2.0 * (x * y - r * z); m2 = 2.0 * (x * z + r * y); }
-    else if (c == 1) { m0 = 2.0 * (x * y + r * z); m1 = 1.0 - 2.0 * (x * x + z * z); m2 = 2.0 * (y * z - r * x); }
-    else { m0 = 2.0 * (x * z - r * y); m1 = 2.0 * (y * z + r * x); m2 = 1.0 - 2.0 * (x * x + y * y); }
-    return (float)(m0 * s0 + m1 * s1 + m2 * s2 + (double)xyz[3 * (size_t)i + c]);
+    const Row64 m = rot_row(q, c);
+    return (float)(m.c0 * s0 + m.c1 * s1 + m.c2 * s2 + (double)xyz[3 * (size_t)i + c]);
 }
 
 __global__ __launch_bounds__(256) void densify_apply_kernel(ApplyArgs a) {
     // the plan in the workspace must be the one the caller sized the outputs for (uniform)
     if (a.counts[C_PNEW] != a.p_new || a.counts[C_NSPLIT] != a.n_split) return;
-    const ApplyGroupDev &G = a.grp[group_of_block(a)];
+    const GroupDev &G = a.grp[group_of_block(a)];
     const uint32_t w = G.w;
     const uint64_t total = (uint64_t)a.p_new * w;               // < 2^32 (checked by the caller)
-    const uint64_t base = (uint64_t)(blockIdx.x - G.first_block) * APPLY_PER_BLOCK;
+    const uint64_t base = (uint64_t)(blockIdx.x - G.first_block) * GROUP_PER_BLOCK;
     const uint32_t child0 = a.counts[C_KEEP_SELF] + a.counts[C_KEEP_CLONE], keep_child = a.counts[C_KEEP_CHILD];
     const bool moments = G.dm != nullptr;
     if (G.vec4) {                                               // w % 4 == 0, role copy: a float4 never leaves its row
@@ -231,7 +217,7 @@ __global__ __launch_bounds__(256) void densify_apply_kernel(ApplyArgs a) {
         return;
     }
 #pragma unroll 1
-    for (int it = 0; it < APPLY_PER_BLOCK / 256; it++) {
+    for (int it = 0; it < GROUP_PER_BLOCK / 256; it++) {
         const uint64_t e = base + (uint64_t)it * 256 + threadIdx.x;
         if (e >= total) return;
         const uint32_t row = (uint32_t)(e / w), c = (uint32_t)(e - (uint64_t)row * w);
@@ -271,18 +257,7 @@ static hipError_t launch_densify_apply(int P, int N, uint32_t n_split, uint32_t 
     a.P = P; a.N = N; a.p_new = p_new; a.n_split = n_split; a.child_div = 0.8 * (double)N;
     a.scaling = scaling; a.rotation = rotation; a.noise = noise;
     a.map = w.map; a.counts = w.counts; a.ranks = w.ranks;
-    unsigned blocks = 0;
-    for (int k = 0; k < n_groups; k++) {
-        const gsr_density_group_t &h = groups[k];
-        if (h.width_floats <= 0) continue;
-        ApplyGroupDev &d = a.grp[a.n_groups++];
-        d.src = h.src; d.sm = h.src_exp_avg; d.sv = h.src_exp_avg_sq; d.dst = h.dst; d.dm = h.dst_exp_avg; d.dv = h.dst_exp_avg_sq;
-        d.w = (uint32_t)h.width_floats; d.role = h.role; d.first_block = blocks;
-        const uintptr_t bits = (uintptr_t)h.src | (uintptr_t)h.dst | (uintptr_t)h.src_exp_avg | (uintptr_t)h.src_exp_avg_sq |
-                               (uintptr_t)h.dst_exp_avg | (uintptr_t)h.dst_exp_avg_sq;
-        d.vec4 = (h.role == GSR_DENSITY_COPY && h.width_floats % 4 == 0 && (bits & 15) == 0) ? 1 : 0;
-        blocks += (unsigned)(((uint64_t)p_new * d.w + APPLY_PER_BLOCK - 1) / APPLY_PER_BLOCK);
-    }
+    const unsigned blocks = fill_group_table(n_groups, groups, p_new, GSR_DENSITY_COPY, a.grp, a.n_groups);
     if (blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(densify_apply_kernel, dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();
@@ -354,13 +329,10 @@ int32_t gsr_densify_apply(gsr_stream_t stream, int32_t P, int32_t N, int32_t n_s
     if (ws_bytes < need) return fail(GSR_ERR_WORKSPACE, "densify workspace %zu < %zu", ws_bytes, need);
     for (int k = 0; k < n_groups; k++) {
         const gsr_density_group_t &g = groups[k];
-        if (g.width_floats < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: width %d", k, g.width_floats);
+        GSR_TRY(refuse_group_size("gsr_densify_apply", k, g, (unsigned long long)P_new, "P_new"));
         if (g.width_floats == 0) continue;
-        if ((unsigned long long)P_new * (unsigned long long)g.width_floats > 0xffffffffULL)
-            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: P_new * width must stay below 2^32", k);
         if (!g.src || !g.dst || g.src == g.dst) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: src / dst NULL or equal", k);
-        const int nm = (g.src_exp_avg != nullptr) + (g.src_exp_avg_sq != nullptr) + (g.dst_exp_avg != nullptr) + (g.dst_exp_avg_sq != nullptr);
-        if (nm != 0 && nm != 4) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: the four moment pointers must all be given or all be NULL", k);
+        GSR_TRY(refuse_group_moments("gsr_densify_apply", k, g));
         if (g.role != GSR_DENSITY_COPY && g.role != GSR_DENSITY_XYZ && g.role != GSR_DENSITY_SCALING)
             return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_densify_apply: group %d: role %d", k, g.role);
         if (g.role != GSR_DENSITY_COPY && g.width_floats != 3)

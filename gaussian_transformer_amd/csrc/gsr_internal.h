@@ -44,7 +44,7 @@ struct Bump {      // hands out consecutive 256-byte-aligned pieces of a workspa
     template <class T> T *take_last(size_t count) { char *r = base ? base + off : nullptr; off += count * sizeof(T); return (T *)r; }      // a last piece whose end is not rounded up
 };
 
-// One launch over several groups of elements (adam.hip, density.hip): group k owns the blocks [grp[k].first_block, grp[k + 1].first_block).
+// One launch over several groups of elements (adam.hip; group_table.h for density.hip and mcmc.hip): group k owns the blocks [grp[k].first_block, grp[k + 1].first_block).
 // The group of this block (block-uniform); Args: any kernel-argument struct with n_groups and grp[].first_block.
 template <class Args>
 __device__ __forceinline__ int group_of_block(const Args &a) {

@@ -2,10 +2,12 @@
 //   plan       : weight kernel (one lane per row: dead flag, integer weight) -> one rocPRIM inclusive scan that carries the uint64 CDF and
 //                the rank among the dead rows in one value -> draw kernel (one lane per draw: binary search of the CDF, integer histogram)
 //                -> correction kernel (one lane per row: a source's new opacity and scaling in float64, into the workspace).
-//   apply      : ONE launch over (row, column) of every group, as density.hip's apply pass: consecutive lanes write consecutive floats of
-//                the parameter and both moments; 16-byte accesses where the width is a multiple of 4 and every pointer is aligned.  In
-//                place (relocation) a lane whose row is neither a source nor a destination returns without touching memory.
-//   noise      : one lane per Gaussian, 56 B read and 12 B written; float64 inside, rounded once.
+//   apply      : ONE launch over (row, column) of every group: consecutive lanes write consecutive floats of the parameter and both
+//                moments; 16-byte accesses where the width is a multiple of 4 and every pointer is aligned.  In place (relocation) a
+//                lane whose row is neither a source nor a destination returns without touching memory.  The group table, its filler
+//                and the common group refusals are group_table.h's, shared with density.hip; the kernel, which reads from[] and
+//                hist[] under a mode, is this file's.
+//   noise      : one lane per Gaussian, 56 B read and 12 B written; float64 inside (the rotation is group_table.h's), rounded once.
 //   regularize : one lane per Gaussian; the two means through a fixed two-level float64 sum (workgroup tree, then one workgroup).
 // Compiled with -ffp-contract=off -fno-slp-vectorize like density.hip: t_j is one IEEE multiply, the regularisers round as written.
 // Every row index a kernel forms (src_j, a destination, a workspace slot) is checked against its bound in every build.  The only atomics
@@ -15,8 +17,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/gsr_mcmc.h"
-#include "gsr_host.h"
-#include "gsr_internal.h"
+#include "group_table.h"
 
 namespace gsr {
 
@@ -178,31 +179,21 @@ static hipError_t launch_mcmc_plan(int mode, int P, const float *opacity, const 
 
 // ---------------------------------------------------------------- apply ----------------------------------------------------------------
 
-struct McmcGroupDev {
-    const float *src, *sm, *sv;
-    float *dst, *dm, *dv;
-    uint32_t w;
-    int role;
-    unsigned first_block;        // the group's blocks are [first_block, next group's first_block)
-    int vec4;
-};
 struct McmcApplyArgs {
-    McmcGroupDev grp[GSR_MCMC_MAX_GROUPS];
+    GroupDev grp[GSR_MCMC_MAX_GROUPS];
     int n_groups, P, mode;
     uint32_t n, p_new;
     const uint32_t *from, *hist, *counts;
     const float *new_op, *new_sc;
 };
 
-#define MCMC_PER_BLOCK 1024        // floats of one group per block: 4 rounds of 256 lanes, or 256 lanes x 16 bytes
-
 __global__ __launch_bounds__(256) void mcmc_apply_kernel(McmcApplyArgs a) {
     // the plan in the workspace must be the one the caller sized the outputs for (uniform)
     if (a.counts[M_PNEW] != a.p_new || a.counts[M_MODE] != (uint32_t)a.mode || a.counts[M_NARG] != a.n) return;
-    const McmcGroupDev &G = a.grp[group_of_block(a)];
+    const GroupDev &G = a.grp[group_of_block(a)];
     const uint32_t w = G.w, P = (uint32_t)a.P;
     const uint64_t total = (uint64_t)a.p_new * w;               // < 2^32 (checked by the caller)
-    const uint64_t base = (uint64_t)(blockIdx.x - G.first_block) * MCMC_PER_BLOCK;
+    const uint64_t base = (uint64_t)(blockIdx.x - G.first_block) * GROUP_PER_BLOCK;
     const bool moments = G.dm != nullptr, in_place = a.mode == GSR_MCMC_RELOCATE;
     if (G.vec4) {                                               // w % 4 == 0, role copy: a float4 never leaves its row
         const uint64_t e = base + (uint64_t)threadIdx.x * 4;
@@ -223,7 +214,7 @@ __global__ __launch_bounds__(256) void mcmc_apply_kernel(McmcApplyArgs a) {
         return;
     }
 #pragma unroll 1
-    for (int it = 0; it < MCMC_PER_BLOCK / 256; it++) {
+    for (int it = 0; it < GROUP_PER_BLOCK / 256; it++) {
         const uint64_t e = base + (uint64_t)it * 256 + threadIdx.x;
         if (e >= total) return;
         const uint32_t row = (uint32_t)(e / w), c = (uint32_t)(e - (uint64_t)row * w);
@@ -252,18 +243,7 @@ static hipError_t launch_mcmc_apply(int mode, int P, int n, int n_groups, const 
     memset(&a, 0, sizeof(a));
     a.P = P; a.mode = mode; a.n = (uint32_t)n; a.p_new = (uint32_t)P + (uint32_t)n;
     a.from = w.from; a.hist = w.hist; a.counts = w.counts; a.new_op = w.new_op; a.new_sc = w.new_sc;
-    unsigned blocks = 0;
-    for (int k = 0; k < n_groups; k++) {
-        const gsr_mcmc_group_t &h = groups[k];
-        if (h.width_floats <= 0) continue;
-        McmcGroupDev &d = a.grp[a.n_groups++];
-        d.src = h.src; d.sm = h.src_exp_avg; d.sv = h.src_exp_avg_sq; d.dst = h.dst; d.dm = h.dst_exp_avg; d.dv = h.dst_exp_avg_sq;
-        d.w = (uint32_t)h.width_floats; d.role = h.role; d.first_block = blocks;
-        const uintptr_t bits = (uintptr_t)h.src | (uintptr_t)h.dst | (uintptr_t)h.src_exp_avg | (uintptr_t)h.src_exp_avg_sq |
-                               (uintptr_t)h.dst_exp_avg | (uintptr_t)h.dst_exp_avg_sq;
-        d.vec4 = (h.role == GSR_MCMC_COPY && h.width_floats % 4 == 0 && (bits & 15) == 0) ? 1 : 0;
-        blocks += (unsigned)(((uint64_t)a.p_new * d.w + MCMC_PER_BLOCK - 1) / MCMC_PER_BLOCK);
-    }
+    const unsigned blocks = fill_group_table(n_groups, groups, a.p_new, GSR_MCMC_COPY, a.grp, a.n_groups);
     if (blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(mcmc_apply_kernel, dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();
@@ -282,22 +262,18 @@ __global__ __launch_bounds__(256) void mcmc_noise_kernel(int P, const float *__r
     if (i >= P) return;
     const double f = 1.0 / (1.0 + exp((double)gate_k * (sigmoid64((double)opacity[i]) - (double)gate_t)));
     const float4 q4 = *reinterpret_cast<const float4 *>(rotation + 4 * (size_t)i);      // rows of 16 bytes: aligned with the buffer (checked by the caller)
-    const double qr = q4.x, qx = q4.y, qy = q4.z, qz = q4.w;
-    const double norm = sqrt(qr * qr + qx * qx + qy * qy + qz * qz);
-    const double r = qr / norm, x = qx / norm, y = qy / norm, z = qz / norm;
-    const double R00 = 1.0 - 2.0 * (y * y + z * z), R01 = 2.0 * (x * y - r * z), R02 = 2.0 * (x * z + r * y);
-    const double R10 = 2.0 * (x * y + r * z), R11 = 1.0 - 2.0 * (x * x + z * z), R12 = 2.0 * (y * z - r * x);
-    const double R20 = 2.0 * (x * z - r * y), R21 = 2.0 * (y * z + r * x), R22 = 1.0 - 2.0 * (x * x + y * y);
+    const Quat64 q = unit_quat64(q4.x, q4.y, q4.z, q4.w);
+    const Row64 R0 = rot_row(q, 0), R1 = rot_row(q, 1), R2 = rot_row(q, 2);
     const size_t b = 3 * (size_t)i;
     const double s0 = exp((double)scaling[b]), s1 = exp((double)scaling[b + 1]), s2 = exp((double)scaling[b + 2]);
     const double n0 = noise[b], n1 = noise[b + 1], n2 = noise[b + 2];
-    const double v0 = (R00 * n0 + R10 * n1 + R20 * n2) * (s0 * s0);                      // S^2 R^T noise
-    const double v1 = (R01 * n0 + R11 * n1 + R21 * n2) * (s1 * s1);
-    const double v2 = (R02 * n0 + R12 * n1 + R22 * n2) * (s2 * s2);
+    const double v0 = (R0.c0 * n0 + R1.c0 * n1 + R2.c0 * n2) * (s0 * s0);                // S^2 R^T noise
+    const double v1 = (R0.c1 * n0 + R1.c1 * n1 + R2.c1 * n2) * (s1 * s1);
+    const double v2 = (R0.c2 * n0 + R1.c2 * n1 + R2.c2 * n2) * (s2 * s2);
     const double g = f * (double)scale;
-    xyz[b] = (float)((double)xyz[b] + (R00 * v0 + R01 * v1 + R02 * v2) * g);
-    xyz[b + 1] = (float)((double)xyz[b + 1] + (R10 * v0 + R11 * v1 + R12 * v2) * g);
-    xyz[b + 2] = (float)((double)xyz[b + 2] + (R20 * v0 + R21 * v1 + R22 * v2) * g);
+    xyz[b] = (float)((double)xyz[b] + (R0.c0 * v0 + R0.c1 * v1 + R0.c2 * v2) * g);
+    xyz[b + 1] = (float)((double)xyz[b + 1] + (R1.c0 * v0 + R1.c1 * v1 + R1.c2 * v2) * g);
+    xyz[b + 2] = (float)((double)xyz[b + 2] + (R2.c0 * v0 + R2.c1 * v1 + R2.c2 * v2) * g);
 }
 
 // ---------------------------------------------------------------- regularize ----------------------------------------------------------------
@@ -408,13 +384,11 @@ int32_t gsr_mcmc_apply(gsr_stream_t stream, int32_t mode, int32_t P, int32_t n_d
     const bool in_place = mode == GSR_MCMC_RELOCATE;
     for (int k = 0; k < n_groups; k++) {
         const gsr_mcmc_group_t &g = groups[k];
-        if (g.width_floats < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_mcmc_apply: group %d: width %d", k, g.width_floats);
+        GSR_TRY(refuse_group_size("gsr_mcmc_apply", k, g, (unsigned long long)p_new, "(P + n_draws)"));
         if (g.width_floats == 0) continue;
-        if ((unsigned long long)p_new * (unsigned long long)g.width_floats > 0xffffffffULL)
-            return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_mcmc_apply: group %d: (P + n_draws) * width must stay below 2^32", k);
         if (!g.src || !g.dst) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_mcmc_apply: group %d: src / dst NULL", k);
-        const int nm = (g.src_exp_avg != nullptr) + (g.src_exp_avg_sq != nullptr) + (g.dst_exp_avg != nullptr) + (g.dst_exp_avg_sq != nullptr);
-        if (nm != 0 && nm != 4) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_mcmc_apply: group %d: the four moment pointers must all be given or all be NULL", k);
+        int nm = 0;
+        GSR_TRY(refuse_group_moments("gsr_mcmc_apply", k, g, &nm));
         const bool same = g.src == g.dst && g.src_exp_avg == g.dst_exp_avg && g.src_exp_avg_sq == g.dst_exp_avg_sq;
         const bool apart = g.src != g.dst && (nm == 0 || (g.src_exp_avg != g.dst_exp_avg && g.src_exp_avg_sq != g.dst_exp_avg_sq));
         if (in_place ? !same : !apart)

@@ -90,10 +90,7 @@ class DensityController:
         self.opt = opt or OptimizationParams()
         self.spatial_lr_scale = spatial_lr_scale
         o = self.opt
-        P, dev = model._xyz.shape[0], model._xyz.device
-        model.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
-        model.denom = torch.zeros((P, 1), device=dev)
-        model.max_radii2D = torch.zeros((P,), device=dev)
+        self._zero_statistics(model._xyz.shape[0], model._xyz.device)
         lrs = {"xyz": o.position_lr_init * spatial_lr_scale, "f_dc": o.feature_lr, "f_rest": o.feature_lr / 20.0,
                "opacity": o.opacity_lr, "scaling": o.scaling_lr, "rotation": o.rotation_lr}
         for n in GROUPS:           # the optimiser must own leaf tensors it can replace
@@ -119,21 +116,38 @@ class DensityController:
         return lr
 
     # ---- optimiser-state surgery: every change of the Gaussian set is one row map applied to parameter and moments ----
-    def _remap(self, param_fn: Callable[[str, torch.Tensor], torch.Tensor],
-               moment_fn: Callable[[str, torch.Tensor], torch.Tensor], only: Optional[str] = None) -> None:
+    def _install(self, new: Dict[str, torch.Tensor], states: Dict[str, Optional[tuple]]) -> None:
+        """The one place a group gets a new tensor: the optimiser state of every group in `new` moves from the old parameter to the new
+        Parameter -- with the moments states[name] = (exp_avg, exp_avg_sq), or its own where that is None -- which group and model take."""
         for g in self.optimizer.param_groups:
             name = g["name"]
+            if name not in new:
+                continue
+            state = self.optimizer.state.pop(g["params"][0], None)
+            p = torch.nn.Parameter(new[name].requires_grad_(True))
+            if state is not None:
+                if states[name] is not None:
+                    state["exp_avg"], state["exp_avg_sq"] = states[name]
+                self.optimizer.state[p] = state
+            g["params"][0] = p
+            setattr(self.model, _ATTR[name], p)
+
+    def _remap(self, param_fn: Callable[[str, torch.Tensor], torch.Tensor],
+               moment_fn: Callable[[str, torch.Tensor], torch.Tensor], only: Optional[str] = None) -> None:
+        for g in self.optimizer.param_groups:                       # group by group: one group's old and new tensors live at a time
+            name, old = g["name"], g["params"][0]
             if only is not None and name != only:
                 continue
-            old = g["params"][0]
-            state = self.optimizer.state.pop(old, None)
-            new = torch.nn.Parameter(param_fn(name, old.detach()).requires_grad_(True))
-            if state is not None:
-                state["exp_avg"] = moment_fn(name, state["exp_avg"])
-                state["exp_avg_sq"] = moment_fn(name, state["exp_avg_sq"])
-                self.optimizer.state[new] = state
-            g["params"][0] = new
-            setattr(self.model, _ATTR[name], new)
+            state = self.optimizer.state.get(old, None)
+            new = param_fn(name, old.detach())
+            moments = (moment_fn(name, state["exp_avg"]), moment_fn(name, state["exp_avg_sq"])) if state is not None else None
+            self._install({name: new}, {name: moments})
+
+    def _zero_statistics(self, P: int, dev) -> None:
+        m = self.model
+        m.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
+        m.denom = torch.zeros((P, 1), device=dev)
+        m.max_radii2D = torch.zeros((P,), device=dev)
 
     def prune_points(self, mask: torch.Tensor) -> None:
         """Removes the Gaussians where `mask` is True (:287-301)."""
@@ -181,11 +195,7 @@ class DensityController:
     def append_points(self, new: Dict[str, torch.Tensor]) -> None:
         """Appends Gaussians with zero Adam moments and resets the densification statistics (:303-347)."""
         self._remap(lambda n, p: torch.cat((p, new[n]), dim=0), lambda n, m: torch.cat((m, torch.zeros_like(new[n])), dim=0))
-        m = self.model
-        P, dev = m._xyz.shape[0], m._xyz.device
-        m.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
-        m.denom = torch.zeros((P, 1), device=dev)
-        m.max_radii2D = torch.zeros((P,), device=dev)
+        self._zero_statistics(self.model._xyz.shape[0], self.model._xyz.device)
 
     def replace_tensor(self, name: str, tensor: torch.Tensor) -> None:
         """New values for one group, its Adam moments zeroed (:258-271)."""
@@ -272,10 +282,66 @@ class DensityController:
         return out
 
 
-_ROLE = {"xyz": _lib.DENSITY_XYZ, "scaling": _lib.DENSITY_SCALING}          # every other group is a plain copy
+class _FusedGroups:
+    """What the two controllers on the HIP path share: the check of a tensor that crosses the boundary, the groups' current tensors,
+    a workspace kept across calls, the tensors of a new state and the group table of an apply entry point (csrc/group_table.h)."""
+
+    def _device_f32(self, name: str, t) -> torch.Tensor:
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise _lib.GsrError(f"{type(self).__name__}: {name} must be on a HIP device (no CPU fallback)")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.GsrError(f"{type(self).__name__}: {name} must be contiguous float32, got {t.dtype}")
+        return t
+
+    def _olds(self) -> Dict[str, torch.Tensor]:
+        olds = {g["name"]: g["params"][0].detach() for g in self.optimizer.param_groups}
+        for n in GROUPS:
+            self._device_f32(n, olds[n])
+        return olds
+
+    def _workspace(self, key: str, dev, sizer: str, *sizes) -> torch.Tensor:
+        """As many bytes as `sizer` asks for, kept across calls under `key` (not _lib.workspace()) and regrown when too small or on
+        another device.  Call it inside torch.cuda.device(dev)."""
+        need = _lib.workspace_bytes(sizer, *sizes)
+        ws = self._kept.get(key)
+        if ws is None or ws.numel() < need or ws.device != dev:
+            ws = self._kept[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+        return ws
+
+    def _moments(self, g):
+        """(exp_avg, exp_avg_sq) of a group, each checked, or None where the optimiser holds none yet"""
+        state = self.optimizer.state.get(g["params"][0], None)
+        if state is None or "exp_avg" not in state:
+            return None
+        return self._device_f32(g["name"] + " exp_avg", state["exp_avg"]), self._device_f32(g["name"] + " exp_avg_sq", state["exp_avg_sq"])
+
+    def _allocate(self, P_new: int, dev):
+        """({group: [P_new, ...] tensor}, {group: two such tensors for the moments, or None where the group has none})"""
+        new, states = {}, {}
+        for g in self.optimizer.param_groups:
+            shape = (P_new,) + tuple(g["params"][0].shape[1:])
+            new[g["name"]] = torch.empty(shape, device=dev)
+            states[g["name"]] = (torch.empty(shape, device=dev), torch.empty(shape, device=dev)) if self._moments(g) else None
+        return new, states
+
+    def _group_table(self, struct, roles, olds, new=None, states=None):
+        """(ctypes array of `struct`, its length) over the groups of positive width: in place (new None: dst == src) or into the
+        tensors of new / states."""
+        ptr, descs = _lib.ptr, []
+        for g in self.optimizer.param_groups:
+            n, old = g["name"], olds[g["name"]]
+            sm = self._moments(g) or (None, None)
+            width = old[0].numel() if old.shape[0] else 0
+            if width:
+                dst, dm = (old, sm) if new is None else (new[n], states[n] or (None, None))
+                descs.append(struct(ptr(old), ptr(sm[0]), ptr(sm[1]), ptr(dst), ptr(dm[0]), ptr(dm[1]), width, roles[n]))
+        return (struct * len(descs))(*descs), len(descs)
 
 
-class FusedDensityController(DensityController):
+_ROLE = {**dict.fromkeys(GROUPS, _lib.DENSITY_COPY), "xyz": _lib.DENSITY_XYZ, "scaling": _lib.DENSITY_SCALING}
+
+
+class FusedDensityController(_FusedGroups, DensityController):
     """DensityController with `record` and `densify_and_prune` on the device (include/gsr_density.h, csrc/density.hip):
     record is one launch without a host wait; densify_and_prune decides every Gaussian once, waits once for the four counts,
     and writes the new parameters and Adam moments in one launch instead of rebuilding them four times.  Same constructor,
@@ -287,15 +353,7 @@ class FusedDensityController(DensityController):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self._counts = None            # pinned host words {n_clone, n_split, n_pruned, P_new}
-        self._ws = None
-
-    @staticmethod
-    def _device_f32(name: str, t: torch.Tensor) -> torch.Tensor:
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise _lib.GsrError(f"FusedDensityController: {name} must be on a HIP device (no CPU fallback)")
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise _lib.GsrError(f"FusedDensityController: {name} must be contiguous float32, got {t.dtype}")
-        return t
+        self._kept = {}                # _workspace()
 
     def record(self, viewspace_points: torch.Tensor, visibility: Optional[torch.Tensor], radii: torch.Tensor) -> None:
         """train.py:113-116 in one launch.  viewspace_points.grad is taken as it comes: [P, >= 2] float32 with unit column
@@ -327,36 +385,25 @@ class FusedDensityController(DensityController):
             _lib.call("gsr_density_record", _lib.stream(grad.device), P, grad.data_ptr(), max(int(grad.stride(0)), 2), ptr(radii),
                       ptr(visibility), ptr(accum), ptr(denom), ptr(mx))
 
-    def _reset_statistics(self, P: int, dev) -> None:
-        m = self.model
-        m.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
-        m.denom = torch.zeros((P, 1), device=dev)
-        m.max_radii2D = torch.zeros((P,), device=dev)
-
     def densify_and_prune(self, max_grad: float, min_opacity: float, extent: float, max_screen_size: Optional[float],
                           generator: Optional[torch.Generator] = None, normal_fn: Optional[Callable] = None) -> Dict[str, int]:
         """:389-403 as plan -> one wait for the counts -> samples -> allocate -> apply -> install."""
         m = self.model
         N = self.SPLIT_N
-        olds = {g["name"]: g["params"][0] for g in self.optimizer.param_groups}
-        for n in GROUPS:
-            self._device_f32(n, olds[n].detach())
+        olds = self._olds()
         accum, denom = self._device_f32("xyz_gradient_accum", m.xyz_gradient_accum), self._device_f32("denom", m.denom)
         dev = olds["xyz"].device
         P = olds["xyz"].shape[0]
         if P == 0:
-            self._reset_statistics(0, dev)
+            self._zero_statistics(0, dev)
             return {"cloned": 0, "split": 0, "pruned": 0}
         f32 = lambda v: float(np.float32(v))       # torch compares a float32 tensor with float32(number)
         ptr = _lib.ptr
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)        # the object, not only _lib.stream(dev): it is waited for below
-            need = _lib.workspace_bytes("gsr_densify_plan_workspace", P, N)
-            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)        # kept across calls: not _lib.workspace()
+            ws = self._workspace("plan", dev, "gsr_densify_plan_workspace", P, N)
             if self._counts is None:
                 self._counts = torch.zeros(4, dtype=torch.int32).pin_memory()
-            ws = self._ws
             # 1. plan
             _lib.call("gsr_densify_plan", _lib.stream(dev), P, ptr(olds["opacity"]), ptr(olds["scaling"]), ptr(accum), ptr(denom),
                       f32(max_grad), f32(min_opacity), f32(self.opt.percent_dense * extent),
@@ -369,39 +416,15 @@ class FusedDensityController(DensityController):
             noise = normal_fn(ones) if normal_fn is not None else torch.normal(mean=torch.zeros_like(ones), std=ones, generator=generator)
             noise = noise.to(device=dev, dtype=torch.float32).contiguous()
             # 4. the new tensors
-            new, states, descs = {}, {}, []
-            for g in self.optimizer.param_groups:
-                n, old = g["name"], g["params"][0]
-                state = self.optimizer.state.get(old, None)
-                has = state is not None and "exp_avg" in state
-                if has:
-                    self._device_f32(n + " exp_avg", state["exp_avg"]); self._device_f32(n + " exp_avg_sq", state["exp_avg_sq"])
-                shape = (P_new,) + tuple(old.shape[1:])
-                new[n] = torch.empty(shape, device=dev)
-                states[n] = (torch.empty(shape, device=dev), torch.empty(shape, device=dev)) if has else None
-                width = old[0].numel()
-                if width:
-                    moments = ((state["exp_avg"], state["exp_avg_sq"]) + states[n]) if has else (None,) * 4
-                    descs.append(_lib.DensityGroup(ptr(old), ptr(moments[0]), ptr(moments[1]), ptr(new[n]), ptr(moments[2]), ptr(moments[3]),
-                                                   width, _ROLE.get(n, _lib.DENSITY_COPY)))
+            new, states = self._allocate(P_new, dev)
+            arr, k = self._group_table(_lib.DensityGroup, _ROLE, olds, new, states)
             # 5. apply
             if P_new:
-                arr = (_lib.DensityGroup * len(descs))(*descs)
-                _lib.call("gsr_densify_apply", _lib.stream(dev), P, N, n_split, P_new, len(descs), arr, ptr(olds["scaling"]),
+                _lib.call("gsr_densify_apply", _lib.stream(dev), P, N, n_split, P_new, k, arr, ptr(olds["scaling"]),
                           ptr(olds["rotation"]), ptr(noise), ptr(ws), ws.numel())
-        # 6. install, as _remap does
-        for g in self.optimizer.param_groups:
-            n, old = g["name"], g["params"][0]
-            state = self.optimizer.state.pop(old, None)
-            p = torch.nn.Parameter(new[n].requires_grad_(True))
-            if state is not None:
-                if states[n] is not None:
-                    state["exp_avg"], state["exp_avg_sq"] = states[n]
-                self.optimizer.state[p] = state
-            g["params"][0] = p
-            setattr(m, _ATTR[n], p)
-        # 7. statistics of the new set
-        self._reset_statistics(P_new, dev)
+        # 6. install, 7. statistics of the new set
+        self._install(new, states)
+        self._zero_statistics(P_new, dev)
         return {"cloned": n_clone, "split": n_split, "pruned": n_pruned}
 
 
@@ -564,15 +587,9 @@ class MCMCController(DensityController):
             m[srcs] = 0
             return torch.cat((m, torch.zeros((n,) + tuple(m.shape[1:]), dtype=m.dtype, device=m.device)), dim=0)
         self._remap(param_fn, moment_fn)
-        self._resize_statistics(P_new, dev)
+        self._zero_statistics(P_new, dev)
         self._last["grow"] = {"n_dead": int(dead.sum()), "n_draws": n if total else 0, "n_sources": int(srcs.shape[0]), "P_new": P_new}
         return P_new
-
-    def _resize_statistics(self, P: int, dev) -> None:
-        m = self.model
-        m.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
-        m.denom = torch.zeros((P, 1), device=dev)
-        m.max_radii2D = torch.zeros((P,), device=dev)
 
     # ---- every iteration ----
     def add_noise(self, generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None) -> None:
@@ -624,29 +641,20 @@ class MCMCController(DensityController):
             self.grow(generator=generator)
 
 
-_MCMC_ROLE = {"opacity": _lib.MCMC_OPACITY, "scaling": _lib.MCMC_SCALING}     # every other group is a plain copy
+_MCMC_ROLE = {**dict.fromkeys(GROUPS, _lib.MCMC_COPY), "opacity": _lib.MCMC_OPACITY, "scaling": _lib.MCMC_SCALING}
 
 
-class FusedMCMCController(MCMCController):
+class FusedMCMCController(_FusedGroups, MCMCController):
     """MCMCController on the HIP path (include/gsr_mcmc.h, csrc/mcmc.hip).  relocate, add_noise and regularize enqueue their kernels
-    and return: no host wait.  grow allocates the new rows -- their number is known on the host -- and installs them as _remap
-    does, also without a wait.  counts() is the one method that synchronises.  Same results as MCMCController: indices, counts
+    and return: no host wait.  grow allocates the new rows -- their number is known on the host -- and installs them through
+    _install, as _remap does, also without a wait.  counts() is the one method that synchronises.  Same results as MCMCController: indices, counts
     and copied rows bit for bit, the corrected opacity and scaling to one float32 ulp.  No CPU fallback."""
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
-        self._ws = None
-        self._reg_ws = None
+        self._kept = {}                # _workspace()
         self._pinned = {}              # which -> pinned host words {n_dead, n_draws, n_sources, P_new}
         self._issued = {}              # which -> device the last plan ran on
-
-    @staticmethod
-    def _device_f32(name: str, t) -> torch.Tensor:
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise _lib.GsrError(f"FusedMCMCController: {name} must be on a HIP device (no CPU fallback)")
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise _lib.GsrError(f"FusedMCMCController: {name} must be contiguous float32, got {t.dtype}")
-        return t
 
     def counts(self, which: str = "relocate") -> Dict[str, int]:
         """Waits for the device, then {"n_dead", "n_draws", "n_sources", "P_new"} of the last relocate() or grow()."""
@@ -655,38 +663,19 @@ class FusedMCMCController(MCMCController):
         torch.cuda.current_stream(self._issued[which]).synchronize()
         return dict(zip(("n_dead", "n_draws", "n_sources", "P_new"), (int(v) for v in self._pinned[which].tolist())))
 
-    def _groups(self, olds, news=None, new_states=None):
-        """The group table of gsr_mcmc_apply: in place (news None) or into the tensors of news / new_states."""
-        ptr, descs = _lib.ptr, []
-        for g in self.optimizer.param_groups:
-            n, old = g["name"], olds[g["name"]]
-            state = self.optimizer.state.get(g["params"][0], None)
-            has = state is not None and "exp_avg" in state
-            width = old[0].numel() if old.shape[0] else 0
-            if not width:
-                continue
-            sm = (self._device_f32(n + " exp_avg", state["exp_avg"]), self._device_f32(n + " exp_avg_sq", state["exp_avg_sq"])) if has else (None, None)
-            dst, dm = (old, sm) if news is None else (news[n], new_states[n] if has else (None, None))
-            descs.append(_lib.McmcGroup(ptr(old), ptr(sm[0]), ptr(sm[1]), ptr(dst), ptr(dm[0]), ptr(dm[1]), width, _MCMC_ROLE.get(n, _lib.MCMC_COPY)))
-        return (_lib.McmcGroup * len(descs))(*descs), len(descs)
-
-    def _plan(self, which: str, mode: int, olds, P: int, n: int, u: torch.Tensor, dev):
-        need = _lib.workspace_bytes("gsr_mcmc_plan_workspace", P, n)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)            # kept across calls: not _lib.workspace()
-        if which not in self._pinned:
-            self._pinned[which] = torch.zeros(4, dtype=torch.int32).pin_memory()
+    def _plan_and_apply(self, which: str, mode: int, olds, P: int, n: int, u: torch.Tensor, dev, new=None, states=None) -> None:
+        """gsr_mcmc_plan, then gsr_mcmc_apply in place (new None) or into new / states: two calls enqueued, nothing waited for."""
         ptr = _lib.ptr
-        _lib.call("gsr_mcmc_plan", _lib.stream(dev), mode, P, ptr(olds["opacity"]), ptr(olds["scaling"]), self.dead_logit, float(self.mcmc.min_opacity),
-                  int(self.mcmc.n_max), n, ptr(u), ptr(self._pinned[which]), ptr(self._ws), self._ws.numel())
-        self._last.pop(which, None)
-        self._issued[which] = dev
-
-    def _olds(self):
-        olds = {g["name"]: g["params"][0].detach() for g in self.optimizer.param_groups}
-        for n in GROUPS:
-            self._device_f32(n, olds[n])
-        return olds
+        with torch.cuda.device(dev):
+            ws = self._workspace("plan", dev, "gsr_mcmc_plan_workspace", P, n)
+            if which not in self._pinned:
+                self._pinned[which] = torch.zeros(4, dtype=torch.int32).pin_memory()
+            _lib.call("gsr_mcmc_plan", _lib.stream(dev), mode, P, ptr(olds["opacity"]), ptr(olds["scaling"]), self.dead_logit, float(self.mcmc.min_opacity),
+                      int(self.mcmc.n_max), n, ptr(u), ptr(self._pinned[which]), ptr(ws), ws.numel())
+            self._last.pop(which, None)
+            self._issued[which] = dev
+            arr, k = self._group_table(_lib.McmcGroup, _MCMC_ROLE, olds, new, states)
+            _lib.call("gsr_mcmc_apply", _lib.stream(dev), mode, P, n, k, arr, ptr(ws), ws.numel())
 
     def relocate(self, generator: Optional[torch.Generator] = None, u: Optional[torch.Tensor] = None) -> None:
         olds = self._olds()
@@ -695,10 +684,7 @@ class FusedMCMCController(MCMCController):
         if P == 0:
             self._last["relocate"] = {"n_dead": 0, "n_draws": 0, "n_sources": 0, "P_new": 0}
             return
-        with torch.cuda.device(dev):
-            self._plan("relocate", _lib.MCMC_RELOCATE, olds, P, 0, u, dev)
-            arr, k = self._groups(olds)
-            _lib.call("gsr_mcmc_apply", _lib.stream(dev), _lib.MCMC_RELOCATE, P, 0, k, arr, _lib.ptr(self._ws), self._ws.numel())
+        self._plan_and_apply("relocate", _lib.MCMC_RELOCATE, olds, P, 0, u, dev)
 
     def grow(self, generator: Optional[torch.Generator] = None, u: Optional[torch.Tensor] = None) -> int:
         olds = self._olds()
@@ -709,28 +695,10 @@ class FusedMCMCController(MCMCController):
             self._last["grow"] = {"n_dead": 0, "n_draws": 0, "n_sources": 0, "P_new": P}
             return P
         u = self._device_f32("u", self._uniforms(n, generator, u, dev))
-        new, states = {}, {}
-        for g in self.optimizer.param_groups:
-            name, old = g["name"], g["params"][0]
-            state = self.optimizer.state.get(old, None)
-            shape = (P_new,) + tuple(old.shape[1:])
-            new[name] = torch.empty(shape, device=dev)
-            states[name] = (torch.empty(shape, device=dev), torch.empty(shape, device=dev)) if state is not None and "exp_avg" in state else None
-        with torch.cuda.device(dev):
-            self._plan("grow", _lib.MCMC_GROW, olds, P, n, u, dev)
-            arr, k = self._groups(olds, new, states)
-            _lib.call("gsr_mcmc_apply", _lib.stream(dev), _lib.MCMC_GROW, P, n, k, arr, _lib.ptr(self._ws), self._ws.numel())
-        for g in self.optimizer.param_groups:                       # install, as _remap does
-            name, old = g["name"], g["params"][0]
-            state = self.optimizer.state.pop(old, None)
-            p = torch.nn.Parameter(new[name].requires_grad_(True))
-            if state is not None:
-                if states[name] is not None:
-                    state["exp_avg"], state["exp_avg_sq"] = states[name]
-                self.optimizer.state[p] = state
-            g["params"][0] = p
-            setattr(self.model, _ATTR[name], p)
-        self._resize_statistics(P_new, dev)
+        new, states = self._allocate(P_new, dev)
+        self._plan_and_apply("grow", _lib.MCMC_GROW, olds, P, n, u, dev, new, states)
+        self._install(new, states)
+        self._zero_statistics(P_new, dev)
         return P_new
 
     def add_noise(self, generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None) -> None:
@@ -770,11 +738,8 @@ class FusedMCMCController(MCMCController):
                                     f"unit column stride, got {g.dtype} {tuple(g.shape)} strides {g.stride()}")
             strides.append(max(int(g.stride(0)), width))
         with torch.cuda.device(dev):
-            need = _lib.workspace_bytes("gsr_mcmc_regularize_workspace", P)
-            if self._reg_ws is None or self._reg_ws.numel() < need or self._reg_ws.device != dev:
-                self._reg_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            ws = self._workspace("regularize", dev, "gsr_mcmc_regularize_workspace", P)
             # .data_ptr(), not ptr(): the strided tensors that cross the boundary, handed over with their row strides
             _lib.call("gsr_mcmc_regularize", _lib.stream(dev), P, _lib.ptr(op.detach()), _lib.ptr(sc.detach()), op.grad.data_ptr(), strides[0],
-                      sc.grad.data_ptr(), strides[1], float(mc.opacity_reg), float(mc.scale_reg), _lib.ptr(means), _lib.ptr(self._reg_ws),
-                      self._reg_ws.numel())
+                      sc.grad.data_ptr(), strides[1], float(mc.opacity_reg), float(mc.scale_reg), _lib.ptr(means), _lib.ptr(ws), ws.numel())
         return mc.opacity_reg * means[0], mc.scale_reg * means[1]

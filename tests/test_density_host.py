@@ -121,6 +121,43 @@ def test_header_declares_exactly_what_the_ctypes_stub_binds():
         assert hasattr(lib, name)
 
 
+@pytest.mark.parametrize("change", ["prune_points", "append_points", "replace_tensor", "relocate", "grow"])
+def test_every_change_of_the_set_leaves_optimiser_model_and_statistics_consistent(change):
+    """After one torch.optim.Adam step on P = 65, whichever method changes the set: optimizer.state holds exactly the six installed
+    parameters, each the very object in its group and on the model, with moments of its shape; the statistics have P rows."""
+    from gaussian_transformer_amd.densify import MCMCController
+    from tests import mcmc_ref as mr
+    mcmc = change in ("relocate", "grow")
+    d = mr.clone_inputs(mr.build_inputs(65, 3)) if mcmc else dr.clone_inputs(dr.build_inputs(65, 3))
+    ctl = mr.make_controller(d, MCMCController, moments=False) if mcmc else make_controller(d, moments=False)
+    for g in ctl.optimizer.param_groups:
+        g["params"][0].grad = torch.ones_like(g["params"][0])
+    ctl.optimizer.step()
+    assert len(ctl.optimizer.state) == 6
+    with torch.no_grad():
+        if change == "prune_points":
+            ctl.prune_points(torch.arange(65) % 3 == 0)
+        elif change == "append_points":
+            ctl.append_points({n: getattr(ctl.model, ATTR[n]).detach()[:7] for n in GROUPS})
+        elif change == "replace_tensor":
+            ctl.replace_tensor("opacity", torch.zeros(65, 1))
+        elif change == "relocate":
+            ctl.relocate(u=mr.uniforms(65))
+            assert ctl.counts("relocate")["n_sources"] > 0
+        else:
+            assert ctl.grow(u=mr.uniforms(3)) == 68
+    P = {"prune_points": 43, "append_points": 72, "replace_tensor": 65, "relocate": 65, "grow": 68}[change]
+    state = ctl.optimizer.state
+    assert len(state) == 6
+    for g in ctl.optimizer.param_groups:
+        p = g["params"][0]
+        assert len(g["params"]) == 1 and p is getattr(ctl.model, ATTR[g["name"]]) and any(k is p for k in state), g["name"]
+        assert isinstance(p, torch.nn.Parameter) and p.shape[0] == P
+        assert state[p]["exp_avg"].shape == p.shape and state[p]["exp_avg_sq"].shape == p.shape, g["name"]
+    m = ctl.model
+    assert tuple(m.xyz_gradient_accum.shape) == (P, 1) and tuple(m.denom.shape) == (P, 1) and tuple(m.max_radii2D.shape) == (P,)
+
+
 def test_fused_controller_has_no_cpu_fallback():
     from gaussian_transformer_amd.densify import FusedDensityController
     ctl = make_controller(dr.clone_inputs(dr.build_inputs(65, 3)), cls=FusedDensityController)
