@@ -210,6 +210,16 @@ CONTRIB_SIGNATURES = {
     "gsr_contrib_read": (_i32, [_p, _i32, _p, _p, _p, _p]),                              # stream P rows weight_sum weight_max pixel_count
 }
 
+# include/gsr_absgrad.h (likewise a table of its own)
+ABSGRAD_SIGNATURES = {
+    "gsr_absgrad_workspace_bytes": (_i32, [_i32, C.POINTER(_sz)]),                       # P bytes
+    "gsr_absgrad_backward": (_i32, [_p, _i32, _i32, _i32, C.c_int64,                     # stream P W H R
+                                    _p, _p,                                              # bg dL_dcolor
+                                    _p, _sz, _p, _sz, _p, _sz, _p, _sz,                  # geom binning img ws (+bytes)
+                                    _i32,                                                # accumulate
+                                    _p, _p]),                                            # absgrad signed_sum
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -237,7 +247,8 @@ def load() -> C.CDLL:
         except OSError as e:
             raise GsrError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES, **SEQUENCE_SIGNATURES, **ROWS_SIGNATURES, **DENSITY_SIGNATURES,
-                                   **MCMC_SIGNATURES, **DEPTH_SIGNATURES, **FEATURES_SIGNATURES, **POSE_SIGNATURES, **CONTRIB_SIGNATURES}.items():
+                                   **MCMC_SIGNATURES, **DEPTH_SIGNATURES, **FEATURES_SIGNATURES, **POSE_SIGNATURES, **CONTRIB_SIGNATURES,
+                                   **ABSGRAD_SIGNATURES}.items():
             fn = getattr(lib, name)       # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

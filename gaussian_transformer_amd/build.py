@@ -60,6 +60,8 @@ SOURCES = {
     # as depth_maps.hip, whose forward walk it restates with an integer reduction per entry (include/gsr_contrib.h): FMA contraction as
     # there, so the weights are depth_fwd_kernel's bits; its atomics are integer ones, so no float-atomic flag
     "contrib_stats.hip": ["-fno-slp-vectorize"],
+    # as depth_maps.hip, whose reverse walk it restates for the colour loss with |.| per (pixel, Gaussian) term (include/gsr_absgrad.h)
+    "absgrad.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result", "-fno-gpu-rdc"]
 

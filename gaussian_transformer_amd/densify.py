@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .model import GaussianParams, inverse_sigmoid
+from .model import GaussianParams, absgrad_rows, inverse_sigmoid
 
 GROUPS = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")          # order of training_setup :155-162
 _ATTR = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity", "scaling": "_scaling",
@@ -202,10 +202,13 @@ class DensityController:
         self._remap(lambda n, p: tensor, lambda n, m: torch.zeros_like(tensor), only=name)
 
     # ---- statistics (train.py:113-116) ----
-    def record(self, viewspace_points: torch.Tensor, visibility: torch.Tensor, radii: torch.Tensor) -> None:
+    def record(self, viewspace_points: torch.Tensor, visibility: torch.Tensor, radii: torch.Tensor, absgrad=None) -> None:
+        """absgrad: a rasterizer.AbsGrad or a [P,2] tensor; its rows take the place of viewspace_points.grad[:, :2] in the norm
+        (visibility, denom and max_radii2D as before).  AbsGS and gsplat raise densify_grad_threshold with it (0.0002 -> about
+        0.0008); the default stays."""
         m = self.model
         m.max_radii2D[visibility] = torch.max(m.max_radii2D[visibility], radii[visibility].to(m.max_radii2D.dtype))
-        m.add_densification_stats(viewspace_points, visibility)
+        m.add_densification_stats(viewspace_points, visibility, absgrad=absgrad)
 
     # ---- densification ----
     def _selected(self, grads: torch.Tensor, threshold: float, extent: float, large: bool) -> torch.Tensor:
@@ -268,12 +271,12 @@ class DensityController:
 
     # ---- the schedule of train.py:69-73, 113-123 ----
     def after_backward(self, iteration: int, viewspace_points: torch.Tensor, visibility: torch.Tensor, radii: torch.Tensor,
-                       extent: float, white_background: bool = False, generator: Optional[torch.Generator] = None):
-        """Call after loss.backward() and before optimizer.step(), with torch.no_grad()."""
+                       extent: float, white_background: bool = False, generator: Optional[torch.Generator] = None, absgrad=None):
+        """Call after loss.backward() and before optimizer.step(), with torch.no_grad().  absgrad: as record()."""
         o = self.opt
         out = None
         if iteration < o.densify_until_iter:
-            self.record(viewspace_points, visibility, radii)
+            self.record(viewspace_points, visibility, radii, absgrad=absgrad)
             if iteration > o.densify_from_iter and iteration % o.densification_interval == 0:
                 size_threshold = 20 if iteration > o.opacity_reset_interval else None
                 out = self.densify_and_prune(o.densify_grad_threshold, 0.005, extent, size_threshold, generator=generator)
@@ -355,11 +358,12 @@ class FusedDensityController(_FusedGroups, DensityController):
         self._counts = None            # pinned host words {n_clone, n_split, n_pruned, P_new}
         self._kept = {}                # _workspace()
 
-    def record(self, viewspace_points: torch.Tensor, visibility: Optional[torch.Tensor], radii: torch.Tensor) -> None:
+    def record(self, viewspace_points: torch.Tensor, visibility: Optional[torch.Tensor], radii: torch.Tensor, absgrad=None) -> None:
         """train.py:113-116 in one launch.  viewspace_points.grad is taken as it comes: [P, >= 2] float32 with unit column
-        stride and any row stride (a view into a gradient arena).  visibility None: radii > 0."""
+        stride and any row stride (a view into a gradient arena).  visibility None: radii > 0.  absgrad: a rasterizer.AbsGrad or a
+        [P,2] tensor whose rows take the place of viewspace_points.grad (which is then not looked at), as DensityController.record."""
         m = self.model
-        grad = viewspace_points.grad
+        grad = viewspace_points.grad if absgrad is None else absgrad_rows(absgrad, m._xyz.shape[0])
         if grad is None:
             raise _lib.GsrError("FusedDensityController.record: viewspace_points has no gradient")
         if grad.device.type != "cuda":

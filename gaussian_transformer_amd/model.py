@@ -17,6 +17,15 @@ def inverse_sigmoid(x: torch.Tensor) -> torch.Tensor:     # utils/general_utils.
     return torch.log(x / (1 - x))
 
 
+def absgrad_rows(absgrad, P: int) -> torch.Tensor:
+    """The [P, 2] rows of an `absgrad=` argument of the density statistics: a rasterizer.AbsGrad's buffer, or the tensor itself."""
+    rows = absgrad if isinstance(absgrad, torch.Tensor) else getattr(absgrad, "grad", None)
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[0] != P or rows.shape[1] < 2:
+        got = tuple(rows.shape) if isinstance(rows, torch.Tensor) else type(absgrad).__name__
+        raise ValueError(f"absgrad must be a rasterizer.AbsGrad or a [{P}, 2] tensor, got {got}")
+    return rows
+
+
 class GaussianParams:
     def __init__(self, sh_degree: int):
         self.max_sh_degree = sh_degree
@@ -123,6 +132,10 @@ class GaussianParams:
         S = L @ L.transpose(1, 2)
         return torch.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], dim=1)
 
-    def add_densification_stats(self, viewspace_point_tensor, update_filter):
-        self.xyz_gradient_accum[update_filter] += torch.norm(viewspace_point_tensor.grad[update_filter, :2], dim=-1, keepdim=True)
+    def add_densification_stats(self, viewspace_point_tensor, update_filter, absgrad=None):
+        """absgrad: a rasterizer.AbsGrad or a [P,2] tensor of per-pixel absolute sums (include/gsr_absgrad.h); its rows then take
+        the place of viewspace_point_tensor.grad[:, :2] in the norm.  AbsGS and gsplat raise densify_grad_threshold with it
+        (0.0002 -> about 0.0008)."""
+        rows = viewspace_point_tensor.grad if absgrad is None else absgrad_rows(absgrad, self._xyz.shape[0])
+        self.xyz_gradient_accum[update_filter] += torch.norm(rows[update_filter, :2], dim=-1, keepdim=True)
         self.denom[update_filter] += 1

@@ -264,6 +264,8 @@ class HipBackend:
                 ptr(g_sh_rest))
             del ann
             _lib.check(rc, "gsr_backward")
+            if _absgrad_buf is not None:       # collect_absgrad: this pass's sums of |dL/dmeans2D| per pixel, from the same dL_dpix and workspaces
+                _absgrad_buf._add_view(dev, stream, P, W, H, int(num_rendered), bg, dL, geom, binning, img)
         out = (g_means3D, g_means2D, g_sh, g_colors, g_opacity, g_scales, g_rots, g_cov3D)
         if shs_rest is not None:
             out = out + (g_sh_rest,)
@@ -513,6 +515,63 @@ class collect_contribution:
     def __exit__(self, *exc):
         global _contrib_stats
         _contrib_stats = self.prev
+        return False
+
+
+_absgrad_buf = None     # the AbsGrad every colour reverse pass adds its view to (collect_absgrad), or None
+
+
+class AbsGrad:
+    """Per-Gaussian sums of |dL/dmeans2D| over the pixels of many reverse passes (include/gsr_absgrad.h): `grad` is float32 [P,2] on
+    `device`, zeroed; `views` counts the reverse passes added.  The absolute value is taken per (pixel, Gaussian) pair, so a splat
+    whose per-pixel gradients cancel in viewspace_points.grad still shows here (AbsGS; gsplat's absgrad).  Only the colour image's
+    loss enters: depth, alpha and feature-map losses of the same graph add nothing.  Hand it to DensityController.record,
+    after_backward or FusedDensityController.record as `absgrad=`; AbsGS and gsplat raise densify_grad_threshold with it
+    (0.0002 -> about 0.0008), since the sums are larger than the signed ones."""
+
+    def __init__(self, P: int, device):
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.P, self.device = int(P), dev
+        self.grad = torch.zeros((self.P, 2), dtype=torch.float32, device=dev)
+        self.views = 0
+
+    def zero_(self) -> "AbsGrad":
+        self.grad.zero_()
+        self.views = 0
+        return self
+
+    def _add_view(self, dev, stream, P, W, H, num_rendered, bg, dL_dpix, geom, binning, img) -> None:
+        if P != self.P or dev != self.device:
+            raise _lib.GsrError(f"collect_absgrad: the collector holds {self.P} Gaussians on {self.device}, "
+                                f"the render has {P} on {dev}")
+        ws = _lib.workspace("gsr_absgrad_workspace_bytes", dev, P)
+        _lib.call("gsr_absgrad_backward", stream, P, W, H, num_rendered, ptr(bg), ptr(dL_dpix), ptr(geom), geom.numel(),
+                  ptr(binning), binning.numel(), ptr(img), img.numel(), ptr(ws), ws.numel(), 1, ptr(self.grad), None)
+        self.views += 1
+
+
+class collect_absgrad:
+    """Context manager: while active, every colour reverse pass of the native backend (HipBackend.backward: GaussianRasterizer with or
+    without depth=, features= or a differentiable camera, render, render_fused, render_rows -- each camera's pass adds its view) is
+    followed, on the same stream, by one gsr_absgrad_backward(accumulate = 1) of that pass's dL_dpix and workspaces into `buf`.  It
+    must be active when backward() runs, not (only) around the forward call.  A render of another P or on another device raises
+    GsrError, as does entering a second collector inside one.  Outside it nothing new runs."""
+
+    def __init__(self, buf: AbsGrad):
+        self.buf = buf
+
+    def __enter__(self):
+        global _absgrad_buf
+        if _absgrad_buf is not None:
+            raise _lib.GsrError("collect_absgrad: a collector is active already (collectors do not nest)")
+        _absgrad_buf = self.buf
+        return self.buf
+
+    def __exit__(self, *exc):
+        global _absgrad_buf
+        _absgrad_buf = None
         return False
 
 

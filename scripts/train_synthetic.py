@@ -5,13 +5,17 @@
 set starts from a perturbed, thinned copy.  Informational (bench.py is the headline metric).
 
     python scripts/train_synthetic.py [--iters 600] [--P 20000] [--size 256] [--density torch|hip|mcmc|mcmc_hip] [--cap N] [--adam hip|hip_sparse]
-                                      [--prune-contribution ITER:THRESHOLD]
+                                      [--prune-contribution ITER:THRESHOLD] [--absgrad] [--densify-grad-threshold X]
 
 --density mcmc / mcmc_hip: MCMC density control (densify.MCMCController / FusedMCMCController, include/gsr_mcmc.h) with a budget of
 --cap Gaussians: regularisers before the step, position noise after it, relocation and growth every `densify_every` iterations.
 --prune-contribution ITER:THRESHOLD: after iteration ITER the blend weights of every training camera are collected under no_grad
 (rasterizer.collect_contribution, include/gsr_contrib.h) and the Gaussians whose largest weight stays below THRESHOLD are pruned
 (DensityController.prune_by_max_weight); the record holds the Gaussians and the PSNR before and after.
+--absgrad: the densification statistics are fed with the per-pixel absolute sums of dL/dmeans2D (rasterizer.collect_absgrad around
+loss.backward(), include/gsr_absgrad.h) in place of viewspace_points.grad; --densify-grad-threshold X sets the threshold they are held
+to (default: OptimizationParams' 0.0002; AbsGS and gsplat use about 0.0008 with absgrad).  Not for mcmc / mcmc_hip, whose rule reads no
+statistics.
 """
 import argparse, json, math, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +28,7 @@ from gaussian_transformer_amd.densify import (DensityController, FusedDensityCon
                                               OptimizationParams)
 from gaussian_transformer_amd.loss import fused_l1_ssim_loss, psnr
 from gaussian_transformer_amd.model import GaussianParams
-from gaussian_transformer_amd.rasterizer import ContributionStats, collect_contribution
+from gaussian_transformer_amd.rasterizer import AbsGrad, ContributionStats, collect_absgrad, collect_contribution
 from gaussian_transformer_amd.render import PipelineParams, TorchCamera, render_fused
 
 
@@ -32,7 +36,7 @@ DEFAULT_CAP = 26619      # the count a --density hip run at the defaults ends at
 
 
 def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_every=100, log=None, density="torch", adam="hip", cap=None,
-        prune_contribution=None):
+        prune_contribution=None, absgrad=False, densify_grad_threshold=None):
     dev = torch.device("cuda", 0)
     sc = synth.make_scene(P=P, width=size, height=size, sh_degree=1, s0=0.03, seed=seed, zmin=3.0, zmax=6.0)
     truth = GaussianParams.from_synthetic(sc, dev, requires_grad=False)
@@ -54,6 +58,8 @@ def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_
     model = GaussianParams.from_synthetic(sc0, dev)
     opt = OptimizationParams(densify_from_iter=densify_from, densification_interval=densify_every, opacity_reset_interval=10 ** 9,
                              densify_until_iter=iters)
+    if densify_grad_threshold is not None:
+        opt.densify_grad_threshold = float(densify_grad_threshold)
     mcmc = density in ("mcmc", "mcmc_hip")
     if mcmc:
         params = MCMCParams(cap_max=cap if cap is not None else DEFAULT_CAP, refine_start=densify_from, refine_every=densify_every, refine_stop=iters)
@@ -76,9 +82,16 @@ def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_
         k = int(rng.integers(ncam))
         pkg = render_fused(cams[k], model, pipe, bg)
         loss = fused_l1_ssim_loss(pkg["render"], targets[k])
-        loss.backward()
+        if absgrad and not mcmc:
+            buf = AbsGrad(int(model._xyz.shape[0]), dev)           # this view's sums (the set's size changes at a densification)
+            with collect_absgrad(buf):
+                loss.backward()
+            stats_kw = {"absgrad": buf}
+        else:
+            loss.backward()
+            stats_kw = {}
         with torch.no_grad():
-            ev = ctl.after_backward(it, pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"], extent=3.0, generator=gen)
+            ev = ctl.after_backward(it, pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"], extent=3.0, generator=gen, **stats_kw)
             if mcmc:
                 ev = None                  # the two regularisation terms (device tensors): not an event, and reading them would wait
             if adam == "hip_sparse":       # rows of Gaussians outside this view stand still (include/gsr_optim.h); a no-op right after a densification
@@ -108,7 +121,7 @@ def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     loss1, psnr1 = evaluate()
-    return {"density": density, "adam": adam, "iters": iters, "seconds": round(dt, 2), "it_per_s": round(iters / dt, 1), "P_start": len(keep), "P_end": int(model._xyz.shape[0]),
+    return {"density": density, "adam": adam, "absgrad": bool(absgrad and not mcmc), "densify_grad_threshold": opt.densify_grad_threshold, "iters": iters, "seconds": round(dt, 2), "it_per_s": round(iters / dt, 1), "P_start": len(keep), "P_end": int(model._xyz.shape[0]),
             "loss_first": round(loss0, 5), "loss_last": round(loss1, 5), "psnr_first": round(psnr0, 2), "psnr": round(psnr1, 2),
             "prune_contribution": pruned, "history": hist}
 
@@ -126,11 +139,13 @@ if __name__ == "__main__":
                     help="hip = HipAdam over all rows; hip_sparse = HipSparseAdam with the view's radii as visibility")
     ap.add_argument("--prune-contribution", default=None, metavar="ITER:THRESHOLD",
                     help="after iteration ITER, prune the Gaussians whose largest blend weight over all training cameras is below THRESHOLD")
+    ap.add_argument("--absgrad", action="store_true", help="densification statistics from the per-pixel absolute sums of dL/dmeans2D")
+    ap.add_argument("--densify-grad-threshold", type=float, default=None, help="OptimizationParams.densify_grad_threshold (default 0.0002; about 0.0008 with --absgrad)")
     a = ap.parse_args()
     prune = None
     if a.prune_contribution:
         at, thr = a.prune_contribution.split(":")
         prune = (int(at), float(thr))
-    out = run(a.iters, a.P, a.size, density=a.density, adam=a.adam, cap=a.cap, prune_contribution=prune, log=lambda r: print(json.dumps(r), flush=True))
+    out = run(a.iters, a.P, a.size, density=a.density, adam=a.adam, cap=a.cap, prune_contribution=prune, absgrad=a.absgrad, densify_grad_threshold=a.densify_grad_threshold, log=lambda r: print(json.dumps(r), flush=True))
     out.pop("history")
     print(json.dumps(out))
