@@ -220,6 +220,18 @@ ABSGRAD_SIGNATURES = {
                                     _p, _p]),                                            # absgrad signed_sum
 }
 
+# include/gsr_normals.h (likewise a table of its own)
+NORMAL_TILE_X, NORMAL_TILE_Y = 32, 8   # GSR_NORMAL_TILE_X, GSR_NORMAL_TILE_Y: the loss kernels' tile
+NORMALS_SIGNATURES = {
+    "gsr_gaussian_normals_forward": (_i32, [_p, _i32, _p, _p, _p, _p, _p, _p]),          # stream P means3D scales rotations view out_normals out_axis
+    "gsr_gaussian_normals_backward": (_i32, [_p, _i32, _p, _p, _p, _p, _p]),             # stream P rotations view axis dL_dnormals dL_drots
+    "gsr_normal_loss_workspace": (_i32, [_i32, _i32, C.POINTER(_sz)]),                   # H W bytes
+    "gsr_normal_loss_forward": (_i32, [_p, _i32, _i32, _f, _f, _f, _p, _p, _p,           # stream H W tanfovx tanfovy alpha_min depth alpha normals
+                                       _p, _p, _p, _sz]),                                # out2 out_surf ws ws_bytes
+    "gsr_normal_loss_backward": (_i32, [_p, _i32, _i32, _f, _f, _f, _p, _p, _p,          # stream H W tanfovx tanfovy alpha_min depth alpha normals
+                                        _p, _p, _p, _p]),                                # grad_loss dL_ddepth dL_dalpha dL_dnormals
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -248,7 +260,7 @@ def load() -> C.CDLL:
             raise GsrError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in {**SIGNATURES, **CHAMFER_SIGNATURES, **SEQUENCE_SIGNATURES, **ROWS_SIGNATURES, **DENSITY_SIGNATURES,
                                    **MCMC_SIGNATURES, **DEPTH_SIGNATURES, **FEATURES_SIGNATURES, **POSE_SIGNATURES, **CONTRIB_SIGNATURES,
-                                   **ABSGRAD_SIGNATURES}.items():
+                                   **ABSGRAD_SIGNATURES, **NORMALS_SIGNATURES}.items():
             fn = getattr(lib, name)       # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

@@ -62,6 +62,8 @@ SOURCES = {
     "contrib_stats.hip": ["-fno-slp-vectorize"],
     # as depth_maps.hip, whose reverse walk it restates for the colour loss with |.| per (pixel, Gaussian) term (include/gsr_absgrad.h)
     "absgrad.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],
+    # as pergauss_bwd.hip: the argmin of the scales and the sign of n_v . p_v round as written (include/gsr_normals.h)
+    "normals.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result", "-fno-gpu-rdc"]
 

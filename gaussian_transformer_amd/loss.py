@@ -106,6 +106,100 @@ def fused_l1_ssim_loss(image: torch.Tensor, gt_image: torch.Tensor, lambda_dssim
     return _FusedL1SSIM.apply(image, gt_image, lambda_dssim)
 
 
+# ---------------------------------------------------------------- depth-normal consistency ----------------------------------------------------------------
+# 2DGS's normal consistency term on the maps of one render (include/gsr_normals.h): the normals the depth map's finite differences
+# imply against the rendered normal map, one HIP kernel per direction.
+
+NORMAL_ALPHA_MIN = 0.05
+
+
+def _normal_maps(who: str, depth, alpha, alpha_min, *normals):
+    """depth and alpha as [H,W] (a leading 1 is dropped: the renderer's maps are [1,H,W]), checked together with the [3,H,W] normal
+    map where one is given: types, dtypes and shapes first, devices last (a CPU test can check every message)."""
+    named = (("depth", depth), ("alpha", alpha)) + tuple(("normals", n) for n in normals)
+    for name, t in named:
+        _lib.require_tensor(who, name, t)
+    d = depth[0] if depth.dim() == 3 and depth.shape[0] == 1 else depth
+    a = alpha[0] if alpha.dim() == 3 and alpha.shape[0] == 1 else alpha
+    if d.dim() != 2 or d.shape[0] < 1 or d.shape[1] < 1:
+        raise _lib.GsrError(f"{who}: depth must have shape [H,W] or [1,H,W], got {tuple(depth.shape)}")
+    if a.shape != d.shape:
+        raise _lib.GsrError(f"{who}: alpha must have depth's shape {tuple(d.shape)} (or a leading 1), got {tuple(alpha.shape)}")
+    for n in normals:
+        if tuple(n.shape) != (3,) + tuple(d.shape):
+            raise _lib.GsrError(f"{who}: normals must have shape {(3,) + tuple(d.shape)}, got {tuple(n.shape)}")
+    if not float(alpha_min) > 0.0:
+        raise _lib.GsrError(f"{who}: alpha_min must be positive (D = depth / alpha is formed where alpha >= alpha_min), got {alpha_min}")
+    for name, t in named:
+        _lib.require_hip(who, name, t)
+        if t.device != depth.device:
+            raise _lib.GsrError(f"{who}: all maps must be on one device: {name} is on {t.device}, depth on {depth.device}")
+    return d, a
+
+
+class _NormalConsistency(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, alpha, normals, tanfovx, tanfovy, alpha_min):
+        dev = depth.device
+        d, a, n = depth.contiguous(), alpha.contiguous(), normals.contiguous()
+        H, W = int(d.shape[0]), int(d.shape[1])
+        with torch.cuda.device(dev):
+            ws = _lib.workspace("gsr_normal_loss_workspace", dev, H, W)
+            out = torch.empty((2,), dtype=torch.float32, device=dev)
+            _lib.call("gsr_normal_loss_forward", _lib.stream(dev), H, W, tanfovx, tanfovy, alpha_min, _lib.ptr(d), _lib.ptr(a), _lib.ptr(n),
+                      _lib.ptr(out), None, _lib.ptr(ws), ws.numel())
+        ctx.save_for_backward(d, a, n)
+        ctx.cfg = (tanfovx, tanfovy, alpha_min)
+        frac = out[1]
+        ctx.mark_non_differentiable(frac)
+        return out[0], frac
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_frac):
+        d, a, n = ctx.saved_tensors
+        dev = d.device
+        H, W = int(d.shape[0]), int(d.shape[1])
+        need = ctx.needs_input_grad
+        with torch.cuda.device(dev):
+            g = grad_loss.to(device=dev, dtype=torch.float32).contiguous().reshape(1)
+            gd = torch.empty_like(d) if need[0] else None
+            ga = torch.empty_like(a) if need[1] else None
+            gn = torch.empty_like(n) if need[2] else None
+            _lib.call("gsr_normal_loss_backward", _lib.stream(dev), H, W, *ctx.cfg, _lib.ptr(d), _lib.ptr(a), _lib.ptr(n), _lib.ptr(g),
+                      _lib.ptr(gd), _lib.ptr(ga), _lib.ptr(gn))
+        return gd, ga, gn, None, None, None
+
+
+def normal_consistency_loss(depth: torch.Tensor, alpha: torch.Tensor, normals: torch.Tensor, tanfovx: float, tanfovy: float,
+                            alpha_min: float = NORMAL_ALPHA_MIN) -> torch.Tensor:
+    """mean over the image of A (1 - N . n~) at the valid pixels (include/gsr_normals.h): N = `normals` [3,H,W], the rendered normal map
+    (render(normals=True)); n~ = the unit normal of the surface the depth map implies, from central differences of the back-projected
+    points of D = depth / alpha; A = alpha taken as a constant.  depth, alpha: [H,W] or [1,H,W], the "expected" maps of
+    render(depth="expected").  A pixel is valid when it is interior and it and its four neighbours have alpha >= alpha_min.
+    Gradients flow to all three maps.  The result carries `.valid_fraction`, a detached scalar tensor.  No CPU fallback."""
+    d, a = _normal_maps("normal_consistency_loss", depth, alpha, alpha_min, normals)
+    loss, frac = _NormalConsistency.apply(d, a, normals, float(tanfovx), float(tanfovy), float(alpha_min))
+    loss.valid_fraction = frac
+    return loss
+
+
+def surface_normals(depth: torch.Tensor, alpha: torch.Tensor, tanfovx: float, tanfovy: float, alpha_min: float = NORMAL_ALPHA_MIN) -> torch.Tensor:
+    """[3,H,W]: the unit normals the depth map implies, n~ of normal_consistency_loss, exact zeros at invalid pixels.  No gradients:
+    for viewing and for tests."""
+    d, a = _normal_maps("surface_normals", depth, alpha, alpha_min)
+    dev = d.device
+    with torch.no_grad(), torch.cuda.device(dev):
+        d, a = d.detach().contiguous(), a.detach().contiguous()
+        H, W = int(d.shape[0]), int(d.shape[1])
+        surf = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+        ws = _lib.workspace("gsr_normal_loss_workspace", dev, H, W)
+        out = torch.empty((2,), dtype=torch.float32, device=dev)
+        zero_n = torch.zeros((3, H, W), dtype=torch.float32, device=dev)      # the loss against it lands in `out` and is dropped
+        _lib.call("gsr_normal_loss_forward", _lib.stream(dev), H, W, float(tanfovx), float(tanfovy), float(alpha_min), _lib.ptr(d), _lib.ptr(a),
+                  _lib.ptr(zero_n), _lib.ptr(out), _lib.ptr(surf), _lib.ptr(ws), ws.numel())
+    return surf
+
+
 # ---------------------------------------------------------------- B views in one call ----------------------------------------------------------------
 # The image loss of the stacked trainer's step (train_stacked_transformer.py:203-222): B renders and B targets, each sanitised with
 # clamp(nan_to_num(.), 0, 1), L1Loss and 1 - ssim over the whole batch, weighted 5.0/B * 0.1 and 0.2/B * 0.1.  One HIP kernel per

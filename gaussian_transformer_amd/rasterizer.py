@@ -396,6 +396,29 @@ class HipBackend:
             _lib.call("gsr_composited_mask", _lib.stream(dev), P, ptr(geom), geom.numel(), ptr(out))
         return out.bool()
 
+    def gaussian_normals_forward(self, viewmatrix, means3D, scales, rotations):
+        """(normals [P,3], axis [P] int32): every Gaussian's shortest axis in view space, facing the camera, and the code of the two
+        decisions behind it (include/gsr_normals.h)."""
+        dev = means3D.device
+        _lib.require_hip("gaussian_normals", "means3D", means3D)
+        P = int(means3D.shape[0])
+        normals = torch.empty((P, 3), dtype=torch.float32, device=dev)
+        axis = torch.empty((P,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call("gsr_gaussian_normals_forward", _lib.stream(dev), P, ptr(means3D), ptr(scales), ptr(rotations), ptr(viewmatrix),
+                      ptr(normals), ptr(axis))
+        return normals, axis
+
+    def gaussian_normals_backward(self, viewmatrix, rotations, axis, dL_dnormals):
+        """dL/drotations [P,4] of gaussian_normals_forward's normals; scales and means receive none (include/gsr_normals.h)."""
+        dev = rotations.device
+        P = int(rotations.shape[0])
+        g_rots = torch.empty((P, 4), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call("gsr_gaussian_normals_backward", _lib.stream(dev), P, ptr(rotations), ptr(viewmatrix), ptr(axis),
+                      ptr(_f32c(dL_dnormals, "grad of the normals", dev)), ptr(g_rots))
+        return g_rots
+
     def mark_visible(self, positions, viewmatrix, projmatrix):
         dev = positions.device
         if dev.type != "cuda":
@@ -907,6 +930,47 @@ def rasterize_gaussians_fused(means3D, means2D, features_dc, features_rest, opac
     viewmatrix, projmatrix and campos are constants here even when they require grad (include/gsr_pose.h has no raw_params form)."""
     return _RasterizeGaussiansFused.apply(means3D, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
                                           rotation_raw, raster_settings)
+
+
+class _GaussianNormals(torch.autograd.Function):
+    """normals [P,3] of (means3D, scales, rotations) under a view matrix (include/gsr_normals.h).  Only `rotations` receives a gradient:
+    the choice of the axis and the flip towards the camera are piecewise constant in the scales and the means."""
+
+    @staticmethod
+    def forward(ctx, means3D, scales, rotations, viewmatrix):
+        be = get_backend()
+        if not hasattr(be, "gaussian_normals_forward"):
+            raise _lib.GsrError(f"the {getattr(be, 'name', type(be).__name__)} backend computes no Gaussian normals")
+        dev = means3D.device
+        m, s, r = _f32c(means3D, "means3D", dev), _f32c(scales, "scales", dev), _f32c(rotations, "rotations", dev)
+        vm = _f32c(viewmatrix, "viewmatrix", dev)
+        normals, axis = be.gaussian_normals_forward(vm, m, s, r)
+        ctx.save_for_backward(r, vm, axis)
+        return normals
+
+    @staticmethod
+    def backward(ctx, grad_normals):
+        r, vm, axis = ctx.saved_tensors
+        g = get_backend().gaussian_normals_backward(vm, r, axis, grad_normals) if ctx.needs_input_grad[2] else None
+        return None, None, g, None
+
+
+def gaussian_normals(means3D, scales, rotations, raster_settings) -> torch.Tensor:
+    """[P,3] float32: per Gaussian, the axis of its smallest scale (ties: the lowest index) as column of the rotation the covariance is
+    built from -- the quaternion as given, not normalised --, turned into the view space of raster_settings.viewmatrix and negated
+    where it points away from the camera (include/gsr_normals.h).  Passed as `features=` to GaussianRasterizer.forward, or asked for
+    with render(normals=True), it blends into the normal map.  Only `rotations` receives a gradient; the viewmatrix is read detached."""
+    who = "gaussian_normals"
+    for name, t, cols in (("means3D", means3D, 3), ("scales", scales, 3), ("rotations", rotations, 4)):
+        _lib.require_tensor(who, name, t)
+        if t.dim() != 2 or t.shape[1] != cols or t.shape[0] != means3D.shape[0]:
+            raise _lib.GsrError(f"{who}: {name} must have dimensions (num_points, {cols}), got {tuple(t.shape)} "
+                                f"for {int(means3D.shape[0]) if means3D.dim() else 0} points")
+    vm = raster_settings.viewmatrix
+    _lib.require_tensor(who, "viewmatrix", vm)
+    if vm.numel() != 16:
+        raise _lib.GsrError(f"{who}: viewmatrix must hold 16 values, got shape {tuple(vm.shape)}")
+    return _GaussianNormals.apply(means3D, scales, rotations, vm.detach())
 
 
 class GaussianRasterizer(nn.Module):

@@ -12,8 +12,8 @@ from dataclasses import dataclass
 
 import torch
 
-from ._lib import GsrError
-from .rasterizer import GaussianRasterizer, camera_settings, rasterize_gaussians_fused
+from ._lib import FEATURES_MAX_C, GsrError
+from .rasterizer import GaussianRasterizer, camera_settings, gaussian_normals, rasterize_gaussians_fused
 
 
 @dataclass
@@ -46,11 +46,17 @@ def eval_sh_torch(deg: int, sh: torch.Tensor, dirs: torch.Tensor) -> torch.Tenso
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0, override_color=None, depth=None,
-           features=None):
+           features=None, normals=False):
     """viewpoint_camera: anything with image_height/width, FoVx/FoVy, world_view_transform,
     full_proj_transform, camera_center (torch tensors on the device).  pc: GaussianParams-like.
     depth: None (the reference's dict), or "expected" / "inverse": the dict also holds "depth" and "alpha", [1,H,W] each
-    (GaussianRasterizer.forward).  features: None, or [P,C] float32: the dict also holds "features", the [C,H,W] map of them."""
+    (GaussianRasterizer.forward).  features: None, or [P,C] float32: the dict also holds "features", the [C,H,W] map of them.
+    normals: the dict also holds "normals" [3,H,W], the map of rasterizer.gaussian_normals(...) -- sum n_g alpha T, not normalised, in
+    view space, facing the camera; it travels as three more columns of the feature route (C + 3 <= 64), so only the rotations receive
+    a gradient through the normals themselves and camera tensors that require grad are refused, as for features."""
+    if normals and pipe.compute_cov3D_python:
+        raise GsrError("render: normals=True with pipe.compute_cov3D_python: the normals are formed from scales and rotations, and "
+                       "that path hands the rasterizer a precomputed covariance only")
     xyz = pc.get_xyz
     screenspace_points = torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True, device=xyz.device) + 0
     try:
@@ -76,13 +82,27 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
             shs = pc.get_features
     else:
         colors_precomp = override_color
+    n_user = 0 if features is None else int(features.shape[1]) if isinstance(features, torch.Tensor) and features.dim() == 2 else None
+    if normals:
+        if n_user is None:
+            raise GsrError(f"render: features must be a [P,C] tensor to travel with normals=True, got {type(features).__name__}")
+        if n_user + 3 > FEATURES_MAX_C:
+            raise GsrError(f"render: normals=True takes 3 of the {FEATURES_MAX_C} feature channels: features may have at most "
+                           f"{FEATURES_MAX_C - 3} columns beside it, got {n_user}")
+        n_g = gaussian_normals(means3D, scales, rotations, raster_settings)
+        features = n_g if features is None else torch.cat((features, n_g), dim=1)
     if features is not None:
         extra = {} if depth is None else {"depth": depth}
         rendered_image, radii, *maps = rasterizer(
             means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity, scales=scales,
             rotations=rotations, cov3D_precomp=cov3D_precomp, features=features, **extra)
-        out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
-               "features": maps[-1]}
+        out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
+        if normals:
+            out["normals"] = maps[-1][n_user:]
+            if n_user:
+                out["features"] = maps[-1][:n_user]
+        else:
+            out["features"] = maps[-1]
         if depth is not None:
             out["depth"], out["alpha"] = maps[0], maps[1]
         return out
@@ -97,12 +117,15 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
     return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
 
 
-def render_fused(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0, features=None):
+def render_fused(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0, features=None, normals=False):
     """Same result dict as render(), through the fused-step entry point: the raw parameters
     of the model go straight to the kernels -- no exp / sigmoid / normalize / cat tensors, no autograd nodes
     for them.  Only the default configuration of render() (SH colours, scale/rotation covariance) is
     covered; use render() for override_color / convert_SHs_python / compute_cov3D_python, and for feature maps:
-    `features` is refused here (include/gsr_features.h has no raw_params form)."""
+    `features` is refused here (include/gsr_features.h has no raw_params form), and `normals`, which travel that route, with it."""
+    if normals:
+        raise GsrError("render_fused: no normal map on the raw-parameter path (the normals travel as feature channels, and "
+                       "include/gsr_features.h has no raw_params form): use render(normals=True)")
     if features is not None:
         raise GsrError("render_fused: no feature maps on the raw-parameter path (include/gsr_features.h has no raw_params form): "
                        "use render(features=...)")

@@ -6,6 +6,7 @@ set starts from a perturbed, thinned copy.  Informational (bench.py is the headl
 
     python scripts/train_synthetic.py [--iters 600] [--P 20000] [--size 256] [--density torch|hip|mcmc|mcmc_hip] [--cap N] [--adam hip|hip_sparse]
                                       [--prune-contribution ITER:THRESHOLD] [--absgrad] [--densify-grad-threshold X]
+                                      [--lambda-normal X [--normal-from ITER]]
 
 --density mcmc / mcmc_hip: MCMC density control (densify.MCMCController / FusedMCMCController, include/gsr_mcmc.h) with a budget of
 --cap Gaussians: regularisers before the step, position noise after it, relocation and growth every `densify_every` iterations.
@@ -16,6 +17,10 @@ set starts from a perturbed, thinned copy.  Informational (bench.py is the headl
 loss.backward(), include/gsr_absgrad.h) in place of viewspace_points.grad; --densify-grad-threshold X sets the threshold they are held
 to (default: OptimizationParams' 0.0002; AbsGS and gsplat use about 0.0008 with absgrad).  Not for mcmc / mcmc_hip, whose rule reads no
 statistics.
+--lambda-normal X: from iteration --normal-from on (default: a third of the run) X times 2DGS's depth-normal consistency term
+(loss.normal_consistency_loss, include/gsr_normals.h) is added to the image loss; those iterations render through render(depth="expected",
+normals=True) instead of the raw-parameter path, which has no maps.  The record holds the term's final value over the training
+cameras ("normal_term", also for a run without the flag, where nothing optimises it).
 """
 import argparse, json, math, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,17 +31,17 @@ from gaussian_transformer_amd import synth
 from gaussian_transformer_amd.camera import look_at_camera
 from gaussian_transformer_amd.densify import (DensityController, FusedDensityController, FusedMCMCController, MCMCController, MCMCParams,
                                               OptimizationParams)
-from gaussian_transformer_amd.loss import fused_l1_ssim_loss, psnr
+from gaussian_transformer_amd.loss import fused_l1_ssim_loss, normal_consistency_loss, psnr
 from gaussian_transformer_amd.model import GaussianParams
 from gaussian_transformer_amd.rasterizer import AbsGrad, ContributionStats, collect_absgrad, collect_contribution
-from gaussian_transformer_amd.render import PipelineParams, TorchCamera, render_fused
+from gaussian_transformer_amd.render import PipelineParams, TorchCamera, render, render_fused
 
 
 DEFAULT_CAP = 26619      # the count a --density hip run at the defaults ends at (profiles/density/bench.json): the same final set size
 
 
 def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_every=100, log=None, density="torch", adam="hip", cap=None,
-        prune_contribution=None, absgrad=False, densify_grad_threshold=None):
+        prune_contribution=None, absgrad=False, densify_grad_threshold=None, lambda_normal=0.0, normal_from=None):
     dev = torch.device("cuda", 0)
     sc = synth.make_scene(P=P, width=size, height=size, sh_degree=1, s0=0.03, seed=seed, zmin=3.0, zmax=6.0)
     truth = GaussianParams.from_synthetic(sc, dev, requires_grad=False)
@@ -73,6 +78,11 @@ def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_
             imgs = [render_fused(c, model, pipe, bg)["render"] for c in cams]
             return (float(np.mean([float(fused_l1_ssim_loss(i, t)) for i, t in zip(imgs, targets)])),
                     float(np.mean([float(psnr(i[None], t[None]).mean()) for i, t in zip(imgs, targets)])))
+    def normal_term(c):
+        """The consistency term of the model seen from camera c, on the maps of one render."""
+        m = render(c, model, pipe, bg, depth="expected", normals=True)
+        return m, normal_consistency_loss(m["depth"], m["alpha"], m["normals"], math.tan(c.FoVx * 0.5), math.tan(c.FoVy * 0.5))
+    normal_from = iters // 3 if normal_from is None else int(normal_from)
     loss0, psnr0 = evaluate()
     hist = []
     pruned = None
@@ -80,8 +90,12 @@ def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_
     for it in range(1, iters + 1):
         ctl.update_learning_rate(it)
         k = int(rng.integers(ncam))
-        pkg = render_fused(cams[k], model, pipe, bg)
-        loss = fused_l1_ssim_loss(pkg["render"], targets[k])
+        if lambda_normal > 0.0 and it >= normal_from:
+            pkg, term = normal_term(cams[k])
+            loss = fused_l1_ssim_loss(pkg["render"], targets[k]) + lambda_normal * term
+        else:
+            pkg = render_fused(cams[k], model, pipe, bg)
+            loss = fused_l1_ssim_loss(pkg["render"], targets[k])
         if absgrad and not mcmc:
             buf = AbsGrad(int(model._xyz.shape[0]), dev)           # this view's sums (the set's size changes at a densification)
             with collect_absgrad(buf):
@@ -121,7 +135,9 @@ def run(iters=600, P=20000, size=256, ncam=8, seed=0, densify_from=100, densify_
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     loss1, psnr1 = evaluate()
-    return {"density": density, "adam": adam, "absgrad": bool(absgrad and not mcmc), "densify_grad_threshold": opt.densify_grad_threshold, "iters": iters, "seconds": round(dt, 2), "it_per_s": round(iters / dt, 1), "P_start": len(keep), "P_end": int(model._xyz.shape[0]),
+    with torch.no_grad():
+        term1 = float(np.mean([float(normal_term(c)[1]) for c in cams]))
+    return {"lambda_normal": lambda_normal, "normal_from": normal_from, "normal_term": round(term1, 6), "density": density, "adam": adam, "absgrad": bool(absgrad and not mcmc), "densify_grad_threshold": opt.densify_grad_threshold, "iters": iters, "seconds": round(dt, 2), "it_per_s": round(iters / dt, 1), "P_start": len(keep), "P_end": int(model._xyz.shape[0]),
             "loss_first": round(loss0, 5), "loss_last": round(loss1, 5), "psnr_first": round(psnr0, 2), "psnr": round(psnr1, 2),
             "prune_contribution": pruned, "history": hist}
 
@@ -141,11 +157,14 @@ if __name__ == "__main__":
                     help="after iteration ITER, prune the Gaussians whose largest blend weight over all training cameras is below THRESHOLD")
     ap.add_argument("--absgrad", action="store_true", help="densification statistics from the per-pixel absolute sums of dL/dmeans2D")
     ap.add_argument("--densify-grad-threshold", type=float, default=None, help="OptimizationParams.densify_grad_threshold (default 0.0002; about 0.0008 with --absgrad)")
+    ap.add_argument("--lambda-normal", type=float, default=0.0, help="weight of the depth-normal consistency term (0: off; 2DGS uses 0.05)")
+    ap.add_argument("--normal-from", type=int, default=None, help="first iteration the term is added at (default: iters / 3)")
     a = ap.parse_args()
     prune = None
     if a.prune_contribution:
         at, thr = a.prune_contribution.split(":")
         prune = (int(at), float(thr))
-    out = run(a.iters, a.P, a.size, density=a.density, adam=a.adam, cap=a.cap, prune_contribution=prune, absgrad=a.absgrad, densify_grad_threshold=a.densify_grad_threshold, log=lambda r: print(json.dumps(r), flush=True))
+    out = run(a.iters, a.P, a.size, density=a.density, adam=a.adam, cap=a.cap, prune_contribution=prune, absgrad=a.absgrad, densify_grad_threshold=a.densify_grad_threshold,
+              lambda_normal=a.lambda_normal, normal_from=a.normal_from, log=lambda r: print(json.dumps(r), flush=True))
     out.pop("history")
     print(json.dumps(out))
