@@ -4,27 +4,10 @@
  *   chamfer_client <problem file>
  * The problem file is written by the Python side: int32 B N M D, then float32 x1 x2 g1 g2, the expected float32 dist1 dist2,
  * int32 idx1 idx2, float32 dx1 dx2 (float64 reference, rounded), and the float32 tolerances of dist1 dist2 dx1 dx2. */
-#define __HIP_PLATFORM_AMD__ 1
-#include <hip/hip_runtime_api.h>
 #include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include "gsr_chamfer.h"
+#include "client_common.h"
 
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %d at line %d\n", (int)e_, __LINE__); return 2; } } while (0)
-
-static void *rd(FILE *f, size_t bytes) {
-    void *p = malloc(bytes ? bytes : 1);
-    if (!p || fread(p, 1, bytes, f) != bytes) { printf("short problem file\n"); exit(3); }
-    return p;
-}
-static void *dev_copy(const void *h, size_t bytes) {
-    void *d;
-    if (hipMalloc(&d, bytes ? bytes : 1) != hipSuccess) return NULL;
-    hipMemcpy(d, h, bytes, hipMemcpyHostToDevice);
-    return d;
-}
 static int close_f(const char *what, const float *got, const float *want, const float *tol, size_t n) {
     for (size_t i = 0; i < n; i++)
         if (!(fabs((double)got[i] - (double)want[i]) <= (double)tol[i])) {
@@ -39,7 +22,7 @@ int main(int argc, char **argv) {
     FILE *f = fopen(argv[1], "rb");
     if (!f) { printf("cannot open %s\n", argv[1]); return 3; }
     int32_t hdr[4];
-    if (fread(hdr, 4, 4, f) != 4) return 3;
+    rd_into(f, hdr, sizeof hdr);
     const int32_t B = hdr[0], N = hdr[1], M = hdr[2], D = hdr[3];
     const size_t n1 = (size_t)B * N, n2 = (size_t)B * M, e1 = n1 * D, e2 = n2 * D;
     float *x1 = rd(f, e1 * 4), *x2 = rd(f, e2 * 4), *g1 = rd(f, n1 * 4), *g2 = rd(f, n2 * 4);

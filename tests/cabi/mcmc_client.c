@@ -6,35 +6,8 @@
  * float64 min_opacity, float32 gate_k gate_t scale, then float32 u [P], noise [P,3], and per group the parameter [P,w], exp_avg [P,w],
  * exp_avg_sq [P,w].  The client relocates in place (plan + apply), then adds the noise, and writes: uint32 counts[4], per group the
  * parameter and both moments after the relocation, and xyz [P,3] after the noise.  The Python side judges the numbers. */
-#define __HIP_PLATFORM_AMD__ 1
-#include <hip/hip_runtime_api.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include "gsr_mcmc.h"
-
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %d at line %d\n", (int)e_, __LINE__); return 2; } } while (0)
-#define EXPECT(call, code, what) do { int rc_ = (call); if (rc_ != (code) || ((code) != GSR_OK && strlen(gsr_last_error()) == 0)) { \
-    printf("%s: expected %d with a message, got %d (%s)\n", what, (int)(code), rc_, gsr_last_error()); return 1; } } while (0)
-
-static void *rd(FILE *f, size_t bytes) {
-    void *p = malloc(bytes ? bytes : 1);
-    if (!p || fread(p, 1, bytes, f) != bytes) { printf("short problem file\n"); exit(3); }
-    return p;
-}
-static float *dev_copy(const void *h, size_t bytes) {
-    void *d;
-    if (hipMalloc(&d, bytes ? bytes : 1) != hipSuccess) return NULL;
-    hipMemcpy(d, h, bytes, hipMemcpyHostToDevice);
-    return (float *)d;
-}
-static int dump(FILE *f, const float *d, size_t bytes) {
-    void *h = malloc(bytes ? bytes : 1);
-    if (hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) return 1;
-    const int bad = fwrite(h, 1, bytes, f) != bytes;
-    free(h);
-    return bad;
-}
+#include "client_common.h"
 
 int main(int argc, char **argv) {
     if (argc < 3) { printf("usage: mcmc_client <problem file> <result file>\n"); return 3; }
@@ -43,7 +16,7 @@ int main(int argc, char **argv) {
     int32_t hdr[7];
     float L, gate[3];
     double m;
-    if (fread(hdr, 4, 7, f) != 7 || fread(&L, 4, 1, f) != 1 || fread(&m, 8, 1, f) != 1 || fread(gate, 4, 3, f) != 3) return 3;
+    rd_into(f, hdr, sizeof hdr); rd_into(f, &L, 4); rd_into(f, &m, 8); rd_into(f, gate, sizeof gate);
     const int32_t P = hdr[0], *w = hdr + 1;
     const int32_t role[6] = {GSR_MCMC_COPY, GSR_MCMC_COPY, GSR_MCMC_COPY, GSR_MCMC_OPACITY, GSR_MCMC_SCALING, GSR_MCMC_COPY};
     if (P < 1 || w[0] != 3 || w[3] != 1 || w[4] != 3 || w[5] != 4) { printf("bad problem header\n"); return 3; }
@@ -58,22 +31,22 @@ int main(int argc, char **argv) {
     if (gsr_abi_version() != GSR_ABI_VERSION) { printf("ABI version mismatch\n"); return 1; }
 
     size_t need = 0;
-    EXPECT(gsr_mcmc_plan_workspace(P, 0, &need), GSR_OK, "workspace size");
+    EXPECT_CODE(gsr_mcmc_plan_workspace(P, 0, &need), GSR_OK, "workspace size");
     void *ws;
     uint32_t *counts;
     CK(hipMalloc(&ws, need));
     CK(hipHostMalloc((void **)&counts, 16, 0));
-    EXPECT(gsr_mcmc_plan(NULL, GSR_MCMC_RELOCATE, P, par[3], par[4], L, m, 0, 0, u, counts, ws, need), GSR_ERR_INVALID_ARGUMENT, "n_max = 0");
-    EXPECT(gsr_mcmc_plan(NULL, GSR_MCMC_RELOCATE, P, par[3], par[4], L, m, GSR_MCMC_N_MAX, 0, u, counts, ws, need - 1), GSR_ERR_WORKSPACE, "short workspace");
-    EXPECT(gsr_mcmc_plan(NULL, GSR_MCMC_RELOCATE, P, par[3], par[4], L, m, GSR_MCMC_N_MAX, 0, u, counts, ws, need), GSR_OK, "plan");
+    EXPECT_CODE(gsr_mcmc_plan(NULL, GSR_MCMC_RELOCATE, P, par[3], par[4], L, m, 0, 0, u, counts, ws, need), GSR_ERR_INVALID_ARGUMENT, "n_max = 0");
+    EXPECT_CODE(gsr_mcmc_plan(NULL, GSR_MCMC_RELOCATE, P, par[3], par[4], L, m, GSR_MCMC_N_MAX, 0, u, counts, ws, need - 1), GSR_ERR_WORKSPACE, "short workspace");
+    EXPECT_CODE(gsr_mcmc_plan(NULL, GSR_MCMC_RELOCATE, P, par[3], par[4], L, m, GSR_MCMC_N_MAX, 0, u, counts, ws, need), GSR_OK, "plan");
     gsr_mcmc_group_t g[6];
     for (int k = 0; k < 6; k++) {
         g[k].src = par[k]; g[k].src_exp_avg = m1[k]; g[k].src_exp_avg_sq = m2[k];
         g[k].dst = par[k]; g[k].dst_exp_avg = m1[k]; g[k].dst_exp_avg_sq = m2[k];
         g[k].width_floats = w[k]; g[k].role = role[k];
     }
-    EXPECT(gsr_mcmc_apply(NULL, GSR_MCMC_RELOCATE, P, 0, GSR_MCMC_MAX_GROUPS + 1, g, ws, need), GSR_ERR_INVALID_ARGUMENT, "17 groups");
-    EXPECT(gsr_mcmc_apply(NULL, GSR_MCMC_RELOCATE, P, 0, 6, g, ws, need), GSR_OK, "apply");
+    EXPECT_CODE(gsr_mcmc_apply(NULL, GSR_MCMC_RELOCATE, P, 0, GSR_MCMC_MAX_GROUPS + 1, g, ws, need), GSR_ERR_INVALID_ARGUMENT, "17 groups");
+    EXPECT_CODE(gsr_mcmc_apply(NULL, GSR_MCMC_RELOCATE, P, 0, 6, g, ws, need), GSR_OK, "apply");
     CK(hipDeviceSynchronize());
 
     FILE *out = fopen(argv[2], "wb");
@@ -83,8 +56,8 @@ int main(int argc, char **argv) {
         const size_t bytes = (size_t)P * w[k] * 4;
         bad |= dump(out, par[k], bytes) | dump(out, m1[k], bytes) | dump(out, m2[k], bytes);
     }
-    EXPECT(gsr_mcmc_noise(NULL, P, par[3], par[4], par[5] + 1, noise, par[0], gate[0], gate[1], gate[2]), GSR_ERR_INVALID_ARGUMENT, "misaligned rotation");
-    EXPECT(gsr_mcmc_noise(NULL, P, par[3], par[4], par[5], noise, par[0], gate[0], gate[1], gate[2]), GSR_OK, "noise");
+    EXPECT_CODE(gsr_mcmc_noise(NULL, P, par[3], par[4], par[5] + 1, noise, par[0], gate[0], gate[1], gate[2]), GSR_ERR_INVALID_ARGUMENT, "misaligned rotation");
+    EXPECT_CODE(gsr_mcmc_noise(NULL, P, par[3], par[4], par[5], noise, par[0], gate[0], gate[1], gate[2]), GSR_OK, "noise");
     CK(hipDeviceSynchronize());
     bad |= dump(out, par[0], (size_t)P * 12);
     if (fclose(out) || bad) { printf("could not write the results\n"); return 3; }

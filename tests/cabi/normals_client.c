@@ -9,59 +9,8 @@
  * were -- then the calls with nothing to do, then the five calls themselves.  It writes normals [P,3], axis [P] int32, dL_drots [P,4],
  * out2 [2], out_surf [3,H,W], dL_ddepth [H,W], dL_dalpha [H,W], dL_dnormals [3,H,W] of the unscaled backward call, and dL_ddepth [H,W] of
  * a call with grad_loss = 0.25 and the other two outputs NULL.  The Python side judges the numbers. */
-#define __HIP_PLATFORM_AMD__ 1
-#include <hip/hip_runtime_api.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include "gsr_normals.h"
-
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %d at line %d\n", (int)e_, __LINE__); return 2; } } while (0)
-#define PATTERN 0xA5
-
-/* every output buffer of the run, so that a refusal can be shown to have written none of them (none registered: nothing to look at) */
-static struct { const void *p; size_t bytes; } outs[8];
-static int n_outs;
-static int changed(void) {
-    for (int k = 0; k < n_outs; k++) {
-        unsigned char *h = (unsigned char *)malloc(outs[k].bytes ? outs[k].bytes : 1);
-        int bad = hipMemcpy(h, outs[k].p, outs[k].bytes, hipMemcpyDeviceToHost) != hipSuccess;      /* synchronises with the null stream */
-        for (size_t i = 0; i < outs[k].bytes && !bad; i++) bad = h[i] != PATTERN;
-        free(h);
-        if (bad) return 1;
-    }
-    return 0;
-}
-/* the call returns `code`; a refusal's text is `text` exactly, and every output still holds the pattern */
-#define EXPECT(call, code, text) do { const int rc_ = (call); const char *said_ = gsr_last_error(); \
-    if (rc_ != (code) || ((code) != GSR_OK && strcmp(said_, text) != 0)) { \
-        printf("line %d: expected %d \"%s\", got %d \"%s\"\n", __LINE__, (int)(code), text, rc_, said_); return 1; } \
-    if (changed()) { printf("line %d: an output was written\n", __LINE__); return 1; } } while (0)
-
-static void *rd(FILE *f, size_t bytes) {
-    void *p = malloc(bytes ? bytes : 1);
-    if (!p || fread(p, 1, bytes, f) != bytes) { printf("short problem file\n"); exit(3); }
-    return p;
-}
-static float *dev_copy(const void *h, size_t bytes) {
-    void *d;
-    if (hipMalloc(&d, bytes ? bytes : 1) != hipSuccess) return NULL;
-    hipMemcpy(d, h, bytes, hipMemcpyHostToDevice);
-    return (float *)d;
-}
-static void *dev_out(size_t bytes) {
-    void *d;
-    if (hipMalloc(&d, bytes) != hipSuccess || hipMemset(d, PATTERN, bytes) != hipSuccess) return NULL;
-    outs[n_outs].p = d; outs[n_outs].bytes = bytes; n_outs++;
-    return d;
-}
-static int dump(FILE *f, const void *d, size_t bytes) {
-    void *h = malloc(bytes ? bytes : 1);
-    if (hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) return 1;
-    const int bad = fwrite(h, 1, bytes, f) != bytes;
-    free(h);
-    return bad;
-}
+#include "client_common.h"
 
 struct bufs {
     int32_t P, H, W;
@@ -84,52 +33,52 @@ static int refusals(const struct bufs *b) {
 #define LB "gsr_normal_loss_backward: "
 #define AMIN "alpha_min must be positive (D = depth / alpha is formed where alpha >= alpha_min)"
 #define INV GSR_ERR_INVALID_ARGUMENT
-    EXPECT(gsr_gaussian_normals_forward(NULL, -1, b->means, b->scales, b->rots, b->view, b->out_n, b->axis), INV, GF "bad sizes");
-    EXPECT(gsr_gaussian_normals_forward(NULL, P, NULL, b->scales, b->rots, b->view, b->out_n, b->axis), INV, GF "missing input or output buffer");
-    EXPECT(gsr_gaussian_normals_forward(NULL, P, b->means, NULL, b->rots, b->view, b->out_n, b->axis), INV, GF "missing input or output buffer");
-    EXPECT(gsr_gaussian_normals_forward(NULL, P, b->means, b->scales, NULL, b->view, b->out_n, b->axis), INV, GF "missing input or output buffer");
-    EXPECT(gsr_gaussian_normals_forward(NULL, P, b->means, b->scales, b->rots, NULL, b->out_n, b->axis), INV, GF "missing input or output buffer");
-    EXPECT(gsr_gaussian_normals_forward(NULL, P, b->means, b->scales, b->rots, b->view, NULL, b->axis), INV, GF "missing input or output buffer");
-    EXPECT(gsr_gaussian_normals_forward(NULL, 0, NULL, NULL, NULL, NULL, NULL, NULL), GSR_OK, "");
-    EXPECT(gsr_gaussian_normals_backward(NULL, -1, b->rots, b->view, b->axis, b->gN, b->g_rots), INV, GB "bad sizes");
-    EXPECT(gsr_gaussian_normals_backward(NULL, P, NULL, b->view, b->axis, b->gN, b->g_rots), INV, GB "missing input or output buffer");
-    EXPECT(gsr_gaussian_normals_backward(NULL, P, b->rots, NULL, b->axis, b->gN, b->g_rots), INV, GB "missing input or output buffer");
-    EXPECT(gsr_gaussian_normals_backward(NULL, P, b->rots, b->view, NULL, b->gN, b->g_rots), INV, GB "missing input or output buffer");
-    EXPECT(gsr_gaussian_normals_backward(NULL, P, b->rots, b->view, b->axis, NULL, b->g_rots), INV, GB "missing input or output buffer");
-    EXPECT(gsr_gaussian_normals_backward(NULL, P, b->rots, b->view, b->axis, b->gN, NULL), INV, GB "missing input or output buffer");
-    EXPECT(gsr_gaussian_normals_backward(NULL, 0, NULL, NULL, NULL, NULL, NULL), GSR_OK, "");
-    EXPECT(gsr_normal_loss_workspace(0, W, &n), INV, LW "bad sizes");
-    EXPECT(gsr_normal_loss_workspace(H, 0, &n), INV, LW "bad sizes");
-    EXPECT(gsr_normal_loss_workspace(H, W, NULL), INV, LW "bad argument");
-    EXPECT(gsr_normal_loss_workspace(8 * 65535 + 1, W, &n), INV, LW "image too large");
+    EXPECT_TEXT(gsr_gaussian_normals_forward(NULL, -1, b->means, b->scales, b->rots, b->view, b->out_n, b->axis), INV, GF "bad sizes");
+    EXPECT_TEXT(gsr_gaussian_normals_forward(NULL, P, NULL, b->scales, b->rots, b->view, b->out_n, b->axis), INV, GF "missing input or output buffer");
+    EXPECT_TEXT(gsr_gaussian_normals_forward(NULL, P, b->means, NULL, b->rots, b->view, b->out_n, b->axis), INV, GF "missing input or output buffer");
+    EXPECT_TEXT(gsr_gaussian_normals_forward(NULL, P, b->means, b->scales, NULL, b->view, b->out_n, b->axis), INV, GF "missing input or output buffer");
+    EXPECT_TEXT(gsr_gaussian_normals_forward(NULL, P, b->means, b->scales, b->rots, NULL, b->out_n, b->axis), INV, GF "missing input or output buffer");
+    EXPECT_TEXT(gsr_gaussian_normals_forward(NULL, P, b->means, b->scales, b->rots, b->view, NULL, b->axis), INV, GF "missing input or output buffer");
+    EXPECT_TEXT(gsr_gaussian_normals_forward(NULL, 0, NULL, NULL, NULL, NULL, NULL, NULL), GSR_OK, "");
+    EXPECT_TEXT(gsr_gaussian_normals_backward(NULL, -1, b->rots, b->view, b->axis, b->gN, b->g_rots), INV, GB "bad sizes");
+    EXPECT_TEXT(gsr_gaussian_normals_backward(NULL, P, NULL, b->view, b->axis, b->gN, b->g_rots), INV, GB "missing input or output buffer");
+    EXPECT_TEXT(gsr_gaussian_normals_backward(NULL, P, b->rots, NULL, b->axis, b->gN, b->g_rots), INV, GB "missing input or output buffer");
+    EXPECT_TEXT(gsr_gaussian_normals_backward(NULL, P, b->rots, b->view, NULL, b->gN, b->g_rots), INV, GB "missing input or output buffer");
+    EXPECT_TEXT(gsr_gaussian_normals_backward(NULL, P, b->rots, b->view, b->axis, NULL, b->g_rots), INV, GB "missing input or output buffer");
+    EXPECT_TEXT(gsr_gaussian_normals_backward(NULL, P, b->rots, b->view, b->axis, b->gN, NULL), INV, GB "missing input or output buffer");
+    EXPECT_TEXT(gsr_gaussian_normals_backward(NULL, 0, NULL, NULL, NULL, NULL, NULL), GSR_OK, "");
+    EXPECT_TEXT(gsr_normal_loss_workspace(0, W, &n), INV, LW "bad sizes");
+    EXPECT_TEXT(gsr_normal_loss_workspace(H, 0, &n), INV, LW "bad sizes");
+    EXPECT_TEXT(gsr_normal_loss_workspace(H, W, NULL), INV, LW "bad argument");
+    EXPECT_TEXT(gsr_normal_loss_workspace(8 * 65535 + 1, W, &n), INV, LW "image too large");
 #define FWD(H_, W_, am_, d_, a_, n_, o2_, ws_, wb_) gsr_normal_loss_forward(NULL, H_, W_, b->tx, b->ty, am_, d_, a_, n_, o2_, b->surf, ws_, wb_)
-    EXPECT(FWD(0, W, b->amin, b->depth, b->alpha, b->normals, b->out2, b->ws, b->wb), INV, LF "bad sizes");
-    EXPECT(FWD(H, -3, b->amin, b->depth, b->alpha, b->normals, b->out2, b->ws, b->wb), INV, LF "bad sizes");
-    EXPECT(FWD(H, (1 << 20) + 1, b->amin, b->depth, b->alpha, b->normals, b->out2, b->ws, b->wb), INV, LF "image too large");
-    EXPECT(FWD(H, W, 0.f, b->depth, b->alpha, b->normals, b->out2, b->ws, b->wb), INV, LF AMIN);
-    EXPECT(FWD(H, W, -1.f, b->depth, b->alpha, b->normals, b->out2, b->ws, b->wb), INV, LF AMIN);
-    EXPECT(FWD(H, W, b->amin, NULL, b->alpha, b->normals, b->out2, b->ws, b->wb), INV, LF "missing input, output or workspace");
-    EXPECT(FWD(H, W, b->amin, b->depth, NULL, b->normals, b->out2, b->ws, b->wb), INV, LF "missing input, output or workspace");
-    EXPECT(FWD(H, W, b->amin, b->depth, b->alpha, NULL, b->out2, b->ws, b->wb), INV, LF "missing input, output or workspace");
-    EXPECT(FWD(H, W, b->amin, b->depth, b->alpha, b->normals, NULL, b->ws, b->wb), INV, LF "missing input, output or workspace");
-    EXPECT(FWD(H, W, b->amin, b->depth, b->alpha, b->normals, b->out2, NULL, b->wb), INV, LF "missing input, output or workspace");
+    EXPECT_TEXT(FWD(0, W, b->amin, b->depth, b->alpha, b->normals, b->out2, b->ws, b->wb), INV, LF "bad sizes");
+    EXPECT_TEXT(FWD(H, -3, b->amin, b->depth, b->alpha, b->normals, b->out2, b->ws, b->wb), INV, LF "bad sizes");
+    EXPECT_TEXT(FWD(H, (1 << 20) + 1, b->amin, b->depth, b->alpha, b->normals, b->out2, b->ws, b->wb), INV, LF "image too large");
+    EXPECT_TEXT(FWD(H, W, 0.f, b->depth, b->alpha, b->normals, b->out2, b->ws, b->wb), INV, LF AMIN);
+    EXPECT_TEXT(FWD(H, W, -1.f, b->depth, b->alpha, b->normals, b->out2, b->ws, b->wb), INV, LF AMIN);
+    EXPECT_TEXT(FWD(H, W, b->amin, NULL, b->alpha, b->normals, b->out2, b->ws, b->wb), INV, LF "missing input, output or workspace");
+    EXPECT_TEXT(FWD(H, W, b->amin, b->depth, NULL, b->normals, b->out2, b->ws, b->wb), INV, LF "missing input, output or workspace");
+    EXPECT_TEXT(FWD(H, W, b->amin, b->depth, b->alpha, NULL, b->out2, b->ws, b->wb), INV, LF "missing input, output or workspace");
+    EXPECT_TEXT(FWD(H, W, b->amin, b->depth, b->alpha, b->normals, NULL, b->ws, b->wb), INV, LF "missing input, output or workspace");
+    EXPECT_TEXT(FWD(H, W, b->amin, b->depth, b->alpha, b->normals, b->out2, NULL, b->wb), INV, LF "missing input, output or workspace");
     {
         char text[128];
         snprintf(text, sizeof text, LF "workspace %zu < %zu", b->wb - 1, b->wb);
-        EXPECT(FWD(H, W, b->amin, b->depth, b->alpha, b->normals, b->out2, b->ws, b->wb - 1), GSR_ERR_WORKSPACE, text);
+        EXPECT_TEXT(FWD(H, W, b->amin, b->depth, b->alpha, b->normals, b->out2, b->ws, b->wb - 1), GSR_ERR_WORKSPACE, text);
     }
     /* the order: sizes, alpha_min, pointers, the workspace's size */
-    EXPECT(FWD(0, W, 0.f, NULL, b->alpha, b->normals, b->out2, b->ws, 0), INV, LF "bad sizes");
-    EXPECT(FWD(H, W, 0.f, NULL, b->alpha, b->normals, b->out2, b->ws, 0), INV, LF AMIN);
-    EXPECT(FWD(H, W, b->amin, NULL, b->alpha, b->normals, b->out2, b->ws, 0), INV, LF "missing input, output or workspace");
+    EXPECT_TEXT(FWD(0, W, 0.f, NULL, b->alpha, b->normals, b->out2, b->ws, 0), INV, LF "bad sizes");
+    EXPECT_TEXT(FWD(H, W, 0.f, NULL, b->alpha, b->normals, b->out2, b->ws, 0), INV, LF AMIN);
+    EXPECT_TEXT(FWD(H, W, b->amin, NULL, b->alpha, b->normals, b->out2, b->ws, 0), INV, LF "missing input, output or workspace");
 #define BWD(H_, W_, am_, d_, a_, n_, gd_, ga_, gn_) gsr_normal_loss_backward(NULL, H_, W_, b->tx, b->ty, am_, d_, a_, n_, NULL, gd_, ga_, gn_)
-    EXPECT(BWD(H, 0, b->amin, b->depth, b->alpha, b->normals, b->gd, b->ga, b->gn), INV, LB "bad sizes");
-    EXPECT(BWD(-1, W, b->amin, b->depth, b->alpha, b->normals, b->gd, b->ga, b->gn), INV, LB "bad sizes");
-    EXPECT(BWD(H, W, 0.f, b->depth, b->alpha, b->normals, b->gd, b->ga, b->gn), INV, LB AMIN);
-    EXPECT(BWD(H, W, b->amin, NULL, b->alpha, b->normals, b->gd, b->ga, b->gn), INV, LB "missing input");
-    EXPECT(BWD(H, W, b->amin, b->depth, NULL, b->normals, b->gd, b->ga, b->gn), INV, LB "missing input");
-    EXPECT(BWD(H, W, b->amin, b->depth, b->alpha, NULL, b->gd, b->ga, b->gn), INV, LB "missing input");
-    EXPECT(BWD(H, W, b->amin, b->depth, b->alpha, b->normals, NULL, NULL, NULL), GSR_OK, "");        /* no output wanted: nothing runs */
+    EXPECT_TEXT(BWD(H, 0, b->amin, b->depth, b->alpha, b->normals, b->gd, b->ga, b->gn), INV, LB "bad sizes");
+    EXPECT_TEXT(BWD(-1, W, b->amin, b->depth, b->alpha, b->normals, b->gd, b->ga, b->gn), INV, LB "bad sizes");
+    EXPECT_TEXT(BWD(H, W, 0.f, b->depth, b->alpha, b->normals, b->gd, b->ga, b->gn), INV, LB AMIN);
+    EXPECT_TEXT(BWD(H, W, b->amin, NULL, b->alpha, b->normals, b->gd, b->ga, b->gn), INV, LB "missing input");
+    EXPECT_TEXT(BWD(H, W, b->amin, b->depth, NULL, b->normals, b->gd, b->ga, b->gn), INV, LB "missing input");
+    EXPECT_TEXT(BWD(H, W, b->amin, b->depth, b->alpha, NULL, b->gd, b->ga, b->gn), INV, LB "missing input");
+    EXPECT_TEXT(BWD(H, W, b->amin, b->depth, b->alpha, b->normals, NULL, NULL, NULL), GSR_OK, "");        /* no output wanted: nothing runs */
     return 0;
 }
 
@@ -149,7 +98,7 @@ int main(int argc, char **argv) {
     if (!f) { printf("cannot open %s\n", argv[1]); return 3; }
     int32_t hdr[3];
     float par[3];
-    if (fread(hdr, 4, 3, f) != 3 || fread(par, 4, 3, f) != 3) return 3;
+    rd_into(f, hdr, sizeof hdr); rd_into(f, par, sizeof par);
     struct bufs b;
     memset(&b, 0, sizeof b);
     b.P = hdr[0]; b.H = hdr[1]; b.W = hdr[2]; b.tx = par[0]; b.ty = par[1]; b.amin = par[2];
@@ -190,8 +139,7 @@ int main(int argc, char **argv) {
     }
     CK(hipDeviceSynchronize());
     bad |= dump(res, b.gd, px);
-    n_outs = 0; outs[n_outs].p = b.ga; outs[n_outs++].bytes = px; outs[n_outs].p = b.gn; outs[n_outs++].bytes = 3 * px;
-    if (changed()) { printf("a NULL output's neighbour was written\n"); return 1; }
+    if (buf_changed(b.ga, px) || buf_changed(b.gn, 3 * px)) { printf("a NULL output's neighbour was written\n"); return 1; }
     if (fclose(res) || bad) { printf("could not write the results\n"); return 3; }
     printf("normals C client ok\n");
     return 0;

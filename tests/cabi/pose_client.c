@@ -2,40 +2,14 @@
  * Built and run by tests/test_gpu_pose_cabi.py on the GPU box:
  *   gcc pose_client.c -I<repo>/include -I/opt/rocm/include -L<pkg> -lgsr_hip -L/opt/rocm/lib -lamdhip64
  *   pose_client <problem file>
- * The problem file is written by the Python side: int32 P D M W H, float32 tanfovx tanfovy scale_modifier, then float32 bg [3],
- * means3D [P,3], shs [P,M,3], opacities [P], scales [P,3], rotations [P,4], viewmatrix [16], projmatrix [16], campos [3],
- * dL_dpix [3,H,W]; then float64 the reference's dL_dviewmatrix [16], dL_dprojmatrix [16], dL_dcampos [3] (tests/pose_ref.py, float64)
+ * The problem file is written by the Python side: the scene block of client_common.h (int32 P D M W H, float32 tanfovx tanfovy
+ * scale_modifier, then float32 bg [3], means3D [P,3], shs [P,M,3], opacities [P], scales [P,3], rotations [P,4], viewmatrix [16],
+ * projmatrix [16], campos [3]), then float32 dL_dpix [3,H,W]; then float64 the reference's dL_dviewmatrix [16], dL_dprojmatrix [16], dL_dcampos [3] (tests/pose_ref.py, float64)
  * and three float64 bounds on the error of each tensor relative to the reference's largest entry. */
-#define __HIP_PLATFORM_AMD__ 1
-#include <hip/hip_runtime_api.h>
 #include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include "gsr_pose.h"
+#include "client_common.h"
 
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %d at line %d\n", (int)e_, __LINE__); return 2; } } while (0)
-#define EXPECT(call, code, what) do { int rc_ = (call); if (rc_ != (code) || ((code) != GSR_OK && strlen(gsr_last_error()) == 0)) { \
-    printf("%s: expected %d with a message, got %d (%s)\n", what, (int)(code), rc_, gsr_last_error()); return 1; } } while (0)
-
-static void *g_bin = NULL; static size_t g_bin_bytes = 0;
-static void *alloc_cb(void *user, size_t bytes) {
-    (void)user;
-    if (hipMalloc(&g_bin, bytes ? bytes : 1) != hipSuccess) return NULL;
-    g_bin_bytes = bytes;
-    return g_bin;
-}
-static void *rd(FILE *f, size_t bytes) {
-    void *p = malloc(bytes ? bytes : 1);
-    if (!p || fread(p, 1, bytes, f) != bytes) { printf("short problem file\n"); exit(3); }
-    return p;
-}
-static float *dev_copy(const float *h, size_t n) {
-    float *d;
-    if (hipMalloc((void **)&d, n * 4 + 4) != hipSuccess) return NULL;
-    hipMemcpy(d, h, n * 4, hipMemcpyHostToDevice);
-    return d;
-}
 static int compare(const char *name, const float *got, const double *want, int n, double bound) {
     double big = 0, err = 0;
     for (int i = 0; i < n; i++) { if (fabs(want[i]) > big) big = fabs(want[i]); }
@@ -49,35 +23,37 @@ int main(int argc, char **argv) {
     if (argc < 2) { printf("usage: pose_client <problem file>\n"); return 3; }
     FILE *f = fopen(argv[1], "rb");
     if (!f) { printf("cannot open %s\n", argv[1]); return 3; }
-    int32_t hdr[5]; float par[3];
-    if (fread(hdr, 4, 5, f) != 5 || fread(par, 4, 3, f) != 3) return 3;
-    const int32_t P = hdr[0], D = hdr[1], M = hdr[2], W = hdr[3], H = hdr[4];
-    const float tanx = par[0], tany = par[1], mod = par[2];
-    float *bg = rd(f, 12), *means = rd(f, (size_t)P * 12), *shs = rd(f, (size_t)P * M * 12), *op = rd(f, (size_t)P * 4), *sc = rd(f, (size_t)P * 12);
-    float *rot = rd(f, (size_t)P * 16), *view = rd(f, 64), *proj = rd(f, 64), *cam = rd(f, 12), *dl = rd(f, (size_t)3 * W * H * 4);
+    struct cabi_scene s = {.spare = 4};               /* one float past every input: a read past an array's end stays inside its allocation */
+    struct cabi_render r;
+    int rc = cabi_scene_read(f, &s);
+    if (rc) return rc;
+    const int32_t P = s.P, D = s.D, M = s.M, W = s.W, H = s.H;
+    const float tanx = s.tanfovx, tany = s.tanfovy, mod = s.scale_modifier;
+    const size_t px = (size_t)3 * W * H * 4;
+    float *dl = rd(f, px);
     double *want = rd(f, 35 * 8), *bound = rd(f, 3 * 8);
     fclose(f);
     if (gsr_abi_version() != GSR_ABI_VERSION) { printf("ABI version mismatch\n"); return 1; }
 
-    float *d_bg = dev_copy(bg, 3), *d_means = dev_copy(means, (size_t)P * 3), *d_shs = dev_copy(shs, (size_t)P * M * 3), *d_op = dev_copy(op, P);
-    float *d_sc = dev_copy(sc, (size_t)P * 3), *d_rot = dev_copy(rot, (size_t)P * 4), *d_view = dev_copy(view, 16), *d_proj = dev_copy(proj, 16);
-    float *d_cam = dev_copy(cam, 3), *d_dl = dev_copy(dl, (size_t)3 * W * H);
-    size_t gb, ib, bb, wb, pb;
-    EXPECT(gsr_workspace_sizes(P, W, H, &gb, &ib, &bb), GSR_OK, "sizes");
-    EXPECT(gsr_pose_workspace_bytes(P, &pb), GSR_OK, "pose workspace size");
+    float *d_bg = s.bg, *d_means = s.means3D, *d_shs = s.shs, *d_sc = s.scales, *d_rot = s.rotations, *d_view = s.viewmatrix, *d_proj = s.projmatrix;
+    float *d_cam = s.campos, *d_dl = dev_copy_spare(dl, px, s.spare);
+    if (!d_dl) { printf("hipMalloc failed\n"); return 2; }
+    if ((rc = cabi_render(&s, &r)) != 0) return rc;
+    void *geom = r.geom, *img = r.img, *bwd, *pws;
+    int32_t *radii = r.radii;
+    const size_t gb = r.gb, ib = r.ib;
+    const int64_t n = r.R;
+    size_t wb, pb;
+    EXPECT_CODE(gsr_pose_workspace_bytes(P, &pb), GSR_OK, "pose workspace size");
     if (pb != (size_t)((P + 255) / 256) * 256) { printf("pose workspace %zu\n", pb); return 1; }
-    void *geom, *img, *bwd, *pws; float *color; int32_t *radii; int64_t n = -1;
-    CK(hipMalloc(&geom, gb)); CK(hipMalloc(&img, ib)); CK(hipMalloc(&pws, pb));
-    CK(hipMalloc((void **)&color, (size_t)3 * W * H * 4)); CK(hipMalloc((void **)&radii, (size_t)P * 4));
-    EXPECT(gsr_forward(NULL, P, D, M, W, H, d_bg, d_means, d_shs, NULL, d_op, d_sc, mod, d_rot, NULL, d_view, d_proj, d_cam, tanx, tany, 0, 0,
-                       color, radii, geom, gb, alloc_cb, NULL, img, ib, &n, NULL, 0), GSR_OK, "forward");
-    EXPECT(gsr_backward_workspace_bytes(P, n, &wb), GSR_OK, "backward workspace size");
+    CK(hipMalloc(&pws, pb));
+    EXPECT_CODE(gsr_backward_workspace_bytes(P, n, &wb), GSR_OK, "backward workspace size");
     CK(hipMalloc(&bwd, wb));
     float *g2, *go, *g3, *gsh, *gs, *gr;
     CK(hipMalloc((void **)&g2, (size_t)P * 12)); CK(hipMalloc((void **)&go, (size_t)P * 4)); CK(hipMalloc((void **)&g3, (size_t)P * 12));
     CK(hipMalloc((void **)&gsh, (size_t)P * M * 12)); CK(hipMalloc((void **)&gs, (size_t)P * 12)); CK(hipMalloc((void **)&gr, (size_t)P * 16));
-    EXPECT(gsr_backward(NULL, P, D, M, n, W, H, d_bg, d_means, radii, d_shs, NULL, d_sc, mod, d_rot, NULL, d_view, d_proj, d_cam, tanx, tany, d_dl,
-                        geom, gb, g_bin, g_bin_bytes, img, ib, bwd, wb, g2, go, NULL, g3, NULL, gsh, gs, gr, 0, NULL, 0, NULL), GSR_OK, "backward");
+    EXPECT_CODE(gsr_backward(NULL, P, D, M, n, W, H, d_bg, d_means, radii, d_shs, NULL, d_sc, mod, d_rot, NULL, d_view, d_proj, d_cam, tanx, tany, d_dl,
+                        geom, gb, r.binning, r.binning_bytes, img, ib, bwd, wb, g2, go, NULL, g3, NULL, gsh, gs, gr, 0, NULL, 0, NULL), GSR_OK, "backward");
 
     float *d_out;                       /* 16 + 16 + 3 outputs between two guard floats each */
     float h_out[41];
@@ -89,14 +65,14 @@ int main(int argc, char **argv) {
     gsr_pose_backward(NULL, kind, p, d, m, W, H, n, d_means, radii, shs_, col_, sc_, mod, rot_, cov_, d_view, d_proj, d_cam, tanx, tany, geom, gb, \
                       bwd, accb, pws, wsb, o1, o2, o3)
     /* refusals: nothing is enqueued, nothing is written */
-    EXPECT(POSE(3, P, D, M, d_shs, NULL, d_sc, d_rot, NULL, wb, pb, gV, gP, gC), GSR_ERR_INVALID_ARGUMENT, "kind 3");
-    EXPECT(POSE(0, P, D, M, d_shs, NULL, d_sc, d_rot, NULL, wb, pb, NULL, NULL, NULL), GSR_ERR_INVALID_ARGUMENT, "no output");
-    EXPECT(POSE(0, P, D, M, d_shs, d_shs, d_sc, d_rot, NULL, wb, pb, gV, gP, gC), GSR_ERR_INVALID_ARGUMENT, "shs and colors");
-    EXPECT(POSE(0, P, D, M, d_shs, NULL, d_sc, NULL, NULL, wb, pb, gV, gP, gC), GSR_ERR_INVALID_ARGUMENT, "scales without rotations");
-    EXPECT(POSE(0, P, 4, M, d_shs, NULL, d_sc, d_rot, NULL, wb, pb, gV, gP, gC), GSR_ERR_INVALID_ARGUMENT, "D = 4");
-    EXPECT(POSE(0, P, D, M, d_shs, NULL, d_sc, d_rot, NULL, 64, pb, gV, gP, gC), GSR_ERR_WORKSPACE, "accumulator workspace too small");
-    EXPECT(POSE(0, P, D, M, d_shs, NULL, d_sc, d_rot, NULL, wb, pb - 1, gV, gP, gC), GSR_ERR_WORKSPACE, "pose workspace too small");
-    EXPECT(gsr_pose_backward(NULL, 0, P, D, M, W, H, n, d_means, radii, d_shs, NULL, d_sc, mod, d_rot, NULL, d_view, d_proj, d_cam, tanx, tany, geom, gb / 2,
+    EXPECT_CODE(POSE(3, P, D, M, d_shs, NULL, d_sc, d_rot, NULL, wb, pb, gV, gP, gC), GSR_ERR_INVALID_ARGUMENT, "kind 3");
+    EXPECT_CODE(POSE(0, P, D, M, d_shs, NULL, d_sc, d_rot, NULL, wb, pb, NULL, NULL, NULL), GSR_ERR_INVALID_ARGUMENT, "no output");
+    EXPECT_CODE(POSE(0, P, D, M, d_shs, d_shs, d_sc, d_rot, NULL, wb, pb, gV, gP, gC), GSR_ERR_INVALID_ARGUMENT, "shs and colors");
+    EXPECT_CODE(POSE(0, P, D, M, d_shs, NULL, d_sc, NULL, NULL, wb, pb, gV, gP, gC), GSR_ERR_INVALID_ARGUMENT, "scales without rotations");
+    EXPECT_CODE(POSE(0, P, 4, M, d_shs, NULL, d_sc, d_rot, NULL, wb, pb, gV, gP, gC), GSR_ERR_INVALID_ARGUMENT, "D = 4");
+    EXPECT_CODE(POSE(0, P, D, M, d_shs, NULL, d_sc, d_rot, NULL, 64, pb, gV, gP, gC), GSR_ERR_WORKSPACE, "accumulator workspace too small");
+    EXPECT_CODE(POSE(0, P, D, M, d_shs, NULL, d_sc, d_rot, NULL, wb, pb - 1, gV, gP, gC), GSR_ERR_WORKSPACE, "pose workspace too small");
+    EXPECT_CODE(gsr_pose_backward(NULL, 0, P, D, M, W, H, n, d_means, radii, d_shs, NULL, d_sc, mod, d_rot, NULL, d_view, d_proj, d_cam, tanx, tany, geom, gb / 2,
                              bwd, wb, pws, pb, gV, gP, gC), GSR_ERR_WORKSPACE, "geometry workspace too small");
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(h_out, d_out, sizeof h_out, hipMemcpyDeviceToHost));
@@ -104,10 +80,10 @@ int main(int argc, char **argv) {
 
     /* the call, twice: same bits; the guards stay */
     float first[41];
-    EXPECT(POSE(0, P, D, M, d_shs, NULL, d_sc, d_rot, NULL, wb, pb, gV, gP, gC), GSR_OK, "pose backward");
+    EXPECT_CODE(POSE(0, P, D, M, d_shs, NULL, d_sc, d_rot, NULL, wb, pb, gV, gP, gC), GSR_OK, "pose backward");
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(first, d_out, sizeof first, hipMemcpyDeviceToHost));
-    EXPECT(POSE(0, P, D, M, d_shs, NULL, d_sc, d_rot, NULL, wb, pb, gV, gP, gC), GSR_OK, "pose backward again");
+    EXPECT_CODE(POSE(0, P, D, M, d_shs, NULL, d_sc, d_rot, NULL, wb, pb, gV, gP, gC), GSR_OK, "pose backward again");
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(h_out, d_out, sizeof h_out, hipMemcpyDeviceToHost));
     if (memcmp(first, h_out, sizeof first)) { printf("two calls on one workspace differ\n"); return 1; }
@@ -124,20 +100,20 @@ int main(int argc, char **argv) {
     float h2[41];
     for (int i = 0; i < 41; i++) h2[i] = NAN;
     CK(hipMemcpy(d_out, h2, sizeof h2, hipMemcpyHostToDevice));
-    EXPECT(POSE(0, P, D, M, d_shs, NULL, d_sc, d_rot, NULL, wb, pb, NULL, NULL, gC), GSR_OK, "campos alone");
+    EXPECT_CODE(POSE(0, P, D, M, d_shs, NULL, d_sc, d_rot, NULL, wb, pb, NULL, NULL, gC), GSR_OK, "campos alone");
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(h2, d_out, sizeof h2, hipMemcpyDeviceToHost));
     if (memcmp(h2 + 37, first + 37, 12)) { printf("campos alone differs\n"); return 1; }
     for (int i = 0; i < 37; i++) if (!isnan(h2[i])) { printf("a NULL output was written (%d)\n", i); return 1; }
 
     /* P = 0 and R = 0: zeros, no workspace read */
-    EXPECT(gsr_pose_backward(NULL, 0, 0, D, M, W, H, 0, NULL, NULL, NULL, NULL, NULL, mod, NULL, NULL, NULL, NULL, NULL, tanx, tany, NULL, 0, NULL, 0, NULL, 0,
+    EXPECT_CODE(gsr_pose_backward(NULL, 0, 0, D, M, W, H, 0, NULL, NULL, NULL, NULL, NULL, mod, NULL, NULL, NULL, NULL, NULL, tanx, tany, NULL, 0, NULL, 0, NULL, 0,
                              gV, gP, gC), GSR_OK, "P = 0");
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(h2, d_out, sizeof h2, hipMemcpyDeviceToHost));
     for (int i = 1; i < 40; i++) if (i != 17 && i != 18 && i != 35 && i != 36 && (h2[i] != 0.f || signbit(h2[i]))) { printf("P = 0: output %d is not +0\n", i); return 1; }
     CK(hipMemcpy(d_out, first, sizeof first, hipMemcpyHostToDevice));
-    EXPECT(gsr_pose_backward(NULL, 2, P, D, M, W, H, 0, NULL, NULL, NULL, NULL, NULL, mod, NULL, NULL, NULL, NULL, NULL, tanx, tany, NULL, 0, NULL, 0, NULL, 0,
+    EXPECT_CODE(gsr_pose_backward(NULL, 2, P, D, M, W, H, 0, NULL, NULL, NULL, NULL, NULL, mod, NULL, NULL, NULL, NULL, NULL, tanx, tany, NULL, 0, NULL, 0, NULL, 0,
                              gV, NULL, gC), GSR_OK, "R = 0");
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(h2, d_out, sizeof h2, hipMemcpyDeviceToHost));

@@ -5,35 +5,15 @@
  * The problem file is written by the Python side: int32 P D B, then float32 rows [P,D], the expected xyz [P,3], f_dc [P,3],
  * f_rest [P,3(K-1)], opacity [P], scaling [P,3], rotation [P,4] (tests/rows_ref.py unpack_ref), B arenas of P (3 K + 11) floats
  * each, and the expected grad_rows [P,D] (pack_ref).  Everything is compared bit for bit. */
-#define __HIP_PLATFORM_AMD__ 1
-#include <hip/hip_runtime_api.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include "gsr_rows.h"
-
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %d at line %d\n", (int)e_, __LINE__); return 2; } } while (0)
-#define EXPECT(call, code, what) do { int rc_ = (call); if (rc_ != (code) || ((code) != GSR_OK && strlen(gsr_last_error()) == 0)) { \
-    printf("%s: expected %d with a message, got %d (%s)\n", what, (int)(code), rc_, gsr_last_error()); return 1; } } while (0)
-
-static void *rd(FILE *f, size_t bytes) {
-    void *p = malloc(bytes ? bytes : 1);
-    if (!p || fread(p, 1, bytes, f) != bytes) { printf("short problem file\n"); exit(3); }
-    return p;
-}
-static void *dev_copy(const void *h, size_t bytes) {
-    void *d;
-    if (hipMalloc(&d, bytes ? bytes : 1) != hipSuccess) return NULL;
-    hipMemcpy(d, h, bytes, hipMemcpyHostToDevice);
-    return d;
-}
+#include "client_common.h"
 
 int main(int argc, char **argv) {
     if (argc < 2) { printf("usage: rows_client <problem file>\n"); return 3; }
     FILE *f = fopen(argv[1], "rb");
     if (!f) { printf("cannot open %s\n", argv[1]); return 3; }
     int32_t hdr[3];
-    if (fread(hdr, 4, 3, f) != 3) return 3;
+    rd_into(f, hdr, sizeof hdr);
     const int32_t P = hdr[0], D = hdr[1], B = hdr[2];
     const int32_t K = (D - 14) / 3;
     if (B < 1 || B > GSR_ROWS_MAX_B || K < 2) { printf("bad problem header\n"); return 3; }
@@ -50,11 +30,11 @@ int main(int argc, char **argv) {
     /* ---- unpack ---- */
     float *d_rows = dev_copy(rows, e * 4), *d_out[6];
     for (int k = 0; k < 6; k++) CK(hipMalloc((void **)&d_out[k], (size_t)P * w[k] * 4 + 16));
-    EXPECT(gsr_rows_unpack(NULL, P, 18, d_rows, d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], d_out[5]), GSR_ERR_INVALID_ARGUMENT, "D = 18");
-    EXPECT(gsr_rows_unpack(NULL, P, D, d_rows, d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], d_out[5] + 1), GSR_ERR_INVALID_ARGUMENT,
+    EXPECT_CODE(gsr_rows_unpack(NULL, P, 18, d_rows, d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], d_out[5]), GSR_ERR_INVALID_ARGUMENT, "D = 18");
+    EXPECT_CODE(gsr_rows_unpack(NULL, P, D, d_rows, d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], d_out[5] + 1), GSR_ERR_INVALID_ARGUMENT,
            "misaligned rotation");
-    EXPECT(gsr_rows_unpack(NULL, 0, D, NULL, NULL, NULL, d_out[2], NULL, NULL, NULL), GSR_OK, "P = 0");
-    EXPECT(gsr_rows_unpack(NULL, P, D, d_rows, d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], d_out[5]), GSR_OK, "unpack");
+    EXPECT_CODE(gsr_rows_unpack(NULL, 0, D, NULL, NULL, NULL, d_out[2], NULL, NULL, NULL), GSR_OK, "P = 0");
+    EXPECT_CODE(gsr_rows_unpack(NULL, P, D, d_rows, d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], d_out[5]), GSR_OK, "unpack");
     CK(hipDeviceSynchronize());
     for (int k = 0; k < 6; k++) {
         const size_t bytes = (size_t)P * w[k] * 4;
@@ -70,10 +50,10 @@ int main(int argc, char **argv) {
     for (int b = B; b <= GSR_ROWS_MAX_B; b++) d_arenas[b] = d_arenas[0];
     float *d_grad;
     CK(hipMalloc((void **)&d_grad, e * 4));
-    EXPECT(gsr_rows_grad_pack(NULL, P, D, GSR_ROWS_MAX_B + 1, d_arenas, d_grad), GSR_ERR_INVALID_ARGUMENT, "B = 65");
-    EXPECT(gsr_rows_grad_pack(NULL, P, D, 0, d_arenas, d_grad), GSR_ERR_INVALID_ARGUMENT, "B = 0");
-    EXPECT(gsr_rows_grad_pack(NULL, P, D, B, d_arenas, (float *)d_arenas[B - 1] + 1), GSR_ERR_INVALID_ARGUMENT, "grad_rows inside an arena");
-    EXPECT(gsr_rows_grad_pack(NULL, P, D, B, d_arenas, d_grad), GSR_OK, "grad pack");
+    EXPECT_CODE(gsr_rows_grad_pack(NULL, P, D, GSR_ROWS_MAX_B + 1, d_arenas, d_grad), GSR_ERR_INVALID_ARGUMENT, "B = 65");
+    EXPECT_CODE(gsr_rows_grad_pack(NULL, P, D, 0, d_arenas, d_grad), GSR_ERR_INVALID_ARGUMENT, "B = 0");
+    EXPECT_CODE(gsr_rows_grad_pack(NULL, P, D, B, d_arenas, (float *)d_arenas[B - 1] + 1), GSR_ERR_INVALID_ARGUMENT, "grad_rows inside an arena");
+    EXPECT_CODE(gsr_rows_grad_pack(NULL, P, D, B, d_arenas, d_grad), GSR_OK, "grad pack");
     CK(hipDeviceSynchronize());
     float *h_grad = malloc(e * 4);
     CK(hipMemcpy(h_grad, d_grad, e * 4, hipMemcpyDeviceToHost));

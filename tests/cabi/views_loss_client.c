@@ -4,14 +4,9 @@
  *   views_loss_client <problem file> <gradient file>
  * The problem file is written by the Python side: int32 B H W sanitize, float32 w_l1 w_ssim, then float32 images [B,3,H,W] and
  * targets [B,3,H,W].  Prints "out3" and "terms" as the bit patterns of the floats (and readably), writes the B gradient images. */
-#define __HIP_PLATFORM_AMD__ 1
-#include <hip/hip_runtime_api.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include "gsr_loss.h"
+#include "client_common.h"
 
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %d at line %d\n", (int)e_, __LINE__); return 2; } } while (0)
 #define MAXB 64
 
 static int expect_invalid(const char *what, int rc) {
@@ -26,12 +21,12 @@ int main(int argc, char **argv) {
     FILE *f = fopen(argv[1], "rb");
     if (!f) { printf("cannot open %s\n", argv[1]); return 3; }
     int32_t hdr[4]; float w[2];
-    if (fread(hdr, 4, 4, f) != 4 || fread(w, 4, 2, f) != 2) return 3;
+    rd_into(f, hdr, sizeof hdr); rd_into(f, w, sizeof w);
     const int32_t B = hdr[0], H = hdr[1], W = hdr[2], sanitize = hdr[3];
     if (B < 1 || B > MAXB) return 3;
     const size_t view = (size_t)3 * H * W, n = view * B;
-    float *h_img = malloc(n * 4), *h_gt = malloc(n * 4), *h_grad = malloc(n * 4);
-    if (!h_img || !h_gt || !h_grad || fread(h_img, 4, n, f) != n || fread(h_gt, 4, n, f) != n) { printf("short problem file\n"); return 3; }
+    float *h_img = rd(f, n * 4), *h_gt = rd(f, n * 4), *h_grad = malloc(n * 4);
+    if (!h_grad) return 3;
     fclose(f);
 
     if (gsr_abi_version() != GSR_ABI_VERSION) { printf("ABI version mismatch\n"); return 1; }

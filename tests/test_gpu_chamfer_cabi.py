@@ -1,16 +1,12 @@
 """-m gpu: a plain C program (tests/cabi/chamfer_client.c) drives the Chamfer entry points of libgsr_hip.so directly -- forward and
 backward on a 100 x 80 x 26 problem against values computed here in float64 (tests/chamfer_ref.py), and the error paths."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+from tests import cabi_client as cc
 from tests import chamfer_ref as cr
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_plain_c_client_chamfer(tmp_path):
@@ -29,13 +25,4 @@ def test_plain_c_client_chamfer(tmp_path):
         f.write(np.array([B, N, M, D], dtype=np.int32).tobytes())
         for a in (x1, x2, g1, g2, f32(d1), f32(d2), i1.astype(np.int32), i2.astype(np.int32), f32(dx1), f32(dx2), *map(f32, tol)):
             f.write(np.ascontiguousarray(a).tobytes())
-    pkg = os.path.join(ROOT, "gaussian_transformer_amd")
-    exe = str(tmp_path / "chamfer_client")
-    cc = shutil.which("gcc") or "gcc"
-    cmd = [cc, "-std=c11", "-O1", os.path.join(ROOT, "tests", "cabi", "chamfer_client.c"), "-I", os.path.join(ROOT, "include"),
-           "-I/opt/rocm/include", "-L", pkg, "-lgsr_hip", "-L/opt/rocm/lib", "-lamdhip64", "-lm",
-           f"-Wl,-rpath,{pkg}", "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    subprocess.check_call(cmd)
-    r = subprocess.run([exe, str(prob)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "chamfer C client ok" in r.stdout
+    cc.run(cc.build(tmp_path, "chamfer_client"), prob)

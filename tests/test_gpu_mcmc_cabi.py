@@ -1,20 +1,16 @@
 """-m gpu: a plain C program (tests/cabi/mcmc_client.c) drives gsr_mcmc_plan, gsr_mcmc_apply and gsr_mcmc_noise of libgsr_hip.so
 directly at P = 65: the relocation against tests/mcmc_ref.py (counts and copies bit for bit, the corrected values within one float32
 ulp), the noise against the float64 evaluation of the header's formula, and a few refusals."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 from gaussian_transformer_amd.densify import GROUPS, MCMCController
+from tests import cabi_client as cc
 from tests import mcmc_ref as mr
 from tests.test_mcmc_host import mr_noise64
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_plain_c_client_mcmc(tmp_path):
@@ -32,27 +28,13 @@ def test_plain_c_client_mcmc(tmp_path):
         for n in GROUPS:
             for t in (d["par"][n], d["mom"][n][0], d["mom"][n][1]):
                 f.write(np.ascontiguousarray(t.numpy()).tobytes())
-    pkg = os.path.join(ROOT, "gaussian_transformer_amd")
-    exe = str(tmp_path / "mcmc_client")
-    cc = shutil.which("gcc") or "gcc"
-    cmd = [cc, "-std=c11", "-O1", os.path.join(ROOT, "tests", "cabi", "mcmc_client.c"), "-I", os.path.join(ROOT, "include"),
-           "-I/opt/rocm/include", "-L", pkg, "-lgsr_hip", "-L/opt/rocm/lib", "-lamdhip64", "-lm",
-           f"-Wl,-rpath,{pkg}", "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    subprocess.check_call(cmd)
-    r = subprocess.run([exe, str(prob), str(res)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "mcmc C client ok" in r.stdout
-    raw = open(res, "rb").read()
-    counts = np.frombuffer(raw, dtype=np.uint32, count=4)
-    off, par, mom = 16, {}, {}
-    for n, w in zip(GROUPS, widths):
-        got = []
-        for _ in range(3):
-            got.append(torch.from_numpy(np.frombuffer(raw, dtype=np.float32, count=P * w, offset=off).copy()).reshape(d["par"][n].shape))
-            off += 4 * P * w
-        par[n], mom[n] = got[0], (got[1], got[2])
-    xyz_after = torch.from_numpy(np.frombuffer(raw, dtype=np.float32, count=P * 3, offset=off).copy()).reshape(P, 3)
-    assert off + 12 * P == len(raw)
+    cc.run(cc.build(tmp_path, "mcmc_client"), prob, res)
+    got = cc.read_result(res, [("counts", np.uint32, 4)] + [((n, k), np.float32, tuple(d["par"][n].shape)) for n in GROUPS for k in range(3)] +
+                         [("xyz_after", np.float32, (P, 3))])
+    counts = got["counts"]
+    t = lambda key: torch.from_numpy(got[key].copy())
+    par, mom = {n: t((n, 0)) for n in GROUPS}, {n: (t((n, 1)), t((n, 2))) for n in GROUPS}
+    xyz_after = t("xyz_after")
     ref = mr.cached_reference(P, rest, "mixed")
     assert dict(zip(("n_dead", "n_draws", "n_sources", "P_new"), (int(v) for v in counts))) == ref["counts"] and ref["counts"]["n_sources"] > 1
     worst = mr.assert_state(par, mom, d, ref, "C client")

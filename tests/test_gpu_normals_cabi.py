@@ -2,28 +2,14 @@
 code and its exact text, in the header's order, on outputs that hold a pattern and must keep it; the calls with nothing to do; then the
 calls themselves on 257 Gaussians and a 17 x 65 image with alpha holes (tiles crossed in both axes), which the Python side holds
 against tests/normals_ref.py under the tolerances of tests/test_gpu_gaussian_normals.py and tests/test_gpu_normal_loss.py."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
+from tests import cabi_client as cc
 from tests import normals_ref as nr
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build_client(tmp_path):
-    pkg = os.path.join(ROOT, "gaussian_transformer_amd")
-    exe = str(tmp_path / "normals_client")
-    cc = shutil.which("gcc") or "gcc"
-    subprocess.check_call([cc, "-std=c11", "-O1", os.path.join(ROOT, "tests", "cabi", "normals_client.c"), "-I", os.path.join(ROOT, "include"),
-                           "-I/opt/rocm/include", "-L", pkg, "-lgsr_hip", "-L/opt/rocm/lib", "-lamdhip64", "-lm",
-                           f"-Wl,-rpath,{pkg}", "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    return exe
 
 
 def rel(x, x64):
@@ -37,26 +23,17 @@ def test_plain_c_client_normals(tmp_path):
     G = np.random.default_rng(9).normal(size=(P, 3)).astype(np.float32)
     depth, alpha, N = nr.maps(H, W, holes=True)
     tx, ty = nr.TANFOV
-    f32 = lambda a: np.ascontiguousarray(np.asarray(a, np.float32)).tobytes()
     prob, res = tmp_path / "problem.bin", tmp_path / "result.bin"
     with open(prob, "wb") as f:
         f.write(np.asarray([P, H, W], dtype=np.int32).tobytes())
         f.write(np.asarray([tx, ty, nr.ALPHA_MIN], dtype=np.float32).tobytes())
         for a in (means, scales, q, V, G, depth, alpha, N):
-            f.write(f32(a))
-    exe = build_client(tmp_path)
-    r = subprocess.run([exe, str(prob), str(res)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "normals C client ok" in r.stdout
-    raw = open(res, "rb").read()
+            f.write(cc.f32(a))
+    cc.run(cc.build(tmp_path, "normals_client"), prob, res)
     px = H * W
-    sizes = [("normals", np.float32, 3 * P), ("axis", np.int32, P), ("g_rots", np.float32, 4 * P), ("out2", np.float32, 2), ("surf", np.float32, 3 * px),
-             ("g_depth", np.float32, px), ("g_alpha", np.float32, px), ("g_normals", np.float32, 3 * px), ("g_depth_quarter", np.float32, px)]
-    got, off = {}, 0
-    for name, dt, cnt in sizes:
-        got[name] = np.frombuffer(raw, dtype=dt, count=cnt, offset=off)
-        off += 4 * cnt
-    assert off == len(raw)
+    got = cc.read_result(res, [("normals", np.float32, 3 * P), ("axis", np.int32, P), ("g_rots", np.float32, 4 * P), ("out2", np.float32, 2),
+                               ("surf", np.float32, 3 * px), ("g_depth", np.float32, px), ("g_alpha", np.float32, px), ("g_normals", np.float32, 3 * px),
+                               ("g_depth_quarter", np.float32, px)])
 
     r64, r32 = nr.gaussian_normals(means, scales, q, V, torch.float64), nr.gaussian_normals(means, scales, q, V, torch.float32)
     assert np.array_equal(got["axis"], r64["axis"])
@@ -78,5 +55,4 @@ def test_plain_c_client_normals(tmp_path):
 
 def test_the_refusals_alone_need_no_device(tmp_path):
     """The same refusals on made-up addresses: the stand-alone form a host-side sanitizer build of the client runs."""
-    r = subprocess.run([build_client(tmp_path), "--refusals"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and "normals C client: refusals ok" in r.stdout, r.stdout + r.stderr
+    cc.run(cc.build(tmp_path, "normals_client"), "--refusals", timeout=60, ok="normals C client: refusals ok")

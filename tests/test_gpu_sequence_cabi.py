@@ -1,20 +1,16 @@
 """-m gpu: a plain C program (tests/cabi/sequence_client.c) drives the sequence entry points of libgsr_hip.so directly -- a box
 sort against the restatement of tests/sequence_ref.py, bit for bit, a two-camera visibility pass against the radii of the float32
 CPU oracle, and the error paths."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 from gaussian_transformer_amd import synth
 from oracle import ref
+from tests import cabi_client as cc
 from tests import sequence_ref as sr
 from tests.helpers import oracle_scene
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_plain_c_client_sequence(tmp_path):
@@ -40,13 +36,4 @@ def test_plain_c_client_sequence(tmp_path):
                   f32([c.tanfovx for c in cams]), f32([c.tanfovy for c in cams]), i32([c.image_width for c in cams]),
                   i32([c.image_height for c in cams]), i32(radii)):
             f.write(np.ascontiguousarray(a).tobytes())
-    pkg = os.path.join(ROOT, "gaussian_transformer_amd")
-    exe = str(tmp_path / "sequence_client")
-    cc = shutil.which("gcc") or "gcc"
-    cmd = [cc, "-std=c11", "-O1", os.path.join(ROOT, "tests", "cabi", "sequence_client.c"), "-I", os.path.join(ROOT, "include"),
-           "-I/opt/rocm/include", "-L", pkg, "-lgsr_hip", "-L/opt/rocm/lib", "-lamdhip64", "-lm",
-           f"-Wl,-rpath,{pkg}", "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    subprocess.check_call(cmd)
-    r = subprocess.run([exe, str(prob)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "sequence C client ok" in r.stdout
+    cc.run(cc.build(tmp_path, "sequence_client"), prob)

@@ -1,18 +1,14 @@
 """-m gpu: a plain C program (tests/cabi/views_loss_client.c) drives gsr_views_loss_* of libgsr_hip.so directly -- the error paths, then
 forward and backward on B = 3 views of 37 x 29 -- and prints the three numbers the Python call returns, bit for bit."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 from gaussian_transformer_amd import loss
+from tests import cabi_client as cc
 from tests import views_loss_ref as vr
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_plain_c_client_views_loss(tmp_path):
@@ -24,16 +20,8 @@ def test_plain_c_client_views_loss(tmp_path):
         f.write(np.array([B, H, W, 1], dtype=np.int32).tobytes())
         f.write(np.array([w_l1, w_ssim], dtype=np.float32).tobytes())
         f.write(img.tobytes()); f.write(gt.tobytes())
-    pkg = os.path.join(ROOT, "gaussian_transformer_amd")
-    exe = str(tmp_path / "views_loss_client")
-    cc = shutil.which("gcc") or "gcc"
-    subprocess.check_call([cc, "-std=c11", "-O1", os.path.join(ROOT, "tests", "cabi", "views_loss_client.c"), "-I", os.path.join(ROOT, "include"),
-                           "-I/opt/rocm/include", "-L", pkg, "-lgsr_hip", "-L/opt/rocm/lib", "-lamdhip64", "-lm",
-                           f"-Wl,-rpath,{pkg}", "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    r = subprocess.run([exe, str(prob), str(out)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "views loss C client ok" in r.stdout
-    line = [l for l in r.stdout.splitlines() if l.startswith("out3")][0].split()
+    said = cc.run(cc.build(tmp_path, "views_loss_client"), prob, out).splitlines()
+    line = [l for l in said if l.startswith("out3")][0].split()
     got = np.array([int(x, 16) for x in line[1:4]], dtype=np.uint32).view(np.float32)
     # the Python call on the same bytes: the same three numbers (loss, L1, SSIM over all views) and the same gradients, bit for bit
     xs = [torch.tensor(v, device="cuda", requires_grad=True) for v in img]
@@ -42,7 +30,7 @@ def test_plain_c_client_views_loss(tmp_path):
     assert got[0] == np.float32(L.detach().cpu().numpy())
     r64 = vr.torch_loss(img, gt, float(w_l1), float(w_ssim), True, torch.float64)
     assert abs(got[1] - r64["terms"][:, 0].mean()) <= 1e-6 and abs(got[2] - r64["terms"][:, 1].mean()) <= 1e-5
-    terms = np.array([int(x, 16) for x in [l for l in r.stdout.splitlines() if l.startswith("terms")][0].split()[1:]], dtype=np.uint32).view(np.float32)
+    terms = np.array([int(x, 16) for x in [l for l in said if l.startswith("terms")][0].split()[1:]], dtype=np.uint32).view(np.float32)
     assert np.array_equal(terms.reshape(B, 3), L.terms.cpu().numpy())
     grads = np.fromfile(out, dtype=np.float32).reshape(B, 3, H, W)
     assert np.array_equal(grads.view(np.uint32), np.stack([x.grad.cpu().numpy() for x in xs]).view(np.uint32))
