@@ -10,19 +10,10 @@ timed with device events after a warm-up, the two alternating inside every repet
 torch's peak allocated memory above what was allocated before the call.  One JSON line to --out.  Needs a HIP device: no fallback."""
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from chamfer_distance import ChamferDistance  # noqa: E402
+import benchkit
+from chamfer_distance import ChamferDistance
 
 SHAPES = [(1, 8192, 8192, 26), (1, 16384, 16384, 26), (4, 4096, 4096, 3)]
 
@@ -37,34 +28,8 @@ def torch_chamfer(_chd, x1, x2):
     return d.min(2).values, d.min(1).values
 
 
-def timed(fn, chd, x1, x2, backward):
-    """One call between two events -> (ms, peak bytes above the starting allocation)."""
-    x1.grad = x2.grad = None
-    torch.cuda.synchronize()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    d1, d2 = fn(chd, x1, x2)
-    if backward:
-        (d1.mean() + d2.mean()).backward()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1), torch.cuda.max_memory_allocated() - base
-
-
-def stats(ms):
-    return {"min_ms": min(ms), "median_ms": statistics.median(ms), "max_ms": max(ms), "reps": len(ms)}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "chamfer", "bench.json"))
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("chamfer_bench.py needs a HIP device (nothing is timed on a CPU)")
+    args = benchkit.parse(benchkit.parser(30, 5, "chamfer"))
     if args.reps < 20:
         raise SystemExit("--reps must be at least 20")
     dev = "cuda:0"
@@ -74,29 +39,34 @@ def main():
         g = torch.Generator(device=dev).manual_seed(N + D)
         x1 = torch.randn(B, N, D, device=dev, generator=g).requires_grad_(True)
         x2 = torch.randn(B, M, D, device=dev, generator=g).requires_grad_(True)
+
+        def clear():
+            x1.grad = x2.grad = None
+
+        def call(fn, backward):
+            d1, d2 = fn(chd, x1, x2)
+            if backward:
+                (d1.mean() + d2.mean()).backward()
+            return d1, d2                                                    # alive until the window has closed and the peak is read
         entry = {"B": B, "N": N, "M": M, "D": D, "inputs_bytes": 4 * B * (N + M) * D}
         for backward in (False, True):
             ms = {"hip": [], "torch": []}
             peak = {"hip": 0, "torch": 0}
             for rep in range(args.warmup + args.reps):
                 for name, fn in (("hip", hip_chamfer), ("torch", torch_chamfer)):      # alternating: both see the same box noise
-                    t, p = timed(fn, chd, x1, x2, backward)
+                    t, p, _ = benchkit.timed_peak(lambda: call(fn, backward), clear)
                     if rep >= args.warmup:
                         ms[name].append(t)
                         peak[name] = max(peak[name], p)
             key = "fwd_bwd" if backward else "fwd"
-            entry[key] = {n: dict(stats(ms[n]), peak_extra_bytes=peak[n]) for n in ms}
+            entry[key] = {n: dict(benchkit.stats_minmax(ms[n]), peak_extra_bytes=peak[n]) for n in ms}
             h, t = entry[key]["hip"], entry[key]["torch"]
             spread = (h["max_ms"] - h["min_ms"]) + (t["max_ms"] - t["min_ms"])
             entry[key]["torch_median_minus_hip_median_ms"] = t["median_ms"] - h["median_ms"]
             entry[key]["sum_of_min_max_spreads_ms"] = spread
             entry[key]["hip_faster_beyond_spread"] = bool(t["median_ms"] - h["median_ms"] > spread)
         result["shapes"].append(entry)
-    line = json.dumps(result)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-    print(line)
+    benchkit.write_json(result, args.out, indent=None)
 
 
 if __name__ == "__main__":

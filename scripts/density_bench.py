@@ -14,22 +14,17 @@ train : scripts/train_synthetic.py at its defaults, --density torch against hip,
 One JSON line to --out.  Needs a HIP device: no fallback."""
 from __future__ import annotations
 
-import argparse
+import functools
 import importlib.util
-import json
 import os
 import statistics
-import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from gaussian_transformer_amd.densify import GROUPS, DensityController, FusedDensityController, OptimizationParams  # noqa: E402
-from gaussian_transformer_amd.model import GaussianParams  # noqa: E402
+import benchkit
+from benchkit import ROOT, timed_dev_wall as timed
+from gaussian_transformer_amd.densify import GROUPS, DensityController, FusedDensityController, OptimizationParams
+from gaussian_transformer_amd.model import GaussianParams
 
 DEV = "cuda:0"
 ATTR = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity", "scaling": "_scaling", "rotation": "_rotation"}
@@ -48,31 +43,25 @@ def make_state(P, M, seed):
     return {"par": par, "mom": mom, "accum": accum, "denom": denom}
 
 
-def make_controller(cls, st):
+def controller_on(build, st):
+    """build(model) -> a controller on a fresh copy of the state's parameters, its optimizer given copies of the state's Adam moments."""
     m = GaussianParams(3)
     for k in GROUPS:
         setattr(m, ATTR[k], st["par"][k].clone().requires_grad_(True))
-    ctl = cls(m, OptimizationParams(), adam="hip")
+    ctl = build(m)
     for grp in ctl.optimizer.param_groups:
         a, b = st["mom"][grp["name"]]
         ctl.optimizer.state[grp["params"][0]] = {"step": 3, "exp_avg": a.clone(), "exp_avg_sq": b.clone()}
-    m.xyz_gradient_accum, m.denom = st["accum"].clone(), st["denom"].clone()
     return ctl
 
 
-def timed(fn):
-    torch.cuda.synchronize()
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    w0 = time.perf_counter()
-    t0.record()
-    out = fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1), (time.perf_counter() - w0) * 1e3, out
+def make_controller(cls, st):
+    ctl = controller_on(lambda m: cls(m, OptimizationParams(), adam="hip"), st)
+    ctl.model.xyz_gradient_accum, ctl.model.denom = st["accum"].clone(), st["denom"].clone()
+    return ctl
 
 
-def stats(ms):
-    return {"min_ms": round(min(ms), 4), "median_ms": round(statistics.median(ms), 4), "max_ms": round(max(ms), 4), "reps": len(ms)}
+stats = functools.partial(benchkit.stats_minmax, digits=4)
 
 
 def bench_shape(P, M, reps, warmup):
@@ -115,11 +104,11 @@ def bench_shape(P, M, reps, warmup):
     return out
 
 
-def bench_train(runs):
+def bench_train(runs, densities=("torch", "hip")):
     spec = importlib.util.spec_from_file_location("train_synthetic", os.path.join(ROOT, "scripts", "train_synthetic.py"))
     ts = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(ts)
-    rates = {"torch": [], "hip": []}
+    rates = {k: [] for k in densities}
     last = {}
     for rep in range(runs + 1):                                       # the first run of each is the warm-up
         for density in rates:
@@ -131,25 +120,16 @@ def bench_train(runs):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = benchkit.parser(10, 3, "density")
     ap.add_argument("--train-runs", type=int, default=3, help="0: skip the training loop")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "density", "bench.json"))
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("density_bench.py needs a HIP device (nothing is timed on a CPU)")
+    args = benchkit.parse(ap)
     result = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "shapes": []}
     for P, M in ((1_000_000, 16), (300_000, 4)):
         result["shapes"].append(bench_shape(P, M, args.reps, args.warmup))
         torch.cuda.empty_cache()
     if args.train_runs > 0:
         result["train_synthetic"] = bench_train(args.train_runs)
-    line = json.dumps(result)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-    print(line)
+    benchkit.write_json(result, args.out, indent=None)
 
 
 if __name__ == "__main__":

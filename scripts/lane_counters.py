@@ -18,16 +18,12 @@ sys.path.insert(0, ROOT)
 
 def count_once(sc, dev, opts=(), mode=1):
     import torch
-    from gaussian_transformer_amd import GaussianRasterizationSettings, GaussianRasterizer, _lib
-    from gaussian_transformer_amd.render import TorchCamera
-    cam = TorchCamera(sc.camera, dev)
+    from scripts import benchkit
+    from gaussian_transformer_amd import GaussianRasterizer, _lib
     t = lambda a, g=False: torch.tensor(a, dtype=torch.float32, device=dev).requires_grad_(g)
     means3D, opac, shs = t(sc.means3D, True), t(sc.opacities, True), t(sc.shs, True)
     scales, rots = t(sc.scales, True), t(sc.rotations, True)
-    rs = GaussianRasterizationSettings(
-        image_height=cam.image_height, image_width=cam.image_width, tanfovx=sc.camera.tanfovx, tanfovy=sc.camera.tanfovy,
-        bg=t(sc.bg), scale_modifier=1.0, viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform,
-        sh_degree=sc.sh_degree, campos=cam.camera_center, prefiltered=False, debug=False)
+    rs = benchkit.scene_settings(sc, dev)
     for k, v in opts:
         _lib.set_option(k, v)
     _lib.set_option("count_lanes", mode)

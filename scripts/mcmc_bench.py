@@ -16,25 +16,14 @@ train : scripts/train_synthetic.py at its defaults, --density hip, mcmc and mcmc
 alternating, after one run each, and the final PSNR.  One JSON line to --out.  Needs a HIP device: no fallback."""
 from __future__ import annotations
 
-import argparse
-import importlib.util
-import json
-import os
-import statistics
-import sys
-import time
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from gaussian_transformer_amd.densify import GROUPS, FusedMCMCController, MCMCController, MCMCParams, OptimizationParams  # noqa: E402
-from gaussian_transformer_amd.model import GaussianParams  # noqa: E402
+import benchkit
+from benchkit import timed_dev_wall as timed
+from density_bench import bench_train, controller_on, stats
+from gaussian_transformer_amd.densify import FusedMCMCController, MCMCController, MCMCParams, OptimizationParams
 
 DEV = "cuda:0"
-ATTR = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity", "scaling": "_scaling", "rotation": "_rotation"}
 CLASSES = {"hip": FusedMCMCController, "torch": MCMCController}
 
 
@@ -51,30 +40,9 @@ def make_state(P, M, seed):
 
 
 def make_controller(cls, st):
-    m = GaussianParams(3)
-    for k in GROUPS:
-        setattr(m, ATTR[k], st["par"][k].clone().requires_grad_(True))
-    ctl = cls(m, MCMCParams(cap_max=10 ** 9), OptimizationParams(), adam="hip")
-    for grp in ctl.optimizer.param_groups:
-        a, b = st["mom"][grp["name"]]
-        ctl.optimizer.state[grp["params"][0]] = {"step": 3, "exp_avg": a.clone(), "exp_avg_sq": b.clone()}
+    ctl = controller_on(lambda m: cls(m, MCMCParams(cap_max=10 ** 9), OptimizationParams(), adam="hip"), st)
     ctl.update_learning_rate(1000)
     return ctl
-
-
-def timed(fn):
-    torch.cuda.synchronize()
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    w0 = time.perf_counter()
-    t0.record()
-    out = fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1), (time.perf_counter() - w0) * 1e3, out
-
-
-def stats(ms):
-    return {"min_ms": round(min(ms), 4), "median_ms": round(statistics.median(ms), 4), "max_ms": round(max(ms), 4), "reps": len(ms)}
 
 
 def bench_shape(P, M, reps, warmup, hbm_gbs):
@@ -116,42 +84,18 @@ def bench_shape(P, M, reps, warmup, hbm_gbs):
     return out
 
 
-def bench_train(runs):
-    spec = importlib.util.spec_from_file_location("train_synthetic", os.path.join(ROOT, "scripts", "train_synthetic.py"))
-    ts = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ts)
-    rates = {"hip": [], "mcmc": [], "mcmc_hip": []}
-    last = {}
-    for rep in range(runs + 1):                                       # the first run of each is the warm-up
-        for density in rates:
-            r = ts.run(density=density)
-            last[density] = {k: r[k] for k in ("P_end", "psnr", "loss_last")}
-            if rep:
-                rates[density].append(r["it_per_s"])
-    return {k: {"it_per_s_min": min(v), "it_per_s_median": statistics.median(v), "it_per_s_max": max(v), "runs": len(v), **last[k]} for k, v in rates.items()}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = benchkit.parser(50, 5, "mcmc")
     ap.add_argument("--train-runs", type=int, default=2, help="0: skip the training loop")
     ap.add_argument("--hbm-gbs", type=float, default=8000.0, help="the card's peak HBM bandwidth in GB/s (MI355X: 8 TB/s)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mcmc", "bench.json"))
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("mcmc_bench.py needs a HIP device (nothing is timed on a CPU)")
+    args = benchkit.parse(ap)
     result = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "hbm_gbs": args.hbm_gbs, "shapes": []}
     for P, M in ((1_000_000, 16), (300_000, 4)):
         result["shapes"].append(bench_shape(P, M, args.reps, args.warmup, args.hbm_gbs))
         torch.cuda.empty_cache()
     if args.train_runs > 0:
-        result["train_synthetic"] = bench_train(args.train_runs)
-    line = json.dumps(result)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-    print(line)
+        result["train_synthetic"] = bench_train(args.train_runs, ("hip", "mcmc", "mcmc_hip"))
+    benchkit.write_json(result, args.out, indent=None)
 
 
 if __name__ == "__main__":

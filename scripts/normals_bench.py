@@ -12,11 +12,11 @@ alternating inside every repetition, medians with p10-p90:
 
     python scripts/normals_bench.py [--reps 50] [--warmup 5] [--out profiles/normals/bench.json]
 """
-import argparse, json, os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import json
 import numpy as np
 import torch
+import benchkit
+from benchkit import alternate, stats_quantiles as stats
 from gaussian_transformer_amd import _lib, synth
 from gaussian_transformer_amd.loss import fused_l1_ssim_loss, normal_consistency_loss
 from gaussian_transformer_amd.model import GaussianParams
@@ -25,30 +25,6 @@ from gaussian_transformer_amd.render import PipelineParams, TorchCamera, render
 from tests import normals_ref as nr
 
 HBM_COPY_TBS = 6.29        # float4 copy on an MI355X (the rate a streaming kernel can be held against; the specification says 8.0)
-
-
-def stats(xs):
-    a = np.sort(np.asarray(xs, np.float64))
-    return dict(median_ms=float(np.median(a)), min_ms=float(a[0]), p10_ms=float(np.quantile(a, 0.1)), p90_ms=float(np.quantile(a, 0.9)), n=int(a.size))
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(); fn(); e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def alternate(fns, reps, warmup):
-    """Every function once per repetition, the order rotated from one repetition to the next."""
-    names = list(fns)
-    ts = {k: [] for k in names}
-    for i in range(warmup + reps):
-        for k in names[i % len(names):] + names[:i % len(names)]:
-            ms = timed(fns[k])
-            if i >= warmup:
-                ts[k].append(ms)
-    return ts
 
 
 def bench_loss(H, W, reps, warmup, dev):
@@ -149,14 +125,7 @@ def bench_step(name, reps, warmup, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--configs", nargs="+", default=["cfg2_table_300k_800", "cfg3_synth_1M_1080p"])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "normals", "bench.json"))
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("normals_bench.py measures on a HIP device; none found (no CPU fallback, no number)")
+    args = benchkit.parse(benchkit.parser(50, 5, "normals", configs=True))
     dev = torch.device("cuda:0")
     out = dict(device=torch.cuda.get_device_name(0), reps=args.reps, warmup=args.warmup, hbm_copy_tb_per_s=HBM_COPY_TBS, loss=[], gaussian_normals=[], step=[])
     for H, W in ((800, 800), (1080, 1920)):
@@ -168,10 +137,7 @@ def main():
     for name in args.configs:
         out["step"].append(bench_step(name, args.reps, args.warmup, dev))
         print(json.dumps(out["step"][-1]), flush=True)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print("wrote", args.out)
+    benchkit.write_json(out, args.out)
 
 
 if __name__ == "__main__":

@@ -13,27 +13,18 @@ The two must agree (images equal, gradients within 1e-4 of the largest entry: th
 the script fails.  One JSON line to --out.  Needs a HIP device."""
 from __future__ import annotations
 
-import argparse
 import ctypes as C
-import json
-import os
-import statistics
-import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from gaussian_transformer_amd import _lib, synth  # noqa: E402
-from gaussian_transformer_amd.model import GaussianParams  # noqa: E402
-from gaussian_transformer_amd.rasterizer import arena_floats  # noqa: E402
-from gaussian_transformer_amd.render import PipelineParams, TorchCamera, render_fused  # noqa: E402
-from gaussian_transformer_amd.rows import render_rows  # noqa: E402
-from gaussian_transformer_amd.sequence import flatten_gaussians, unflatten_gaussians  # noqa: E402
+import benchkit
+from gaussian_transformer_amd import _lib, synth
+from gaussian_transformer_amd.model import GaussianParams
+from gaussian_transformer_amd.rasterizer import arena_floats
+from gaussian_transformer_amd.render import PipelineParams, TorchCamera, render_fused
+from gaussian_transformer_amd.rows import render_rows
+from gaussian_transformer_amd.sequence import flatten_gaussians, unflatten_gaussians
 
 P, B, W, H = 65536, 4, 800, 800
 TANFOVX = (0.5773502691896257, 0.5, 0.45, 0.65)
@@ -52,19 +43,6 @@ def rows_step(cams, rows, pipe, bg, G):
 
 
 FORMS = (("views", views_step), ("rows", rows_step))
-
-
-def timed(fn, cams, rows, pipe, bg, G):
-    rows.grad = None
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    images = fn(cams, rows, pipe, bg, G)
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3, images
-
-
-def stats(ms):
-    return {"min_ms": min(ms), "median_ms": statistics.median(ms), "max_ms": max(ms), "steps": len(ms)}
 
 
 def kernel_times(rows, reps=200):
@@ -97,13 +75,7 @@ def kernel_times(rows, reps=200):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rows", "bench.json"))
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("rows_render_bench.py needs a HIP device (nothing is timed on a CPU)")
+    args = benchkit.parse(benchkit.parser(50, 10, "rows", reps_flag="--steps"))
     dev = "cuda:0"
     sc = synth.make_scene(P, W, H, sh_degree=1, s0=0.01, seed=7)
     rows = flatten_gaussians(GaussianParams.from_synthetic(sc, dev, requires_grad=False)).contiguous().requires_grad_()
@@ -114,7 +86,8 @@ def main():
     first = {}
     for step in range(args.warmup + args.steps):
         for name, fn in FORMS:                                            # alternating: both see the same box noise
-            t, images = timed(fn, cams, rows, pipe, bg, G)
+            rows.grad = None
+            _dev_ms, t, images = benchkit.timed_dev_wall(lambda: fn(cams, rows, pipe, bg, G))
             if step == 0:
                 first[name] = ([im.detach().clone() for im in images], rows.grad.clone())
             if step >= args.warmup:
@@ -128,14 +101,10 @@ def main():
         raise SystemExit(f"render_rows and render_fused disagree on the row gradient: {dg:.3e} of the largest entry")
     result = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "what": "forward + backward of B renders from rows, wall ms per step",
               "P": P, "D": int(rows.shape[1]), "B": B, "W": W, "H": H, "warmup": args.warmup,
-              "views": stats(ms["views"]), "rows": stats(ms["rows"]), "grad_max_diff_over_max": dg}
+              "views": benchkit.stats_minmax(ms["views"], count="steps"), "rows": benchkit.stats_minmax(ms["rows"], count="steps"), "grad_max_diff_over_max": dg}
     result["rows_median_over_views_median"] = result["rows"]["median_ms"] / result["views"]["median_ms"]
     result["kernels"] = kernel_times(rows.detach())
-    line = json.dumps(result)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-    print(line)
+    benchkit.write_json(result, args.out, indent=None)
 
 
 if __name__ == "__main__":

@@ -14,23 +14,16 @@ Each pair alternates inside every repetition and is timed with device events aft
 around every timed call; min / median / max in milliseconds.  One JSON line to --out.  Needs a HIP device: no fallback."""
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from gaussian_transformer_amd import sequence as seq, synth  # noqa: E402
-from gaussian_transformer_amd.model import GaussianParams  # noqa: E402
-from gaussian_transformer_amd.render import PipelineParams, TorchCamera, render  # noqa: E402
+import benchkit
+from benchkit import timed_drained as timed
+from gaussian_transformer_amd import sequence as seq, synth
+from gaussian_transformer_amd.model import GaussianParams
+from gaussian_transformer_amd.render import PipelineParams, TorchCamera, render
 
 DEV = "cuda:0"
 
@@ -67,39 +60,15 @@ def loop_box_sort(rows, xyz_col, n):
     return out, filled
 
 
-def timed(fn):
-    torch.cuda.synchronize()
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    out = fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1), out
-
-
-def stats(ms):
-    return {"min_ms": min(ms), "median_ms": statistics.median(ms), "max_ms": max(ms), "reps": len(ms)}
-
-
 def compare(fns, reps, warmup):
-    ms = {k: [] for k in fns}
-    for rep in range(warmup + reps):
-        for name, fn in fns.items():                                  # alternating: both see the same box noise
-            t, _ = timed(fn)
-            if rep >= warmup:
-                ms[name].append(t)
-    return {k: stats(v) for k, v in ms.items()}
+    """alternating, in a fixed order: both see the same box noise"""
+    return {k: benchkit.stats_minmax(v) for k, v in benchkit.alternate(fns, reps, warmup, timed=timed, rotate=False).items()}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = benchkit.parser(20, 3, "sequence")
     ap.add_argument("--no-loop", action="store_true", help="skip the reference's Python loop (about a second at n = 10)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sequence", "bench.json"))
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("sequence_bench.py needs a HIP device (nothing is timed on a CPU)")
+    args = benchkit.parse(ap)
     result = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "box_sort": [], "visible_union": []}
     g = torch.Generator(device=DEV).manual_seed(1)
     for P in (300_000, 1_000_000):
@@ -138,11 +107,7 @@ def main():
             entry = {"config": name, "P": sc.P, "W": W, "H": H, "B": B, "equal_to_render": same}
             entry.update(compare({"hip": lambda: seq.visible_union(cams, pc), "render": by_render}, args.reps, args.warmup))
             result["visible_union"].append(entry)
-    line = json.dumps(result)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-    print(line)
+    benchkit.write_json(result, args.out, indent=None)
 
 
 if __name__ == "__main__":

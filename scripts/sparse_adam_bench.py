@@ -13,11 +13,10 @@ Per case: the bytes the algorithm needs (28 w per visible row plus the mask's by
 
     python scripts/sparse_adam_bench.py [--P 1000000] [--reps 50] [--out profiles/sparse_adam/bench.json]
 """
-import argparse, json, os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import json
 import numpy as np
 import torch
+import benchkit
 from gaussian_transformer_amd import _lib, rasterizer, synth
 from gaussian_transformer_amd.model import GaussianParams
 from gaussian_transformer_amd.render import PipelineParams, TorchCamera, render_fused
@@ -57,11 +56,13 @@ class State:
                    "gsr_adam_step_masked")
 
 
-def stats(xs):
-    return {"median_ms": round(float(np.median(xs)), 4), "min_ms": round(float(np.min(xs)), 4), "max_ms": round(float(np.max(xs)), 4)}
+def summary(xs):
+    """benchkit's min / median / max, the median first: the key order these records have had from the first profile on."""
+    s = benchkit.stats_minmax(xs, count=None, digits=4)
+    return {k: s[k] for k in ("median_ms", "min_ms", "max_ms")}
 
 
-def measure(state, mask, reps, warmup=5):
+def measure(state, mask, reps, warmup):
     dense, masked = [], []
     for it in range(warmup + reps):
         e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
@@ -72,15 +73,15 @@ def measure(state, mask, reps, warmup=5):
     return dense, masked
 
 
-def case(name, state, layout, mask, reps):
+def case(name, state, layout, mask, reps, warmup):
     n_vis = int((mask > 0).sum()) if mask.dtype == torch.int32 else int((mask != 0).sum())
     P = state.P
     need = 28 * sum(WIDTHS) * n_vis + mask.numel() * mask.element_size()
     dense_bytes = 28 * sum(WIDTHS) * P
-    d, m = measure(state, mask, reps)
+    d, m = measure(state, mask, reps, warmup)
     md, mm = float(np.median(d)), float(np.median(m))
     rec = {"case": name, "layout": layout, "P": P, "misaligned_gradient_slices": int(state.misaligned), "mask_dtype": str(mask.dtype).replace("torch.", ""),
-           "visible": n_vis, "visible_fraction": round(n_vis / max(P, 1), 4), "dense": stats(d), "masked": stats(m),
+           "visible": n_vis, "visible_fraction": round(n_vis / max(P, 1), 4), "dense": summary(d), "masked": summary(m),
            "masked_over_dense": round(mm / md, 4), "dense_bytes": dense_bytes, "dense_GBps": round(dense_bytes / md / 1e6, 1),
            "needed_bytes": need, "needed_over_dense_bytes": round(need / dense_bytes, 4), "masked_needed_GBps": round(need / mm / 1e6, 1)}
     print(json.dumps(rec), flush=True)
@@ -113,12 +114,10 @@ def render_masks(config, dev):
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
+    ap = benchkit.parser(50, 5, "sparse_adam")
     ap.add_argument("--P", type=int, default=1_000_000)
-    ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--configs", default="cfg3_synth_1M_1080p,cfg2_table_300k_800")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sparse_adam", "bench.json"))
-    a = ap.parse_args()
+    a = benchkit.parse(ap)
     dev = torch.device("cuda", 0)
     scene_masks = {}
     for cfg in [c for c in a.configs.split(",") if c]:
@@ -133,19 +132,16 @@ if __name__ == "__main__":
             masks = {k: masks[k] for k in ("all rows (bytes)", "random 0.09", "runs of 1024 rows, 9 %")}
         masks.update(scene_masks.get(P, {}))
         for name, mask in masks.items():
-            records.append(case(name, st, layout, mask, a.reps))
+            records.append(case(name, st, layout, mask, a.reps, a.warmup))
         del st
         torch.cuda.empty_cache()
     for P, masks in scene_masks.items():
         if P in (a.P, a.P + 1):
             continue
         st = State(P, "tensors", dev)
-        records.append(case("all rows (bytes)", st, "tensors", torch.ones(P, dtype=torch.uint8, device=dev), a.reps))
+        records.append(case("all rows (bytes)", st, "tensors", torch.ones(P, dtype=torch.uint8, device=dev), a.reps, a.warmup))
         for name, mask in masks.items():
-            records.append(case(name, st, "tensors", mask, a.reps))
+            records.append(case(name, st, "tensors", mask, a.reps, a.warmup))
         del st
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump({"what": "gsr_adam_step vs gsr_adam_step_masked, device events, alternating in one process", "widths": WIDTHS, "reps": a.reps,
-                   "device": torch.cuda.get_device_name(0), "records": records}, f, indent=1)
-    print("wrote", a.out)
+    benchkit.write_json({"what": "gsr_adam_step vs gsr_adam_step_masked, device events, alternating in one process", "widths": WIDTHS, "reps": a.reps,
+                         "device": torch.cuda.get_device_name(0), "records": records}, a.out)

@@ -22,17 +22,13 @@ sys.path.insert(0, ROOT)
 
 def tile_stats(config, dev):
     import torch
-    from gaussian_transformer_amd import GaussianRasterizationSettings, _lib, synth
+    from scripts import benchkit
+    from gaussian_transformer_amd import _lib, synth
     from gaussian_transformer_amd.rasterizer import get_backend
-    from gaussian_transformer_amd.render import TorchCamera
     sc = synth.make_config(config, seed=0)
-    cam = TorchCamera(sc.camera, dev)
     t = lambda a: torch.tensor(a, dtype=torch.float32, device=dev)
-    W, H = cam.image_width, cam.image_height
-    rs = GaussianRasterizationSettings(
-        image_height=H, image_width=W, tanfovx=sc.camera.tanfovx, tanfovy=sc.camera.tanfovy, bg=t(sc.bg), scale_modifier=1.0,
-        viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, sh_degree=sc.sh_degree,
-        campos=cam.camera_center, prefiltered=False, debug=False)
+    rs = benchkit.scene_settings(sc, dev)
+    W, H = rs.image_width, rs.image_height
     be = get_backend()
     empty = torch.empty(0, device=dev)
     N, color, radii, geom, binning, img = be.forward(rs, t(sc.means3D), t(sc.shs), empty, t(sc.opacities), t(sc.scales),

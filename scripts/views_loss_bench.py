@@ -12,19 +12,10 @@ torch's peak allocated memory above what was allocated before the call.  The thr
 formulations of one formula: 1e-4 of the largest gradient) or the script fails.  One JSON line to --out.  Needs a HIP device."""
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from gaussian_transformer_amd import loss  # noqa: E402
+import benchkit
+from gaussian_transformer_amd import loss
 
 SHAPES = [(4, 800, 800), (8, 800, 800), (4, 900, 1600), (8, 900, 1600)]      # B, H, W
 
@@ -58,34 +49,8 @@ def views_form(xs, gts):
 FORMS = (("torch", torch_form), ("fused", fused_form), ("views", views_form))
 
 
-def timed(fn, xs, gts):
-    """One forward + backward between two events -> (ms, peak bytes above the starting allocation, loss, gradients)."""
-    for x in xs:
-        x.grad = None
-    torch.cuda.synchronize()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    L = fn(xs, gts)
-    L.backward()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1), torch.cuda.max_memory_allocated() - base, L.detach()
-
-
-def stats(ms):
-    return {"min_ms": min(ms), "median_ms": statistics.median(ms), "max_ms": max(ms), "reps": len(ms)}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "views_loss", "bench.json"))
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("views_loss_bench.py needs a HIP device (nothing is timed on a CPU)")
+    args = benchkit.parse(benchkit.parser(30, 5, "views_loss"))
     if args.reps < 20:
         raise SystemExit("--reps must be at least 20")
     dev = "cuda:0"
@@ -94,12 +59,22 @@ def main():
         g = torch.Generator(device=dev).manual_seed(B * H + W)
         xs = [(torch.rand(3, H, W, device=dev, generator=g) * 1.5 - 0.25).requires_grad_(True) for _ in range(B)]
         gts = [torch.rand(3, H, W, device=dev, generator=g) for _ in range(B)]
+
+        def clear():
+            for x in xs:
+                x.grad = None
+
+        def call(fn):
+            L = fn(xs, gts)
+            L.backward()
+            return L
         ms = {n: [] for n, _ in FORMS}
         peak = {n: 0 for n, _ in FORMS}
         first = {}
         for rep in range(args.warmup + args.reps):
             for name, fn in FORMS:                                   # alternating: all three see the same box noise
-                t, p, L = timed(fn, xs, gts)
+                t, p, L = benchkit.timed_peak(lambda: call(fn), clear)
+                L = L.detach()                                       # the graph goes now, not under the next call's starting allocation
                 if rep == 0:
                     first[name] = (float(L), [x.grad.clone() for x in xs])
                 if rep >= args.warmup:
@@ -114,7 +89,7 @@ def main():
             if not (dl <= 1e-4 and dg <= 1e-4):
                 raise SystemExit(f"{name} disagrees with torch at B={B} {H}x{W}: loss {dl:.3e}, gradient {dg:.3e}")
         for name in ms:
-            entry[name] = dict(stats(ms[name]), peak_extra_bytes=peak[name])
+            entry[name] = dict(benchkit.stats_minmax(ms[name]), peak_extra_bytes=peak[name])
         v, f = entry["views"], entry["fused"]
         spread = (v["max_ms"] - v["min_ms"]) + (f["max_ms"] - f["min_ms"])
         entry["fused_median_minus_views_median_ms"] = f["median_ms"] - v["median_ms"]
@@ -123,11 +98,7 @@ def main():
         result["shapes"].append(entry)
         del xs, gts, first
         torch.cuda.empty_cache()
-    line = json.dumps(result)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-    print(line)
+    benchkit.write_json(result, args.out, indent=None)
 
 
 if __name__ == "__main__":
